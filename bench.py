@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """LF-MMI forward+backward throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
 
 A step = one ChainLoss forward + backward (denominator + per-utterance numerators,
 x.grad produced) over one synthetic minibatch already resident in HBM.  For N > 1 there is
@@ -20,14 +20,20 @@ is a plain torch function of the shard - no kernels, "value" is meaningless and 
 and checks what sharding can get wrong: every utterance owned once, frames add up, the global
 loss equals the single-process loss (tests/test_bench_launch.py).
 
-Rank 0 prints ONE JSON line: the driver contract plus
+Rank 0 prints ONE JSON line: the driver contract (metric, value, unit, higher_is_better, dtype, ms_per_step = wall
+time of the K timed steps / K) with the configuration, the per-rank view and the sharding checks.  A plain run does only
+that: set up, W warm-up steps, K timed steps, the line.  `--dump-outputs DIR` then writes what the last timed step gave
+its caller (rank 0's shard): the loss and a fixed sample of x.grad, as .npy files (dump_outputs below).
+
+`--full` adds the figures that take runs of their own beside the metric (each `--no-*` option drops one of them):
   "roofline"     for the dominant kernel (the denominator's alpha/beta recursion launch), measured here with
                  HIP events on the launch stream; algorithmic bytes are stated in DESIGN.md §4; `traffic` is
                  the HBM byte count of the SAME launch from the committed rocprofv3 PMC passes
                  (profiles/r*_hbm_traffic.json, `traffic_source` names the file), not re-measured per run;
   "cpu_baseline" the reference's own CPU path (oracle/_ref, kind "reference") or, when that
                  binary is absent, the C restatement (kind "port"), timed on a bounded
-                 sample of the same workload on this box's host cores (N=1 only).
+                 sample of the same workload on this box's host cores (N=1 only);
+  "other_workloads", "host_graph_batch" (N = 1, C3) and "grad_slab_allreduce" (N > 1): see the functions of those names.
 """
 import argparse
 import json
@@ -56,6 +62,11 @@ def parse():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is reported beside the metric: per-kernel rooflines, the CPU baseline, the other "
+                         "workloads, the host graph-batch leg and (N > 1) the gradient-slab all-reduce; off: the metric alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (loss, stats, a fixed sample of x.grad) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-grad-slab", action="store_true",
                     help="skip the optional fused all-reduce of the gradient slab (N > 1 only)")
@@ -644,6 +655,29 @@ def rank_shard(args, world, rank, dev, dry=False):
     return shard, g, idx
 
 
+DUMP_BYTES = 48 << 20          # the sampled gradient rows (the whole dump stays under 64 MB)
+
+
+def dump_outputs(out_dir, loss, stats, x, lengths):
+    """What the last timed step gave its caller, as float32 / float64 .npy files for output-for-output comparison of two
+    builds: the loss, [objf, frames, bad] of the step, and of x.grad a fixed sample of live frame rows (the same rows for the
+    same arguments: drawn from the lengths by a seeded generator) plus every utterance's sum of |grad| over all its rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    g = x.grad.detach()
+    B, T, D = g.shape
+    L = torch.as_tensor(lengths).cpu().long()
+    live = (torch.arange(T)[None, :] < L[:, None]).nonzero()          # (b, t) of every live frame, row-major
+    n = min(int(live.shape[0]), max(1, DUMP_BYTES // (4 * D)))
+    pick = live[torch.randperm(live.shape[0], generator=torch.Generator().manual_seed(0))[:n].sort().values]
+    rows = g[pick[:, 0].to(g.device), pick[:, 1].to(g.device)]
+    arrays = {"loss": loss.detach().double().reshape(1), "stats": stats.detach().double().reshape(-1),
+              "grad_rows": rows.float(), "grad_row_index": pick.double(),
+              "grad_abs_sum_per_utterance": g.abs().sum((1, 2), dtype=torch.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def workload_label(args, cfg, world, local_frames, global_frames):
     name = "C5" if (args.workload == "C3" and world == 8) else (args.workload if world == 1 else "%sx%d" % (args.workload, world))
     what = "%d pdfs, den %d states/%d arcs%s" % (cfg["D"], cfg["H"], cfg["K"], " + per-utt log-domain numerators" if cfg["num"] else "")
@@ -715,6 +749,8 @@ def main():
     fence()
     dt = time.perf_counter() - t0
     stats = loss_fn.last_stats
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, stats, x, w["lengths"])
     # per-rank view (imbalance between the shards is the only thing that can cost the scaling): each rank's own time
     # for the K steps, its frame count, its longest sequence and its utterance count, gathered once after the timed region
     mine = torch.tensor([dt, float(local_frames), float(w["lengths"].max()), float(idx.numel())], device=dev, dtype=torch.float64)
@@ -736,7 +772,7 @@ def main():
     n_bad = int(stats[2])
     global_frames = int(glob["lengths"].sum())
     slab = None
-    if world > 1 and not args.no_grad_slab and not dry:
+    if args.full and world > 1 and not args.no_grad_slab and not dry:
         try:
             slab = grad_slab_allreduce(x, idx, cfg["B_global"], dev)
         except Exception as e:      # an option beside the metric: never lose the bench line to it
@@ -776,7 +812,7 @@ def main():
                 "per_rank": per_rank_out, "sharding": sharding, "config": config}))
         else:
             # (N > 1: the other ranks idle in a barrier behind this: 3 launches per kernel there, ~50 ms)
-            roof = None if args.no_rooflines else kernel_rooflines(w, dev, 3 if world > 1 else max(3, min(args.steps, 10)), d2d=world == 1,
+            roof = None if (args.no_rooflines or not args.full) else kernel_rooflines(w, dev, 3 if world > 1 else max(3, min(args.steps, 10)), d2d=world == 1,
                                                                    step_ms=dt / args.steps * 1e3 if world == 1 else None)
             out = {
                 "metric": "LF-MMI frames/sec (fwd+bwd)", "value": round(total_frames * args.steps / dt, 1),
@@ -786,15 +822,15 @@ def main():
                 "n_bad": n_bad, "roofline": roof, "per_rank": per_rank_out, "sharding": sharding,
             }
             if roof is None:
-                out["roofline_note"] = "per-kernel rooflines skipped (--no-rooflines)"
+                out["roofline_note"] = "per-kernel rooflines skipped (%s)" % ("--no-rooflines" if args.full else "measured with --full")
             if slab is not None:
                 out["grad_slab_allreduce"] = slab
-            if world == 1 and cfg["num"] and not args.no_fresh_num_graphs:
+            if args.full and world == 1 and cfg["num"] and not args.no_fresh_num_graphs:
                 try:
                     out["host_graph_batch"] = fresh_num_graphs(w, dev)
                 except Exception as e:
                     out["host_graph_batch"] = {"error": str(e)[:200]}
-            if world == 1 and not args.no_other_workloads and args.workload == "C3":
+            if args.full and world == 1 and not args.no_other_workloads and args.workload == "C3":
                 keep = {k: w[k] for k in ("cfg", "lengths", "den_graph", "num_graphs")}
                 x_cpu = w["x"].detach().float().cpu() if not args.no_cpu_baseline else None
                 del x
@@ -804,7 +840,7 @@ def main():
                 if x_cpu is not None:
                     keep["x"] = x_cpu
                 w = keep
-            if world == 1 and not args.no_cpu_baseline:
+            if args.full and world == 1 and not args.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline(w, args.cpu_sample)
             print(json.dumps(out))
     if use_dist:

@@ -108,7 +108,9 @@ def chain_function(x, lengths, gb, leaky_coef=1e-5, flavour="f32"):
     returns (objf scalar, input_grad[B,T,D])."""
     xc = torch.as_tensor(x).detach().cpu().float().contiguous().clamp(-30, 30)
     if not gb.log_domain:
-        o, g, _ = den(gb, xc.exp(), lengths, leaky_coef, flavour=flavour)
+        # (exp in float64, rounded once to float32: the same bits on every host - a vectorised float32 exp can differ in the
+        # last bit from one CPU to another, and the fp64 flavour reproduces its stored results to 1e-12: tests/test_oracle.py)
+        o, g, _ = den(gb, xc.double().exp().float(), lengths, leaky_coef, flavour=flavour)
         return o.sum(), g
     o, lg, _ = num(gb, xc, lengths, shared=getattr(gb, "shared_graph", None) is not None,
                    flavour=flavour)

@@ -87,3 +87,24 @@ def test_eight_ranks_as_the_scaling_run_will_start_them():
     assert j["n_gpus"] == 8 and j["config"]["parallelism"].endswith("dp8")
     _check_sharded(j, 8)
     assert "C5: global B=" in j["config"]["workload"] and "batch-sharded over 8 GPUs" in j["config"]["workload"]
+
+
+def test_dump_outputs_writes_the_last_step_the_same_every_run(tmp_path):
+    """--dump-outputs DIR: what the last timed step gave its caller, float32 / float64 .npy files, identical for the same
+    arguments (two builds are compared output for output on them)."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--dry-run", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, env=_env(), timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _last_json(r.stdout)
+        dumps.append({f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))})
+    a, b = dumps
+    assert {"loss.npy", "stats.npy", "grad_rows.npy"} <= set(a) and set(a) == set(b)
+    assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert abs(float(a["loss.npy"][0]) - j["loss"]) <= 1e-6 * abs(j["loss"])
+    assert a["grad_rows.npy"].shape[0] == j["global_frames"]          # (tiny shapes: every live frame row is in the sample)

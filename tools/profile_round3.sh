@@ -7,7 +7,7 @@
 tag=$1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
 cd /tmp && export TMPDIR=/tmp
 for wl in C3 C4; do
   rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_$wl -o bench -- python $R/bench.py --workload $wl $B > $O/prof_${tag}_$wl.log 2>&1

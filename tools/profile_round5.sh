@@ -7,7 +7,7 @@
 tag=$1
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
 cd /tmp && export TMPDIR=/tmp
 # C3 is the fused loss: its recursions exp their rows themselves (den_dma = 2 in the calls of the denominator alone that the
 # counter passes time); C4 is a call of the denominator alone: rows exp'd ahead by den_exp_rows_kernel, as shipped

@@ -21,7 +21,7 @@ for lb in $labels; do
   done
 done
 unset PYCHAIN_DEN_SEGMENTS
-B="--steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
+B="--full --steps 5 --warmup 2 --no-cpu-baseline --no-other-workloads --no-fresh-num-graphs"
 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_C3 -o bench -- python $R/bench.py --workload C3 $B > $O/prof_${tag}_C3.log 2>&1
 PYCHAIN_DEN_SEGMENTS=1 rocprofv3 --kernel-trace --stats -d $O/prof_${tag}_C3_unseg -o bench -- python $R/bench.py --workload C3 $B > $O/prof_${tag}_C3_unseg.log 2>&1
 cd $R

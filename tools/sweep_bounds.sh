@@ -1,6 +1,6 @@
 #!/bin/bash
 # segment-schedule experiments: ms per step and per denominator call
-run() { echo -n "$1 segs=$2 bounds=$3 relaunch=$4 : "; env PYCHAIN_DEN_SEGMENTS=$2 PYCHAIN_DEN_BOUNDS=$3 ${4:+PYCHAIN_DEN_RELAUNCH=1} timeout 200 python bench.py --workload $1 --steps ${STEPS:-30} --warmup 6 --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['den_forward_backward']['ms'])"; }
+run() { echo -n "$1 segs=$2 bounds=$3 relaunch=$4 : "; env PYCHAIN_DEN_SEGMENTS=$2 PYCHAIN_DEN_BOUNDS=$3 ${4:+PYCHAIN_DEN_RELAUNCH=1} timeout 200 python bench.py --workload $1 --steps ${STEPS:-30} --warmup 6 --full --no-cpu-baseline 2>&1 | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['roofline']['den_forward_backward']['ms'])"; }
 if [ $# -gt 0 ]; then run "$@"; exit; fi
 run C3 3 "" 1
 run C3 3 ""
