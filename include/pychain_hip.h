@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 17
+#define PYCHAIN_HIP_ABI_VERSION 18
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -337,6 +337,45 @@ int pychain_hip_num_forward_backward(
 /* 1 if the numerator's recursions read 2-byte network outputs for this shape (the tile kernels' float4-chunk forms; not the
  * general kernels, not option num_compat).  The gradient of pychain_hip_num_forward_backward stays fp32. */
 int pychain_hip_num_half_native(int num_states, int num_transitions, int num_pdfs);
+
+/* ------------------------------------------------------------------------
+ * Viterbi forced alignment over log-domain numerator graphs (ABI 18): the best path through each sequence's graph.  Graphs,
+ * graph_batch_stride, nnet_output (raw, clamped to [-30, 30] in-kernel) and the shapes as in pychain_hip_num_forward_backward;
+ * only the backward-transition arrays (the arcs entering each state), initial_probs and final_probs are read.
+ * Let x be the clamped input widened to fp64 and take the arcs entering h in the order of backward_transition_indices[h] = [lo, hi)
+ * (columns src, dst, pdf; log-prob lp).  Then, in fp64 adds and compares only (no contraction, no transcendental):
+ *   s(0,h)   = initial(h)
+ *   s(t+1,h) = max over k in [lo,hi) of  s(t,src_k) + ((double)lp_k + x(t,pdf_k))     exactly this association;
+ *              ties: the FIRST k in list order wins (a later arc replaces only on strictly greater); no arc: -inf
+ *   score    = max over h of s(L,h) + (double)final(h)                                 ties: the lowest h
+ * Outputs (dev; the host twin: host):
+ *   score_per_seq[b]  double [B]: the best-path log-score, final weight included.  NaN (0x7ff8000000000000) if an arc of the
+ *                     sequence's graph emits a NaN column of x at some frame t < L; -inf if no path of length L reaches a final state
+ *   states[b][t]      int32 [B,T+1]: the state occupied before frame t, t = 0..L (states[b][L] = the final state); -1 beyond
+ *   pdfs[b][t]        int64 [B,T]: the pdf of the arc taken from frame t to t+1; -1 for t >= L
+ *   A sequence whose score is not finite has every row -1.  bad_count (dev int32[1]): sequences whose score is not finite,
+ *   plus device-resident lengths outside [1, T] (the kernels clamp them).
+ * The device and the host twin give the same bits.  Graphs the tile kernels take (pychain_hip_num_half_native's shapes) keep
+ * uint16 backpointers (2 B T H bytes of workspace); larger ones run on a global-memory kernel with int32 backpointers.
+ * 2-byte network outputs: pychain_hip_align_half_native says where the kernels read them as they are (else up-cast first).
+ * pychain_hip_cpu_align: fp32 input, host threads as the other host twins. */
+size_t pychain_hip_align_workspace_bytes(int B, int T, int num_states, int num_transitions, int num_pdfs);
+int pychain_hip_align(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream);
+int pychain_hip_align_half_native(int num_states, int num_transitions, int num_pdfs);
+int pychain_hip_cpu_align(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 17
+ABI_VERSION = 18
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -59,6 +59,10 @@ _SIGNATURES = {
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),
+    "pychain_hip_align_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pychain_hip_align": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pychain_hip_align_half_native": (_i, [_i, _i, _i]),
+    "pychain_hip_cpu_align": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
     "pychain_hip_den_tseg_state": (_i, [_vp, _vp]),
     "pychain_hip_den_tseg_state_bytes": (_sz, []),
     "pychain_hip_rescale": (_i, [_vp, _i, _sz, _vp, _vp]),

@@ -1,0 +1,459 @@
+// align.hip - Viterbi (best-path) alignment over log-domain numerator graphs for gfx950: the max-plus sibling of the
+// numerator's forward pass (num_kernels.hip: num_fb_kernel), followed by a backtrace.
+//
+//   align_kernel           B persistent workgroups, one per sequence.  Forward: one state per thread, the sequence's arcs by
+//                          destination in LDS, fp64 ping-pong score vectors, row-staging waves, ONE barrier per frame; per
+//                          frame every state writes the offset of its winning arc inside its [lo, hi) as a uint16
+//                          backpointer row (2 H bytes, coalesced).  Then a workgroup argmax over s(L,.) + final and the
+//                          backtrace in the same workgroup: blocks of backpointer rows are read back by all but the first
+//                          wave, turned into the winning arc's packed (state, pdf) and staged in LDS, while one lane walks the
+//                          previous block inside LDS (one dependent LDS read per frame) - double-buffered, one barrier per block.
+//   align_general_kernel   graphs beyond the tile kernels (num_needs_general): score vectors and int32 backpointers in the
+//                          workspace, states strided over 1024 threads, a barrier per frame, a plain walk at the end.
+//
+// Both reach the same bits as the host twin (cpu.cpp: align_one): fp64 adds and compares only, in the association
+//   s(t+1,h) = max_k  s(t,src_k) + ((double)lp_k + (double)clamp(x(t,pdf_k)))      (first k in list order wins ties)
+//   score    = max_h  s(L,h) + (double)final(h)                                      (lowest h wins ties)
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/pychain_hip.h"
+#include "align.h"
+#include "common.h"
+#include "device_utils.h"
+#include "num_kernels.h"
+
+namespace pychain_hip {
+namespace {
+
+constexpr int kAlNT = 512;                 // threads that own states (one state per thread up to 512 states)
+constexpr int kAlLd = 128;                 // row-staging threads (num_kernels.hip: kFbLd)
+constexpr int kAlPre = 24;                 // backpointers a converting thread holds in registers per block
+constexpr int kAlWalkCap = 96 * 1024;      // LDS the backtrace stages rows in, at most (more where the forward's buffers are larger)
+constexpr int kAlGT = 1024;                // align_general_kernel
+
+struct AArc { uint32_t pk; float lp; };    // pk = src | pdf << 16
+
+__device__ __forceinline__ double canonical_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// a word written by another thread of this workgroup before the last barrier: read around the vector L1 (num_general.hip: fresh)
+__device__ __forceinline__ uint32_t fresh_u32(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ int32_t fresh_i32(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ double fresh_f64(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// torch.clamp(x, -30, 30) keeps a NaN (pychain/loss.py:30): so does this
+__device__ __forceinline__ float aclamp(float x) { return x != x ? x : fminf(fmaxf(x, -30.f), 30.f); }
+
+// (value, index) with the larger value; equal values: the lower index.  NaN never enters (the callers skip it).
+__device__ __forceinline__ void argmax_merge(double& v, int& i, double ov, int oi) {
+  if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+}
+__device__ __forceinline__ void wave_argmax(double& v, int& i) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const double ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    argmax_merge(v, i, ov, oi);
+  }
+}
+
+// -1 into every row of sequence b the path does not cover (all of them where there is no path)
+__device__ __forceinline__ void pad_rows(const AlignArgs& a, int b, int L, bool ok, int tid, int nt) {
+  int64_t* pd = a.pdfs + (size_t)b * a.T;
+  int32_t* st = a.states + (size_t)b * (a.T + 1);
+  for (int t = (ok ? L : 0) + tid; t < a.T; t += nt) pd[t] = -1;
+  for (int t = (ok ? L + 1 : 0) + tid; t <= a.T; t += nt) st[t] = -1;
+}
+
+template <int VEC, int XCH, int LD, bool XH = false>
+__global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
+  constexpr int NTOT = kAlNT + LD;
+  constexpr int NW = NTOT / 64;
+  constexpr size_t kXe = XH ? 2 : 4;
+  const bool bf16 = a.x_half == kXBf16;
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int b = blockIdx.x;
+  const int L = __builtin_amdgcn_readfirstlane(seq_len(a.lengths, b, a.T));
+  const int H = a.H, K = a.K, D = a.D, T = a.T, Dp = (D + 3) & ~3;
+  const size_t g = (size_t)b * a.graph_stride;
+
+  // ---- LDS: [score vectors (fp64, ping-pong), nnet-output rows (ping-pong) | reused by the backtrace] [reductions] [arcs]
+  char* p = smem_raw;
+  const int Hq = (H + 1) & ~1;
+  char* walk = p;
+  double* va = reinterpret_cast<double*>(p);
+  double* vb = va + Hq;
+  float* xr0 = reinterpret_cast<float*>(vb + Hq);
+  float* xr1 = xr0 + Dp;
+  p += a.walk_bytes;
+  double* redd = reinterpret_cast<double*>(p); p += 8 * 16;
+  int* redi = reinterpret_cast<int*>(p); p += 4 * 16;    // a wave's argmax, -1 where it met a NaN
+  AArc* arc = reinterpret_cast<AArc*>(p); p += 8 * (size_t)K;     // by destination: (src, pdf, lp)
+  {
+    const int32_t* tr = a.bwd_trans + g * K * 3;
+    const float* pr = a.bwd_probs + g * K;
+    for (int k = tid; k < K; k += NTOT) arc[k] = AArc{(uint32_t)tr[3 * k] | ((uint32_t)tr[3 * k + 2] << 16), pr[k]};
+  }
+  const float* xseq = reinterpret_cast<const float*>(reinterpret_cast<const char*>(a.x) + (size_t)b * T * D * kXe);
+  const XBuf xbuf = make_xbuf(xseq, (size_t)T * D * kXe);
+  auto xload = [&](auto& xr, int t, int ti) {
+    if constexpr (XH) xr.load_h(reinterpret_cast<const char*>(xseq) + (size_t)t * D * 2, D, ti);
+    else xr.load(xseq + (size_t)t * D, D, ti);
+  };
+  auto xload_row = [&](auto& xr, int t, int ti) {
+    if constexpr (XH) xr.load_row_h(xbuf, t, D, ti);
+    else xr.load_row(xbuf, t, D, ti);
+  };
+  // a row, clamped, into LDS; a NaN stays a NaN (it makes the arc terms that read it NaN: the per-thread flag below)
+  auto stage = [&](auto& xr, float* lds, const float* row, int t) {
+    if constexpr (XH) xr.convert_h(bf16);
+    xr.store(lds, row, D, t, kXClamp);
+  };
+  uint16_t* bps = a.bp16 + (size_t)b * T * a.Hb;
+  const int2* idx = reinterpret_cast<const int2*>(a.bwd_idx + g * H * 2);
+
+  const int h0 = tid;
+  const bool own = h0 < H && tid < kAlNT;
+  int2 be = make_int2(0, 0);
+  if (own) be = idx[h0];
+  XRow<LD ? LD : kAlNT, VEC, XCH> xq;
+  const int xt = LD ? tid - kAlNT : tid;
+  {
+    const float* xrow = XH ? nullptr : xseq;
+    if (!LD || tid >= kAlNT) xload(xq, 0, xt);
+    if (tid < kAlNT)
+      for (int h = tid; h < H; h += kAlNT) va[h] = (double)a.initial[g * H + h];
+    if (!LD || tid >= kAlNT) stage(xq, xr0, xrow, xt);
+  }
+  __syncthreads();
+  int nanf = 0;
+  if (LD > 0 && tid >= kAlNT) {
+    if constexpr (LD > 0) {
+      // ---- row-staging waves (num_kernels.hip: num_fb_kernel): step s reads xr0 (s odd) / xr1 (s even)
+      static_assert(VEC == 4 && XCH > 0, "row-staging waves use the float4 buffer-load form");
+      XRow<LD, VEC, XCH> xq2;
+      auto row_of_step = [&](int s) { return min(s, L) - 1; };
+      xload_row(xq, row_of_step(2), xt);
+      for (int s = 1; s <= L; s += 2) {
+        xload_row(xq2, row_of_step(s + 2), xt);
+        stage(xq, xr1, nullptr, xt);                 // row of step s+1
+        __syncthreads();
+        if (s + 1 <= L) {
+          xload_row(xq, row_of_step(s + 3), xt);
+          stage(xq2, xr0, nullptr, xt);              // row of step s+2
+          __syncthreads();
+        }
+      }
+    }
+  } else {
+    AArc w0{0u, 0.f}, w1{0u, 0.f};
+    const int n0 = be.y - be.x;
+    if (own) {
+      if (n0 > 0) w0 = arc[be.x];
+      if (n0 > 1) w1 = arc[be.x + 1];
+    }
+    // s(t+1,h) = max_k s(t,src_k) + (lp_k + x(t,pdf_k)), t = s - 1
+    for (int s = 1; s <= L; s++) {
+      const double* vin = (s & 1) ? va : vb;
+      double* vout = (s & 1) ? vb : va;
+      const float* xcur = (s & 1) ? xr0 : xr1;
+      float* xnext = (s & 1) ? xr1 : xr0;
+      const bool have_next = s < L;
+      const int t_next = have_next ? s : 0;
+      const float* xrow_next = XH ? nullptr : xseq + (size_t)t_next * D;
+      uint16_t* brow = bps + (size_t)(s - 1) * a.Hb;
+      if (!LD && have_next) {
+        if constexpr (VEC == 4 && XCH > 0) xload_row(xq, t_next, tid);
+        else xq.load(xrow_next, D, tid);
+      }
+      if (own) {
+        double best = -INFINITY;
+        int bi = 0;
+        if (n0 > 0) {
+          best = vin[w0.pk & 0xffffu] + ((double)w0.lp + (double)xcur[w0.pk >> 16]);
+          nanf |= best != best;
+        }
+        if (n0 > 1) {
+          const double e = vin[w1.pk & 0xffffu] + ((double)w1.lp + (double)xcur[w1.pk >> 16]);
+          nanf |= e != e;
+          if (e > best) { best = e; bi = 1; }
+        }
+        for (int k = be.x + 2; k < be.y; k++) {
+          const AArc w = arc[k];
+          const double e = vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]);
+          nanf |= e != e;
+          if (e > best) { best = e; bi = k - be.x; }
+        }
+        vout[h0] = best;
+        brow[h0] = (uint16_t)bi;
+      }
+      for (int h = h0 + kAlNT; h < H; h += kAlNT) {             // graphs with more than 512 states
+        const int2 e2 = idx[h];
+        double best = -INFINITY;
+        int bi = 0;
+        for (int k = e2.x; k < e2.y; k++) {
+          const AArc w = arc[k];
+          const double e = vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]);
+          nanf |= e != e;
+          if (k == e2.x || e > best) { best = e; bi = k - e2.x; }
+        }
+        vout[h] = best;
+        brow[h] = (uint16_t)bi;
+      }
+      if (!LD && have_next) stage(xq, xnext, xrow_next, tid);
+      __syncthreads();
+    }
+  }
+
+  // ---- score = max_h s(L,h) + final(h), the lowest h on ties; NaN if any arc term was NaN
+  const double* vL = (L & 1) ? vb : va;
+  double mx = -INFINITY;
+  int mi = 0x7fffffff;
+  if (tid < kAlNT)
+    for (int h = tid; h < H; h += kAlNT) {
+      const double e = vL[h] + (double)a.final_[g * H + h];
+      nanf |= e != e;
+      if (e > mx) { mx = e; mi = h; }
+    }
+  wave_argmax(mx, mi);
+  const int wnan = __builtin_amdgcn_ballot_w64(nanf != 0) != 0;
+  if (lane == 0) { redd[wave] = mx; redi[wave] = wnan ? -1 : mi; }
+  __threadfence();                                     // (the backpointer rows reach L2 before anyone reads them back)
+  __syncthreads();
+  double best = redd[0];
+  int hstar = redi[0], anynan = redi[0] < 0;
+#pragma unroll
+  for (int w = 1; w < NW; w++) { argmax_merge(best, hstar, redd[w], redi[w]); anynan |= redi[w] < 0; }
+  const double score = anynan ? canonical_nan() : best;
+  const bool ok = !anynan && best > -INFINITY && best < INFINITY;
+  if (tid == 0) {
+    a.score[b] = score;
+    if (!ok || seq_len_bad(a.lengths, b, T)) atomicAdd(a.bad, 1);
+  }
+  pad_rows(a, b, L, ok, tid, NTOT);
+  if (!ok) return;                                     // (uniform over the workgroup)
+  int64_t* pd = a.pdfs + (size_t)b * T;
+  int32_t* st = a.states + (size_t)b * (T + 1);
+  if (tid == 0) st[L] = hstar;
+
+#if PYCHAIN_EXP_ALIGN_NAIVE_WALK
+  // measurement variant: one lane walks the backpointers where the forward left them (a dependent global load per frame)
+  if (tid == 0) {
+    int h = hstar;
+    for (int t = L - 1; t >= 0; t--) {
+      const size_t q = (size_t)t * a.Hb + h;
+      const uint32_t wd = fresh_u32(reinterpret_cast<const uint32_t*>(bps) + (q >> 1));
+      const int off = (q & 1) ? (int)(wd >> 16) : (int)(wd & 0xffffu);
+      const uint32_t pk = arc[idx[h].x + off].pk;
+      pd[t] = (int64_t)(pk >> 16);
+      h = (int)(pk & 0xffffu);
+      st[t] = h;
+    }
+  }
+#else
+  // ---- backtrace over blocks of F frames from the end: iteration j, one barrier each:
+  //   waves 1.. : backpointer rows of block j -> the winning arc's pk (src | pdf << 16) into tab[j & 1];
+  //               the path of block j - 2 (path[j & 1]) out to states / pdfs, coalesced
+  //   lane 0    : walks block j - 1 inside tab[(j - 1) & 1], one dependent LDS read per frame, into path[(j - 1) & 1]
+  constexpr int nconv = NTOT - 64;
+  int F = a.walk_bytes / (8 * H + 8);
+  F = min(F, kAlPre * nconv / H);
+  F = max(F, 1);
+  uint32_t* tab0 = reinterpret_cast<uint32_t*>(walk);
+  uint32_t* tab1 = tab0 + (size_t)F * H;
+  uint32_t* path0 = tab1 + (size_t)F * H;
+  uint32_t* path1 = path0 + F;
+  const int nblk = (L + F - 1) / F;
+  const uint32_t* bpw = reinterpret_cast<const uint32_t*>(bps);
+  int h = hstar;                                       // (lane 0's walk position: the state at the end of the next block)
+  for (int j = 0; j <= nblk + 1; j++) {
+    if (tid >= 64) {
+      const int c = tid - 64;
+      if (j < nblk) {
+        const int hi = L - j * F, lo = max(hi - F, 0), ne = (hi - lo) * H;
+        uint32_t* tab = (j & 1) ? tab1 : tab0;
+        uint32_t wv[kAlPre];
+        int lov[kAlPre], hv[kAlPre];
+#pragma unroll
+        for (int i = 0; i < kAlPre; i++) {
+          const int e = c + i * nconv;
+          if (e < ne) {
+            const int r = e / H, hh = e - r * H;
+            hv[i] = hh;
+            wv[i] = fresh_u32(bpw + (((size_t)(lo + r) * a.Hb + hh) >> 1));
+            lov[i] = idx[hh].x;
+          }
+        }
+#pragma unroll
+        for (int i = 0; i < kAlPre; i++) {
+          const int e = c + i * nconv;
+          if (e < ne) {
+            const int off = (hv[i] & 1) ? (int)(wv[i] >> 16) : (int)(wv[i] & 0xffffu);     // (Hb even: a row starts a word)
+            tab[e] = arc[min(lov[i] + off, K - 1)].pk;      // (states no path enters may point anywhere: kept in range)
+          }
+        }
+      }
+      if (j >= 2) {
+        const int jj = j - 2, hi = L - jj * F, lo = max(hi - F, 0);
+        const uint32_t* path = (jj & 1) ? path1 : path0;
+        for (int i = c; i < hi - lo; i += nconv) {
+          const uint32_t pk = path[i];
+          st[lo + i] = (int32_t)(pk & 0xffffu);
+          pd[lo + i] = (int64_t)(pk >> 16);
+        }
+      }
+    } else if (tid == 0 && j >= 1 && j <= nblk) {
+      const int jj = j - 1, hi = L - jj * F, lo = max(hi - F, 0);
+      const uint32_t* tab = (jj & 1) ? tab1 : tab0;
+      uint32_t* path = (jj & 1) ? path1 : path0;
+      for (int t = hi - 1; t >= lo; t--) {
+        const uint32_t pk = tab[(t - lo) * H + h];
+        path[t - lo] = pk;
+        h = (int)(pk & 0xffffu);
+      }
+    }
+    __syncthreads();
+  }
+#endif
+}
+
+// ------------------------------------------------------------------------------------
+// graphs beyond the tile kernel: everything in global memory
+// ------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a) {
+  __shared__ double redd[kAlGT / 64];
+  __shared__ int redi[kAlGT / 64], redn[kAlGT / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int b = blockIdx.x;
+  const int L = seq_len(a.lengths, b, a.T);
+  const int H = a.H, K = a.K, D = a.D, T = a.T;
+  const size_t g = (size_t)b * a.graph_stride;
+  const int32_t* tr = a.bwd_trans + g * K * 3;
+  const float* pr = a.bwd_probs + g * K;
+  const int2* idx = reinterpret_cast<const int2*>(a.bwd_idx + g * H * 2);
+  const float* xseq = a.x + (size_t)b * T * D;
+  double* sc = a.gen_sc + (size_t)b * 2 * H;
+  int32_t* bps = a.bp32 + (size_t)b * T * H;
+  for (int h = tid; h < H; h += kAlGT) sc[h] = (double)a.initial[g * H + h];
+  __threadfence();
+  __syncthreads();
+  int nanf = 0;
+  for (int s = 1; s <= L; s++) {
+    const double* vin = sc + (size_t)((s - 1) & 1) * H;
+    double* vout = sc + (size_t)(s & 1) * H;
+    const float* xrow = xseq + (size_t)(s - 1) * D;
+    int32_t* brow = bps + (size_t)(s - 1) * H;
+    for (int h = tid; h < H; h += kAlGT) {
+      const int2 be = idx[h];
+      double best = -INFINITY;
+      int bi = 0;
+      for (int k = be.x; k < be.y; k++) {
+        const double e = fresh_f64(vin + tr[3 * k]) + ((double)pr[k] + (double)aclamp(xrow[tr[3 * k + 2]]));
+        nanf |= e != e;
+        if (k == be.x || e > best) { best = e; bi = k - be.x; }
+      }
+      vout[h] = best;
+      brow[h] = bi;
+    }
+    __threadfence();
+    __syncthreads();
+  }
+  const double* vL = sc + (size_t)(L & 1) * H;
+  double mx = -INFINITY;
+  int mi = 0x7fffffff;
+  for (int h = tid; h < H; h += kAlGT) {
+    const double e = fresh_f64(vL + h) + (double)a.final_[g * H + h];
+    nanf |= e != e;
+    if (e > mx) { mx = e; mi = h; }
+  }
+  wave_argmax(mx, mi);
+  const int wnan = __builtin_amdgcn_ballot_w64(nanf != 0) != 0;
+  if (lane == 0) { redd[wave] = mx; redi[wave] = mi; redn[wave] = wnan; }
+  __syncthreads();
+  double best = redd[0];
+  int hstar = redi[0], anynan = redn[0];
+  for (int w = 1; w < kAlGT / 64; w++) { argmax_merge(best, hstar, redd[w], redi[w]); anynan |= redn[w]; }
+  const bool ok = !anynan && best > -INFINITY && best < INFINITY;
+  if (tid == 0) {
+    a.score[b] = anynan ? canonical_nan() : best;
+    if (!ok || seq_len_bad(a.lengths, b, T)) atomicAdd(a.bad, 1);
+  }
+  pad_rows(a, b, L, ok, tid, kAlGT);
+  if (!ok || tid != 0) return;
+  int64_t* pd = a.pdfs + (size_t)b * T;
+  int32_t* st = a.states + (size_t)b * (T + 1);
+  st[L] = hstar;
+  int h = hstar;
+  for (int t = L - 1; t >= 0; t--) {
+    const int k = idx[h].x + fresh_i32(bps + (size_t)t * H + h);
+    pd[t] = (int64_t)tr[3 * k + 2];
+    h = tr[3 * k];
+    st[t] = h;
+  }
+}
+
+template <int VEC, int XCH, int LD, bool XH>
+hipError_t launch_align_x(const AlignArgs& a, size_t lds, hipStream_t st) {
+  auto k = align_kernel<VEC, XCH, LD, XH>;
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3(a.B), dim3(kAlNT + LD), lds, st, a);
+  return hipGetLastError();
+}
+template <int VEC, int XCH, int LD = 0>
+hipError_t launch_align_t(const AlignArgs& a, size_t lds, hipStream_t st) {
+  if (a.x_half) {
+    if constexpr (VEC == 4 && XCH > 0) return launch_align_x<VEC, XCH, LD, true>(a, lds, st);
+    else return hipErrorInvalidValue;
+  }
+  return launch_align_x<VEC, XCH, LD, false>(a, lds, st);
+}
+
+size_t align_fixed_lds_bytes(int K) { return 8 * 16 + 4 * 16 + 8 * (size_t)K + 64; }     // (with the forward's region: num_fb_lds_bytes)
+
+}  // namespace
+
+// the region the forward's score vectors and rows live in, enlarged (up to kAlWalkCap, within the 160 KiB) for the backtrace
+int align_walk_bytes(int H, int K, int D) {
+  const size_t Dp = (D + 3) & ~3, Hq = (H + 1) & ~1;
+  const size_t fwd = 16 * Hq + 8 * Dp;
+  const size_t room = 160 * 1024 > align_fixed_lds_bytes(K) ? 160 * 1024 - align_fixed_lds_bytes(K) : 0;
+  size_t w = kAlWalkCap < room ? kAlWalkCap : room;
+  if (w < fwd) w = fwd;
+  return (int)((w + 15) & ~(size_t)15);
+}
+size_t align_lds_bytes(int H, int K, int D) { return (size_t)align_walk_bytes(H, K, D) + align_fixed_lds_bytes(K); }
+
+hipError_t launch_align(const AlignArgs& a, hipStream_t st, const char** why) {
+  if (a.general) {
+    hipLaunchKernelGGL(align_general_kernel, dim3(a.B), dim3(kAlGT), 0, st, a);
+    return hipGetLastError();
+  }
+  const size_t lds = align_lds_bytes(a.H, a.K, a.D);
+  if (lds > 160 * 1024) {
+    *why = "numerator graph + nnet-output rows do not fit the 160 KiB LDS of one CU";
+    return hipErrorInvalidValue;
+  }
+  if (a.x_half && (a.D % 4 != 0 || a.D > 4 * 8 * kAlNT)) {
+    *why = "2-byte network outputs need rows of a multiple of four pdfs within the register-staged forms";
+    return hipErrorInvalidValue;
+  }
+  if ((size_t)a.T * a.D * 4 >= (size_t)1 << 31) {
+    *why = "one sequence's nnet-output slab reaches 2 GiB";
+    return hipErrorInvalidValue;
+  }
+  const int D = a.D;
+  if (D % 4 == 0) {
+    if (D <= 4 * 4 * kAlLd) return launch_align_t<4, 4, kAlLd>(a, lds, st);
+    if (D <= 4 * 8 * kAlLd) return launch_align_t<4, 8, kAlLd>(a, lds, st);
+    if (D <= 4 * 2 * kAlNT) return launch_align_t<4, 2>(a, lds, st);
+    if (D <= 4 * 8 * kAlNT) return launch_align_t<4, 8>(a, lds, st);
+  } else if (D <= 8 * kAlNT) {
+    return launch_align_t<1, 8>(a, lds, st);
+  }
+  return launch_align_t<1, 0>(a, lds, st);
+}
+
+}  // namespace pychain_hip

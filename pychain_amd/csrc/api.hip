@@ -11,6 +11,7 @@
 #include <string>
 
 #include "../../include/pychain_hip.h"
+#include "align.h"
 #include "common.h"
 #include "den_kernels.h"
 #include "device_utils.h"
@@ -943,6 +944,80 @@ extern "C" int pychain_hip_num_forward_backward(
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "num_forward_backward: %s",
                 why ? why : hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}
+
+// ---- Viterbi alignment (align.hip) ------------------------------------------------------------
+
+namespace {
+struct AlignCarve { size_t bp, sc, total; };
+AlignCarve align_carve(int B, int T, int H, int K, int D) {
+  AlignCarve c;
+  c.bp = 0;
+  if (num_needs_general(H, K, D)) {                  // int32 backpointers + the two score vectors per sequence
+    c.sc = align256(4 * (size_t)B * T * H);
+    c.total = c.sc + align256(16 * (size_t)B * H) + 256;
+  } else {                                          // uint16 backpointers, rows of H rounded up to even
+    c.sc = align256(2 * (size_t)B * T * (size_t)((H + 1) & ~1));
+    c.total = c.sc + 256;
+  }
+  return c;
+}
+bool align_half_native(int H, int K, int D) { return !num_needs_general(H, K, D) && D % 4 == 0 && D <= 4 * 8 * 512; }
+}  // namespace
+
+extern "C" size_t pychain_hip_align_workspace_bytes(int B, int T, int H, int K, int D) {
+  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
+  return align_carve(B, T, H, K, D).total;
+}
+extern "C" int pychain_hip_align_half_native(int H, int K, int D) {
+  if (H <= 0 || K <= 0 || D <= 0) return 0;
+  return align_half_native(H, K, D) ? 1 : 0;
+}
+
+extern "C" int pychain_hip_align(
+    const int32_t* ft, const int32_t* fi, const float* fp,
+    const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "align";
+  (void)ft; (void)fi; (void)fp;                      // (the recursion gathers over the arcs entering each state only)
+  if (nnet_output_dtype < PYCHAIN_HIP_F32 || nnet_output_dtype > PYCHAIN_HIP_F16)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, nnet_output_dtype);
+  if (!bt || !bi || !bp || !initial || !final_ || !nnet_output || !seq_lengths || !score_per_seq || !states || !pdfs ||
+      !bad_count || !workspace)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || K <= 0)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
+  if (graph_batch_stride != 0 && graph_batch_stride != 1)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+  if (((uintptr_t)nnet_output | (uintptr_t)bi) & 15)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output and index tensors must be 16-byte aligned", who);
+  const AlignCarve c = align_carve(B, T, H, K, D);
+  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
+  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !align_half_native(H, K, D))
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_align_half_native)", who);
+  AlignArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bwd_trans = bt; a.bwd_idx = bi; a.bwd_probs = bp; a.initial = initial; a.final_ = final_;
+  a.x = (const float*)nnet_output; a.x_half = nnet_output_dtype; a.lengths = seq_lengths;
+  a.score = score_per_seq; a.states = states; a.pdfs = pdfs; a.bad = bad_count;
+  a.graph_stride = graph_batch_stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
+  a.Hb = (H + 1) & ~1;
+  a.general = num_needs_general(H, K, D) ? 1 : 0;
+  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  if (a.general) { a.bp32 = (int32_t*)(ws + c.bp); a.gen_sc = (double*)(ws + c.sc); }
+  else { a.bp16 = (uint16_t*)(ws + c.bp); a.walk_bytes = align_walk_bytes(H, K, D); }
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(bad_count, 0, sizeof(int32_t), st) != hipSuccess)
+    return fail(PYCHAIN_HIP_ELAUNCH, "%s: hipMemsetAsync failed", who);
+  const char* why = nullptr;
+  hipError_t e = launch_align(a, st, &why);
+  if (e != hipSuccess)
+    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
 }
 

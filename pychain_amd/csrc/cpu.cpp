@@ -208,6 +208,57 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
   return ok;
 }
 
+// ---- Viterbi alignment over a numerator graph (include/pychain_hip.h: pychain_hip_cpu_align; the device's align.hip) ----------
+// fp64 adds and compares only, in the association and with the tie rules the device kernels use, so both give the same bits.
+bool align_one(const Csr& bwd, const float* init, const float* fin, const float* x, int L, int T, int D, int H, double* score,
+               int32_t* states, int64_t* pdfs) {
+  const double ninf = -std::numeric_limits<double>::infinity();
+  std::vector<double> sa((size_t)H), sb((size_t)H);
+  std::vector<int32_t> bp((size_t)L * H);           // winning arc (absolute index) of every (frame, state)
+  bool nan = false;
+  for (int h = 0; h < H; h++) sa[h] = (double)init[h];
+  for (int t = 0; t < L; t++) {
+    const float* xr = x + (size_t)t * D;
+    const double* vin = (t & 1) ? sb.data() : sa.data();
+    double* vout = (t & 1) ? sa.data() : sb.data();
+    int32_t* brow = bp.data() + (size_t)t * H;
+    for (int h = 0; h < H; h++) {
+      const int lo = bwd.idx[2 * h], hi = bwd.idx[2 * h + 1];
+      double best = ninf;
+      int bk = lo;
+      for (int k = lo; k < hi; k++) {
+        const double e = vin[bwd.trans[3 * k]] + ((double)bwd.prob[k] + (double)clamp30(xr[bwd.trans[3 * k + 2]]));
+        nan = nan || e != e;
+        if (k == lo || e > best) { best = e; bk = k; }
+      }
+      vout[h] = best;
+      brow[h] = bk;
+    }
+  }
+  const double* vL = (L & 1) ? sb.data() : sa.data();
+  double best = ninf;
+  int hstar = 0;
+  for (int h = 0; h < H; h++) {
+    const double e = vL[h] + (double)fin[h];
+    nan = nan || e != e;
+    if (e > best) { best = e; hstar = h; }
+  }
+  const bool ok = !nan && std::isfinite(best);
+  *score = nan ? std::numeric_limits<double>::quiet_NaN() : best;
+  for (int t = ok ? L : 0; t < T; t++) pdfs[t] = -1;
+  for (int t = ok ? L + 1 : 0; t <= T; t++) states[t] = -1;
+  if (!ok) return false;
+  int h = hstar;
+  states[L] = h;
+  for (int t = L - 1; t >= 0; t--) {
+    const int k = bp[(size_t)t * H + h];
+    pdfs[t] = bwd.trans[3 * k + 2];
+    h = bwd.trans[3 * k];
+    states[t] = h;
+  }
+  return true;
+}
+
 int check_common(const char* who, const void* ft, const void* fi, const void* fp, const void* bt, const void* bi, const void* bp,
                  const void* initial, const void* final_, const void* x, const int64_t* lengths, const void* objf, const void* grad,
                  const void* bad, int B, int T, int D, int H, int K) {
@@ -268,6 +319,30 @@ extern "C" int pychain_hip_cpu_num_forward_backward(
     const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
     const bool ok = num_one(fwd, bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
                             grad_mode, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D);
+    if (!ok) bad++;
+  });
+  *bad_count = bad.load();
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_align(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_align";
+  int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, score_per_seq, states, bad_count,
+                        B, T, D, H, K);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (!pdfs) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (graph_batch_stride != 0 && graph_batch_stride != 1) return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+  g_cpu_calls++;
+  std::atomic<int> bad{0};
+  for_each_sequence(B, num_threads, [&](int b) {
+    const size_t g = (size_t)b * graph_batch_stride;
+    const Csr bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
+    const bool ok = align_one(bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
+                              score_per_seq + b, states + (size_t)b * (T + 1), pdfs + (size_t)b * T);
     if (!ok) bad++;
   });
   *bad_count = bad.load();

@@ -203,6 +203,56 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
     return objf, grad, bad
 
 
+def align(gt, graph_stride, num_states, x, lengths):
+    """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
+    Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
+    _require_device(x, "nnet_output")
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    K = gt["backward_transitions"].shape[1]
+    L = _lib.lib()
+    dev = x.device
+    with torch.cuda.device(dev):
+        x, xcode = _rows_as_given(x, lambda: L.pychain_hip_align_half_native(int(num_states), K, D))
+        ld = _lengths_dev(lengths, dev)
+        score = torch.empty(B, dtype=torch.float64, device=dev)
+        states = torch.empty(B, T + 1, dtype=torch.int32, device=dev)
+        pdfs = torch.empty(B, T, dtype=torch.int64, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pychain_hip_align_workspace_bytes(B, T, int(num_states), K, D), dev, "align")
+        _lib.check(L.pychain_hip_align(
+            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
+            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
+            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
+            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
+            x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K,
+            score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
+            "pychain_hip_align")
+    return score, states, pdfs, bad
+
+
+def cpu_align(graphs, x, lengths):
+    """Viterbi alignment on CPU tensors (the host twin, pychain_hip_cpu_align): same results, bit for bit, as `align` on the
+    fp32 value of the same input.  Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32)."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_align is for CPU tensors; device tensors run on the HIP kernels")
+    xf = x.detach().to(torch.float32).contiguous()
+    B, T, D = xf.shape
+    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
+    _check_lengths(lc, B, T)
+    ts, stride = _cpu_graph(graphs, False)
+    H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
+    score = torch.empty(B, dtype=torch.float64)
+    states = torch.empty(B, T + 1, dtype=torch.int32)
+    pdfs = torch.empty(B, T, dtype=torch.int64)
+    bad = torch.zeros(1, dtype=torch.int32)
+    _lib.check(_lib.lib().pychain_hip_cpu_align(
+        *[t.data_ptr() for t in ts], stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K,
+        score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_align")
+    return score, states, pdfs, bad
+
+
 def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengths,
                                 leaky_coefficient=1e-5, grad_scale=1.0):
     """Fused ChainLoss: returns (den_objf[B], num_objf[B], grad[B,T,D] = grad_scale*(gamma_den - gamma_num),
