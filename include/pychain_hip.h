@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 18
+#define PYCHAIN_HIP_ABI_VERSION 19
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -376,6 +376,64 @@ int pychain_hip_cpu_align(
     const float* nnet_output, const int64_t* seq_lengths,
     int B, int T, int num_pdfs, int num_states, int num_transitions,
     double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Alignment time windows on numerator graphs (ABI 19): constrained ("regular") LF-MMI, the numerator restricted to the paths
+ * that stay near a given alignment.  The *_tw entry points are the entry points of the same name without the suffix, with one
+ * argument more, last:
+ *   time_windows  int32 [B][H][2] = {lo, hi} (dev; the host twin: host), H = num_states of the call.  One row per sequence,
+ *                 also where the graph is shared (graph_batch_stride 0).  NULL = no windows: exactly the call without them.
+ * State h is ADMISSIBLE at time index t in [0, L] iff lo <= t <= hi.  Any int32 values are legal: lo > hi = never,
+ * lo <= 0 and hi >= L = always.  t is the index of alpha and of pychain_hip_align's states: "the state before frame t".
+ * With adm(t,h) for admissible and x the clamped input as in pychain_hip_num_forward_backward:
+ *   alpha(0,h) = initial(h)                                           if adm(0,h)   else -inf
+ *   alpha(t,h) = LogSum_k alpha(t-1,src_k) + lp_k + x(t-1,pdf_k)      if adm(t,h)   else -inf     t = 1..L
+ *   beta(L,h)  = final(h)                                             if adm(L,h)   else -inf
+ *   beta(t,h)  = LogSum_k lp_k + beta(t+1,dst_k) + x(t,pdf_k)         if adm(t,h)   else -inf     t = L-1..0
+ *   logP       = LogSum_h alpha(L,h) + final(h)
+ * - the sum over the paths whose state lies in its window at every time.  Occupancies follow as without windows; they are
+ * zero on every arc with an inadmissible end.  The mask is a select AFTER the log-sum: a masked state's value and its arcs'
+ * log-shares are -inf whatever the sum was, so a NaN term that reaches only masked states goes no further (the host twin
+ * does the same).  Windows that admit every state at every time give the same bits as NULL (objectives, gradient,
+ * bad_count, totals).  A sequence whose windows admit no path gets logP = -inf and counts in bad_count, like a graph with no
+ * path of length L.  Option num_compat = 1 (the reference's own arithmetic) takes no windows: such a call fails
+ * (PYCHAIN_HIP_EUNSUPPORTED, pychain_hip_last_error says why).  The fused calls offset the windows with the sequences of a
+ * slice; pychain_hip_chain_loss_backward reads the stored rows and takes none.  pychain_hip_align takes none either. */
+int pychain_hip_num_forward_backward_tw(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* time_windows);
+int pychain_hip_chain_loss_forward_tw(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_num_states, float leaky_hmm_coefficient,
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride, int num_num_states, int num_num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float* den_objf_per_seq, float* num_objf_per_seq, void* grad, float grad_scale, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_workspace, size_t den_workspace_bytes, void* num_workspace, size_t num_workspace_bytes, void* stream,
+    const int32_t* time_windows);
+int pychain_hip_chain_loss_forward_backward_tw(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_num_states, float leaky_hmm_coefficient,
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride, int num_num_states, int num_num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs, float grad_scale,
+    float* den_objf_per_seq, float* num_objf_per_seq, void* grad, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_workspace, size_t den_workspace_bytes, void* num_workspace, size_t num_workspace_bytes, void* stream,
+    const int32_t* time_windows);
+int pychain_hip_cpu_num_forward_backward_tw(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

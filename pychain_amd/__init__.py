@@ -1,6 +1,6 @@
 """pychain_amd: MI355X-native LF-MMI loss behind the pychain API.
 
-    from pychain_amd import ChainGraph, ChainGraphBatch, ChainFunction, ChainLoss, viterbi_align
+    from pychain_amd import ChainGraph, ChainGraphBatch, ChainFunction, ChainLoss, viterbi_align, alignment_windows
 
 (`import pychain` resolves to the same objects through the alias package at the
 repository root, so code written against the reference imports unchanged.)
@@ -28,4 +28,4 @@ _more_hardware_queues()
 
 from .graph import ChainGraph, ChainGraphBatch  # noqa: F401
 from .loss import ChainFunction, ChainLoss, ChainLossFunction  # noqa: F401
-from .align import Alignment, viterbi_align  # noqa: F401
+from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 18
+ABI_VERSION = 19
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -56,6 +56,16 @@ _SIGNATURES = {
     "pychain_hip_chain_loss_forward": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
                                        + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
                                        + [_vp, _sz, _vp, _sz, _vp]),
+    # (ABI 19: the same four with alignment time windows, one pointer more, last - include/pychain_hip.h)
+    "pychain_hip_num_forward_backward_tw": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f,
+                                                 _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "pychain_hip_chain_loss_forward_backward_tw": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
+                                                   + [_vp, _i, _vp, _i, _i, _i, _f] + [_vp] * 4 + [_f, _vp, _vp]
+                                                   + [_vp, _sz, _vp, _sz, _vp, _vp]),
+    "pychain_hip_chain_loss_forward_tw": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
+                                          + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
+                                          + [_vp, _sz, _vp, _sz, _vp, _vp]),
+    "pychain_hip_cpu_num_forward_backward_tw": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),

@@ -12,6 +12,13 @@ inputs follow ChainFunction's contract (the network output [B,T,D] in fp32 / bf1
 in any order, on any device).  Device tensors run on the HIP kernels (csrc/align.hip), CPU tensors on the host twin
 (csrc/cpu.cpp) - never one for the other - and both give the same bits (include/pychain_hip.h: pychain_hip_align).  The
 call is not differentiable, does not synchronise the host, and runs on the current stream.
+
+alignment_windows turns an alignment into the time windows of constrained LF-MMI (ChainGraphBatch.set_time_windows): the next
+model trains on numerators restricted to the previous model's alignment plus a tolerance -
+
+    ali = viterbi_align(x_flat_start, lengths, num_graphs)
+    num_graphs.set_time_windows(alignment_windows(ali, num_graphs.num_states, tolerance=2))
+    loss = ChainLoss(den_graph)(x, lengths, num_graphs)
 """
 import collections
 
@@ -20,7 +27,7 @@ import torch
 from . import native
 from .graph import ChainGraphBatch
 
-__all__ = ["Alignment", "viterbi_align"]
+__all__ = ["Alignment", "viterbi_align", "alignment_windows"]
 
 Alignment = collections.namedtuple("Alignment", ["pdfs", "states", "score", "ok"])
 
@@ -29,6 +36,9 @@ def viterbi_align(nnet_output, input_lengths, num_graphs):
     """Best path through every sequence's log-domain numerator graph (a ChainGraphBatch, from one shared graph or a list)."""
     if not isinstance(num_graphs, ChainGraphBatch):
         raise TypeError("viterbi_align: num_graphs must be a ChainGraphBatch")
+    if getattr(num_graphs, "time_windows", None) is not None:
+        raise ValueError("viterbi_align: this batch carries time windows (set_time_windows); constrained re-alignment is not "
+                         "supported - align on a batch without them")
     if not num_graphs.log_domain:
         raise ValueError("viterbi_align: the graphs must be log-domain numerator graphs (log_domain=True); denominator graphs "
                          "(leaky-HMM, probability domain) have no best-path meaning here")
@@ -47,3 +57,43 @@ def viterbi_align(nnet_output, input_lengths, num_graphs):
             score, states, pdfs, _ = native.align(gt, gstride, num_graphs.num_states, x, input_lengths)
         ok = torch.isfinite(score)
     return Alignment(pdfs, states, score, ok)
+
+
+def alignment_windows(alignment, num_states, tolerance=0):
+    """Time windows (int32 [B, num_states, 2] on the alignment's device) around an Alignment: for a sequence with `ok`, state h
+    gets lo = max(0, first t with states[b, t] == h - left), hi = min(L_b, last such t + right), L_b = (number of
+    states[b] >= 0) - 1; a state the path never visits gets (0, -1), never admissible.  A sequence without `ok` gets (0, T)
+    for every state: it stays unconstrained.  `tolerance`: frames on both sides, or (left, right); non-negative integers.
+    The aligned path stays admissible, so the constrained log-probability is >= alignment.score.  Torch ops only: no host
+    sync.  (`num_states` must exceed every state of the alignment - the graphs' num_states.)"""
+    if isinstance(tolerance, (tuple, list)):
+        if len(tolerance) != 2:
+            raise ValueError("tolerance must be an int or a pair (left, right)")
+        left, right = tolerance
+    else:
+        left = right = tolerance
+    for v in (left, right):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError("tolerance must be non-negative integers, got %r" % (tolerance,))
+    H = int(num_states)
+    if H <= 0:
+        raise ValueError("num_states must be positive")
+    states = alignment.states
+    B, T1 = states.shape
+    dev = states.device
+    st = states.to(torch.int64)
+    valid = (st >= 0) & (st < H)                     # (anything else is no state of these graphs: never scattered)
+    idx = torch.where(valid, st, torch.zeros_like(st))
+    t = torch.arange(T1, device=dev, dtype=torch.int64).expand(B, T1)
+    first = torch.full((B, H), T1, dtype=torch.int64, device=dev)
+    first.scatter_reduce_(1, idx, torch.where(valid, t, torch.full_like(t, T1)), reduce="amin")
+    last = torch.full((B, H), -1, dtype=torch.int64, device=dev)
+    last.scatter_reduce_(1, idx, torch.where(valid, t, torch.full_like(t, -1)), reduce="amax")
+    L = ((st >= 0).sum(1) - 1).unsqueeze(1)
+    visited = last >= 0
+    lo = torch.where(visited, (first - left).clamp(min=0), torch.zeros_like(first))
+    hi = torch.where(visited, torch.minimum(last + right, L), torch.full_like(last, -1))
+    ok = alignment.ok.to(device=dev, dtype=torch.bool).unsqueeze(1)
+    lo = torch.where(ok, lo, torch.zeros_like(lo))
+    hi = torch.where(ok, hi, torch.full_like(hi, T1 - 1))
+    return torch.stack([lo, hi], dim=-1).to(torch.int32)

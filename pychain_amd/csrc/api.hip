@@ -869,7 +869,7 @@ int fill_num_args(NumArgs& a, const int32_t* ft, const int32_t* fi, const float*
                   const void* nnet_output, int x_dtype, const int64_t* seq_lengths,
                   int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
                   float* objf_per_seq, void* grad, int32_t* bad_count,
-                  void* workspace, size_t workspace_bytes, const char* who) {
+                  void* workspace, size_t workspace_bytes, const char* who, const int32_t* windows) {
   if (x_dtype < PYCHAIN_HIP_F32 || x_dtype > PYCHAIN_HIP_F16)
     return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, x_dtype);
   if (!ft || !fi || !fp || !bt || !bi || !bp || !initial || !final_ || !nnet_output || !seq_lengths ||
@@ -886,6 +886,8 @@ int fill_num_args(NumArgs& a, const int32_t* ft, const int32_t* fi, const float*
   const CallKnobs knobs = call_knobs();
   const NumCarve c = num_carve(B, T, H, K, D, knobs.num_compat != 0);
   if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
+  if (windows && knobs.num_compat)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: option num_compat (the reference's own arithmetic) takes no alignment time windows", who);
   memset(&a, 0, sizeof(a));
   a.fwd_trans = ft; a.fwd_idx = fi; a.fwd_probs = fp; a.bwd_trans = bt; a.bwd_idx = bi; a.bwd_probs = bp;
   a.initial = initial; a.final_ = final_; a.x = (const float*)nnet_output; a.x_half = x_dtype; a.lengths = seq_lengths;
@@ -904,6 +906,7 @@ int fill_num_args(NumArgs& a, const int32_t* ft, const int32_t* fi, const float*
   a.general = num_needs_general(H, K, D) ? 1 : 0;             // graphs beyond the tile kernels: num_general.hip
   a.gen_acc = ws + c.gacc;
   a.compat = knobs.num_compat; a.compat_ws = ws + c.compat; a.compat_stride = num_compat_stride(H, K);
+  a.windows = windows;                                       // (NumArgs::windows; nullptr = none)
   return PYCHAIN_HIP_OK;
 }
 }  // namespace
@@ -913,18 +916,18 @@ extern "C" size_t pychain_hip_num_workspace_bytes(int B, int T, int H, int K, in
   return num_carve(B, T, H, K, D, call_knobs().num_compat != 0).total;   // (the calling thread's options, as the call will read them)
 }
 
-extern "C" int pychain_hip_num_forward_backward(
+extern "C" int pychain_hip_num_forward_backward_tw(
     const int32_t* ft, const int32_t* fi, const float* fp,
     const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
     int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream) {
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
   NumArgs a;
   int rc = fill_num_args(a, ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
                          B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, workspace,
-                         workspace_bytes, "num_forward_backward");
+                         workspace_bytes, "num_forward_backward", time_windows);
   if (rc != PYCHAIN_HIP_OK) return rc;
   // (2-byte network outputs are READ as they are by the tile recursions; the gradient of this entry point stays fp32)
   if (a.x_half && !num_half_native(a))
@@ -945,6 +948,19 @@ extern "C" int pychain_hip_num_forward_backward(
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "num_forward_backward: %s",
                 why ? why : hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_num_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp,
+    const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  return pychain_hip_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype,
+                                             seq_lengths, B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count,
+                                             workspace, workspace_bytes, stream, nullptr);
 }
 
 // ---- Viterbi alignment (align.hip) ------------------------------------------------------------
@@ -1032,7 +1048,7 @@ int chain_loss_forward_one(
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* windows) {
   const char* who = "chain_loss_forward";
   if (!bad_count) return fail(PYCHAIN_HIP_EINVAL, "%s: null bad_count", who);
   DenArgs da;
@@ -1043,7 +1059,7 @@ int chain_loss_forward_one(
   NumArgs na;
   rc = fill_num_args(na, ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
                      B, T, D, num_H, num_K, PYCHAIN_HIP_GRAD_ACCUM, -grad_scale, num_objf,
-                     grad ? grad : num_ws, bad_count + 1, num_ws, num_ws_bytes, who);
+                     grad ? grad : num_ws, bad_count + 1, num_ws, num_ws_bytes, who, windows);
   if (rc != PYCHAIN_HIP_OK) return rc;
 
   da.fused = 1;
@@ -1179,14 +1195,14 @@ extern "C" int pychain_hip_chain_loss_slices(int64_t plan_stride_bytes, int resi
   return chain_loss_slices(B, resident_slot_rows, plan_stride_bytes, true);
 }
 
-extern "C" int pychain_hip_chain_loss_forward(
+extern "C" int pychain_hip_chain_loss_forward_tw(
     const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
   const int nsl = (B > 0 && T > 0 && D > 0 && den_ws && bad_count && den_objf && num_objf && seq_lengths && nnet_output && ft && fi && fp &&
                    bt && bi && bp && initial && final_ && den_ws_bytes > 8192)
                       ? chain_loss_slices(B, resident_slot_rows, plan_stride_bytes, grad != nullptr) : 1;
@@ -1195,7 +1211,7 @@ extern "C" int pychain_hip_chain_loss_forward(
     return chain_loss_forward_one(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
                                   graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, den_objf, num_objf,
                                   grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes,
-                                  stream);
+                                  stream, time_windows);
   // the scratch lines: the last 4 KiB of the denominator's workspace (sized by the caller for all B sequences; a slice
   // needs about 1 / nsl of it)
   const size_t ws_bytes = (den_ws_bytes - 4096) & ~(size_t)255;
@@ -1214,7 +1230,8 @@ extern "C" int pychain_hip_chain_loss_forward(
         initial + g * num_H, final_ + g * num_H, graph_batch_stride, num_H, num_K,
         (const char*)nnet_output + (size_t)b0 * T * D * esz, nnet_output_dtype, seq_lengths + b0, nb, T, D,
         den_objf + b0, num_objf + b0, (char*)grad + (size_t)b0 * T * D * esz, grad_scale, lines[c].bad,
-        loss_scale, loss_norm_dev, lines[c].totals, den_ws, ws_bytes, num_ws, num_ws_bytes, stream);
+        loss_scale, loss_norm_dev, lines[c].totals, den_ws, ws_bytes, num_ws, num_ws_bytes, stream,
+        time_windows ? time_windows + (size_t)b0 * num_H * 2 : nullptr);     // (one window row per sequence, shared graph or not)
     if (rc != PYCHAIN_HIP_OK) return rc;
   }
   hipLaunchKernelGGL(chain_slices_combine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lines, c, den_objf, num_objf, seq_lengths,
@@ -1222,6 +1239,20 @@ extern "C" int pychain_hip_chain_loss_forward(
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "chain_loss_forward: %s", hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_chain_loss_forward(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
+  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp, initial,
+                                           final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D,
+                                           den_objf, num_objf, grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws,
+                                           den_ws_bytes, num_ws, num_ws_bytes, stream, nullptr);
 }
 
 // grad *= *scale_dev unless the scalar is exactly 1 (the common `loss.backward()` case costs one
@@ -1326,7 +1357,7 @@ int chain_loss_backward_impl(
   // the occupancy launch reads only the forward transitions / indices / log-probs of the graphs
   rc = fill_num_args(na, ft, fi, fp, ft, fi, fp, fp, fp,
                      graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, num_H, num_K, PYCHAIN_HIP_GRAD_ACCUM,
-                     -grad_scale, (float*)num_ws, grad, bad_count + 1, num_ws, num_ws_bytes, who);
+                     -grad_scale, (float*)num_ws, grad, bad_count + 1, num_ws, num_ws_bytes, who, nullptr);   // (stored rows: no windows)
   if (rc != PYCHAIN_HIP_OK) return rc;
   na.grad_scale_dev = grad_scale_dev;
   hipStream_t st = (hipStream_t)stream;
@@ -1354,6 +1385,21 @@ extern "C" int pychain_hip_chain_loss_backward(
                                   bad_count, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, true);
 }
 
+extern "C" int pychain_hip_chain_loss_forward_backward_tw(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D, float grad_scale,
+    float* den_objf, float* num_objf, void* grad, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
+  if (!grad) return fail(PYCHAIN_HIP_EINVAL, "chain_loss_forward_backward: null grad");
+  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt,
+                                           bi, bp, initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
+                                           seq_lengths, B, T, D, den_objf, num_objf, grad, grad_scale, bad_count, loss_scale,
+                                           loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows);
+}
+
 extern "C" int pychain_hip_chain_loss_forward_backward(
     const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
@@ -1362,11 +1408,10 @@ extern "C" int pychain_hip_chain_loss_forward_backward(
     float* den_objf, float* num_objf, void* grad, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
-  if (!grad) return fail(PYCHAIN_HIP_EINVAL, "chain_loss_forward_backward: null grad");
-  return pychain_hip_chain_loss_forward(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt,
-                                        bi, bp, initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
-                                        seq_lengths, B, T, D, den_objf, num_objf, grad, grad_scale, bad_count, loss_scale,
-                                        loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream);
+  return pychain_hip_chain_loss_forward_backward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp,
+                                                    initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
+                                                    seq_lengths, B, T, D, grad_scale, den_objf, num_objf, grad, bad_count, loss_scale,
+                                                    loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, nullptr);
 }
 
 // ---- on-device reorder of a staged batch (include/pychain_hip.h: batch containers) ------------------------------------

@@ -143,17 +143,20 @@ struct Lse64 {
   }
   double value() const { return (m != m || m == -std::numeric_limits<double>::infinity()) ? m : m + std::log(s); }
 };
+// win: the sequence's alignment time windows, {lo, hi} per state, or nullptr (include/pychain_hip.h: pychain_hip_*_tw): a state
+// outside its window gets -inf, selected after its log-sum as on the device, and its arcs carry no occupancy
 bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin, const float* x, int L, int T, int D, int H,
-             int grad_mode_flags, float gscale, float* objf, float* grad) {
+             int grad_mode_flags, float gscale, float* objf, float* grad, const int32_t* win) {
   // (PYCHAIN_HIP_CPU_NO_CLAMP: the network output as it is - the contract of pychain_C.forward_backward_log_domain, whose C++
   // does not clamp (chain-log-domain-computation.cc:137-145); ChainFunction's clamp(-30, 30), pychain/loss.py:30, otherwise)
   const bool clamp = (grad_mode_flags & PYCHAIN_HIP_CPU_NO_CLAMP) == 0;
   const int grad_mode = grad_mode_flags & 0xff;
   auto xv = [clamp](float v) { return clamp ? clamp30(v) : v; };
   const double ninf = -std::numeric_limits<double>::infinity();
+  auto adm = [win](int h, int t) { return !win || (win[2 * h] <= t && t <= win[2 * h + 1]); };
   std::vector<double> alpha((size_t)(L + 1) * H), beta(2 * (size_t)H), occ((size_t)D);
   bool ok = true;
-  for (int h = 0; h < H; h++) alpha[h] = (double)init[h];
+  for (int h = 0; h < H; h++) alpha[h] = adm(h, 0) ? (double)init[h] : ninf;
   for (int t = 1; t <= L; t++) {
     const float* xr = x + (size_t)(t - 1) * D;
     const double* pa = alpha.data() + (size_t)(t - 1) * H;
@@ -162,7 +165,7 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
       Lse64 acc;
       for (int k = bwd.idx[2 * h]; k < bwd.idx[2 * h + 1]; k++)
         acc.push(pa[bwd.trans[3 * k]] + ((double)bwd.prob[k] + (double)xv(xr[bwd.trans[3 * k + 2]])));
-      a[h] = acc.value();
+      a[h] = adm(h, t) ? acc.value() : ninf;
     }
   }
   Lse64 tl;
@@ -173,7 +176,7 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
   const float fill = grad_mode == PYCHAIN_HIP_GRAD_LOG ? -std::numeric_limits<float>::infinity() : 0.f;
   if (grad_mode != PYCHAIN_HIP_GRAD_ACCUM) for (size_t i = 0; i < (size_t)T * D; i++) grad[i] = fill;
   double* bn = beta.data() + (size_t)(L & 1) * H;
-  for (int h = 0; h < H; h++) bn[h] = (double)fin[h];
+  for (int h = 0; h < H; h++) bn[h] = adm(h, L) ? (double)fin[h] : ninf;
   std::vector<int> touched;
   for (int t = L - 1; t >= 0; t--) {
     const float* xr = x + (size_t)t * D;
@@ -184,6 +187,7 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
     touched.clear();
     double fsum = 0.0;
     for (int h = 0; h < H; h++) {
+      if (!adm(h, t)) { b[h] = ninf; continue; }
       Lse64 acc;
       for (int k = fwd.idx[2 * h]; k < fwd.idx[2 * h + 1]; k++) {
         const int pdf = fwd.trans[3 * k + 2];
@@ -204,7 +208,6 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
       else g[pdf] += gscale * (float)o;
     }
   }
-  (void)ninf;
   return ok;
 }
 
@@ -301,11 +304,11 @@ extern "C" int pychain_hip_cpu_den_forward_backward(
   return PYCHAIN_HIP_OK;
 }
 
-extern "C" int pychain_hip_cpu_num_forward_backward(
+extern "C" int pychain_hip_cpu_num_forward_backward_tw(
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
-    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads) {
+    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows) {
   const char* who = "cpu_num_forward_backward";
   int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, objf_per_seq, grad, bad_count, B, T, D, H, K);
   if (rc != PYCHAIN_HIP_OK) return rc;
@@ -318,11 +321,21 @@ extern "C" int pychain_hip_cpu_num_forward_backward(
     const size_t g = (size_t)b * graph_batch_stride;
     const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
     const bool ok = num_one(fwd, bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
-                            grad_mode, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D);
+                            grad_mode, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D,
+                            time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
     if (!ok) bad++;
   });
   *bad_count = bad.load();
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_num_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads) {
+  return pychain_hip_cpu_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, seq_lengths,
+                                                 B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, num_threads, nullptr);
 }
 
 extern "C" int pychain_hip_cpu_align(

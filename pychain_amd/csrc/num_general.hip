@@ -68,6 +68,8 @@ __device__ __forceinline__ float block_sumf(float v, double* red, int tid) {
   return (float)s;
 }
 
+// TW: alignment time windows (NumArgs::windows), as num_kernels.hip's num_fb_kernel: -inf selected after the log-sum
+template <bool TW = false>
 __global__ __launch_bounds__(kNGT) void num_general_fb_kernel(const NumArgs a) {
   __shared__ double red[32];
   const int tid = threadIdx.x;
@@ -84,8 +86,11 @@ __global__ __launch_bounds__(kNGT) void num_general_fb_kernel(const NumArgs a) {
   const float* xseq = a.x + (size_t)b * T * D;
   double* rows = (fwd ? a.alpha_ws : a.beta_ws) + (size_t)b * (T + 1) * H;
   const int other = fwd ? 0 : 1;                       // the arc's other end: source for alpha, destination for beta
+  const int32_t* win = TW ? a.windows + (size_t)b * H * 2 : nullptr;    // {lo, hi} per state: one row per sequence
+  auto adm = [&](int h, int t) { return !TW || (win[2 * h] <= t && t <= win[2 * h + 1]); };
   // AlphaFirstFrame :84-90 / BetaLastFrame :192-202 (unnormalised: beta(L,i) = final(i); 1 / P enters the occupancy)
-  for (int h = tid; h < H; h += kNGT) rows[(size_t)(fwd ? 0 : L) * H + h] = (double)(fwd ? a.initial : a.final_)[g * H + h];
+  for (int h = tid; h < H; h += kNGT)
+    rows[(size_t)(fwd ? 0 : L) * H + h] = adm(h, fwd ? 0 : L) ? (double)(fwd ? a.initial : a.final_)[g * H + h] : -INFINITY;
   __threadfence();
   __syncthreads();
   // fwd: alpha(t,h) = LogSum_k alpha(t-1,src_k) + lp_k + x(t-1,pdf_k), t = 1..L     (:93-159, unnormalised)
@@ -101,13 +106,14 @@ __global__ __launch_bounds__(kNGT) void num_general_fb_kernel(const NumArgs a) {
       GLse acc; acc.init();
       for (int k = be.x; k < be.y; k++)
         acc.push(fresh(prev + tr[3 * k + other]) + ((double)pr[k] + (double)gclamp(xrow[tr[3 * k + 2]])));
-      const double v = acc.value();
+      const bool ok = adm(h, t_out);
+      const double v = ok ? acc.value() : -INFINITY;
       out[h] = v;
       // the backward pass also writes, per arc, its log-share of its source state's beta: r_k(t) = term_k - beta(t,h) <= 0
       // (all the occupancy pass needs from this frame's nnet-output row: num_kernels.hip)
       if (!fwd)
         for (int k = be.x; k < be.y; k++)
-          frow[k] = (float)(fresh(prev + tr[3 * k + other]) + ((double)pr[k] + (double)gclamp(xrow[tr[3 * k + 2]])) - v);
+          frow[k] = ok ? (float)(fresh(prev + tr[3 * k + other]) + ((double)pr[k] + (double)gclamp(xrow[tr[3 * k + 2]])) - v) : -INFINITY;
     }
     __threadfence();
     __syncthreads();
@@ -214,7 +220,8 @@ bool num_needs_general(int H, int K, int D) {
 size_t num_general_acc_bytes(int D) { return (size_t)kNumGeneralBlocks * (((size_t)D + 3) & ~(size_t)3) * 8; }
 
 hipError_t launch_num_general_fb(const NumArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(num_general_fb_kernel, dim3(2 * a.B), dim3(kNGT), 0, st, a);
+  auto k = a.windows ? num_general_fb_kernel<true> : num_general_fb_kernel<false>;
+  hipLaunchKernelGGL(k, dim3(2 * a.B), dim3(kNGT), 0, st, a);
   return hipGetLastError();
 }
 hipError_t launch_num_general_occ(const NumArgs& a, void* acc, hipStream_t st) {

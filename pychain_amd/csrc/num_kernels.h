@@ -53,6 +53,10 @@ struct NumArgs {
   int compat;
   char* compat_ws;
   size_t compat_stride;
+  // alignment time windows (include/pychain_hip.h: pychain_hip_num_forward_backward_tw): int32 [B][H][2] = {lo, hi}, one row per
+  // sequence; state h is admissible at time index t iff lo <= t <= hi, and alpha(t,h), beta(t,h) and the log-shares of its arcs
+  // are -inf where it is not.  nullptr = none (the recursion kernels without the window: num_fb_kernel, num_general_fb_kernel)
+  const int32_t* windows;
 };
 
 // Numerator graphs the tile kernels do not take - more than 65 535 states or pdfs, or state vectors + nnet-output rows +

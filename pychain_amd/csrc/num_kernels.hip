@@ -72,7 +72,9 @@ __device__ __forceinline__ double wave_max(double v) {
 constexpr int kFbLd = 128;
 // XH: 2-byte network output (NumArgs::x_half; float4-chunk forms only): four elements = 8 bytes per thread and chunk, converted
 // as they arrive
-template <int VEC, int XCH, int LD, bool XH = false>
+// TW: alignment time windows (NumArgs::windows): a state outside its window at time t gets -inf, selected AFTER its log-sum, and
+// so do the log-shares of its arcs.  The forms without them compile to the instructions they had before windows existed.
+template <int VEC, int XCH, int LD, bool XH = false, bool TW = false>
 __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
   static_assert(!XH || (VEC == 4 && XCH > 0), "2-byte rows: chunks of four elements through registers");
   constexpr size_t kXe = XH ? 2 : 4;
@@ -115,12 +117,15 @@ __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
   };
   double* rows = (fwd ? a.alpha_ws : a.beta_ws) + (size_t)b * (T + 1) * H;     // row t = alpha(t,.) / beta(t,.), fp64 log-prob
   const int2* idx = reinterpret_cast<const int2*>((fwd ? a.bwd_idx : a.fwd_idx) + g * H * 2);
+  const int32_t* win = TW ? a.windows + (size_t)b * H * 2 : nullptr;         // {lo, hi} per state: one row per sequence
 
   // this thread's state(s): h = tid (+ kFbNT, ... for graphs with more than 512 states)
   const int h0 = tid;
   const bool own = h0 < H && tid < kFbNT;
   int2 be = make_int2(0, 0);
   if (own) be = idx[h0];
+  int wlo = 0, whi = 0;                              // this thread's state's window, in registers
+  if constexpr (TW) if (own) { wlo = win[2 * h0]; whi = win[2 * h0 + 1]; }
   XRow<LD ? LD : kFbNT, VEC, XCH> xq;
   const int xt = LD ? tid - kFbNT : tid;            // this thread's index among the threads that stage rows
   // a row, clamped, into LDS; NaNs kept only where nobody else watches for them (NumArgs::watch_nan)
@@ -140,7 +145,8 @@ __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
     // AlphaFirstFrame :84-90 / BetaLastFrame :192-202 (unnormalised: beta(L,i) = final(i); 1/P enters the occupancy)
     if (tid < kFbNT)
       for (int h = tid; h < H; h += kFbNT) {
-        const double v = (double)(fwd ? a.initial : a.final_)[g * H + h];
+        double v = (double)(fwd ? a.initial : a.final_)[g * H + h];
+        if constexpr (TW) { const int t0 = fwd ? 0 : L; if (!(win[2 * h] <= t0 && t0 <= win[2 * h + 1])) v = -INFINITY; }
         va[h] = v; rows[(size_t)(fwd ? 0 : L) * H + h] = v;
       }
     if (!LD || tid >= kFbNT) stage(xq, xr0, xrow, xt);
@@ -184,7 +190,8 @@ __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
     const bool have_next = s < L;
     const int t_next = have_next ? (fwd ? s : L - 1 - s) : 0;
     const float* xrow_next = XH ? nullptr : xseq + (size_t)t_next * D;
-    const size_t trow = (size_t)(fwd ? s : L - s) * H;
+    const int tout = fwd ? s : L - s;                  // time index of the row this step writes
+    const size_t trow = (size_t)tout * H;
     if (!LD && have_next) {
       // buffer form: no address VGPR is written per step, so the load does not wait for this step's row stores
       if constexpr (VEC == 4 && XCH > 0) xload_row(xq, t_next, tid);
@@ -204,32 +211,35 @@ __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
         const ArcW w = arc[k];
         acc.push(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]));
       }
-      const double v = acc.value();
+      const bool adm = !TW || (wlo <= tout && tout <= whi);
+      const double v = adm ? acc.value() : -INFINITY;
       vout[h0] = v;
       rows[trow + h0] = v;
       if (!fwd) {
-        if (be.y - be.x > 0) frow[be.x] = (float)(e0 - v);
-        if (be.y - be.x > 1) frow[be.x + 1] = (float)(e1 - v);
+        if (be.y - be.x > 0) frow[be.x] = adm ? (float)(e0 - v) : -INFINITY;
+        if (be.y - be.x > 1) frow[be.x + 1] = adm ? (float)(e1 - v) : -INFINITY;
         for (int k = be.x + 2; k < be.y; k++) {
           const ArcW w = arc[k];
-          frow[k] = (float)(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]) - v);
+          frow[k] = adm ? (float)(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]) - v) : -INFINITY;
         }
       }
     }
     for (int h = h0 + kFbNT; h < H; h += kFbNT) {             // graphs with more than 512 states
       const int2 e2 = idx[h];
+      bool adm = true;
+      if constexpr (TW) adm = win[2 * h] <= tout && tout <= win[2 * h + 1];
       Lse acc; acc.init();
       for (int k = e2.x; k < e2.y; k++) {
         const ArcW w = arc[k];
         acc.push(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]));
       }
-      const double v = acc.value();
+      const double v = adm ? acc.value() : -INFINITY;
       vout[h] = v;
       rows[trow + h] = v;
       if (!fwd)
         for (int k = e2.x; k < e2.y; k++) {
           const ArcW w = arc[k];
-          frow[k] = (float)(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]) - v);
+          frow[k] = adm ? (float)(vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]) - v) : -INFINITY;
         }
     }
     if (!LD && have_next) stage(xq, xnext, xrow_next, tid);
@@ -264,6 +274,7 @@ __global__ __launch_bounds__(kFbNT + LD) void num_fb_kernel(const NumArgs a) {
     if (!(objf - objf == 0.f) || seq_len_bad(a.lengths, b, a.T)) atomicAdd(a.bad, 1);
   }
 }
+
 
 // ------------------------------------------------------------------------------------
 // the distinct pdf-ids of every sequence's numerator graph, ascending: upd[b][u], ucount[b]
@@ -589,7 +600,7 @@ __global__ __launch_bounds__(kOcNT) void num_scatter_kernel(const NumArgs a) {
 
 template <int VEC, int XCH, int LD, bool XH>
 hipError_t launch_fb_x(const NumArgs& a, size_t lds, hipStream_t st) {
-  auto k = num_fb_kernel<VEC, XCH, LD, XH>;
+  auto k = a.windows ? num_fb_kernel<VEC, XCH, LD, XH, true> : num_fb_kernel<VEC, XCH, LD, XH, false>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(2 * a.B), dim3(kFbNT + LD), lds, st, a);

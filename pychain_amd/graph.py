@@ -209,6 +209,10 @@ def _pack_record_uncached(g):
 class ChainGraphBatch(object):
     """B graphs as batched tensors (pychain/graph.py:73-194)."""
 
+    # alignment time windows of a log-domain (numerator) batch: int32 [batch_size, num_states, 2] = {lo, hi}, or None
+    # (set_time_windows; a class attribute so that batches pickled before windows existed load with none)
+    time_windows = None
+
     def __init__(self, graphs, batch_size=None, max_num_transitions=None, max_num_states=None):
         self.shared_graph = None     # set when every row is the same ChainGraph
         self._device_cache = {}
@@ -241,6 +245,7 @@ class ChainGraphBatch(object):
         d = dict(self.__dict__)
         d["_device_cache"] = {}
         d.pop("_pickle_keepalive", None)
+        d.pop("_tw_device", None)
         if self.shared_graph is None and self._packed_consistent():
             for name, _shape, _dt in _PACKED:
                 d.pop(name, None)
@@ -363,10 +368,53 @@ class ChainGraphBatch(object):
             self.final_probs[i, :h].copy_(g.final_probs)
             self.start_state[i] = g.start_state
 
+    def set_time_windows(self, windows):
+        """Restrict every sequence's numerator to the paths that stay near an alignment (constrained LF-MMI): `windows` is
+        an integer tensor [batch_size, num_states, 2] on any device, row b, state h = {lo, hi}: the state is admissible at
+        time index t (the state before frame t, t = 0..length) iff lo <= t <= hi (include/pychain_hip.h: time windows;
+        alignment_windows builds them from viterbi_align's output).  Kept as int32, contiguous; None clears them.
+        ChainFunction and ChainLoss use them on this batch from then on; reorder and shard_batch carry them."""
+        self.__dict__.pop("_tw_device", None)
+        if windows is None:
+            self.time_windows = None
+            return
+        if not self.log_domain:
+            raise ValueError("time windows restrict log-domain numerator graphs; this batch is in the probability domain")
+        if not isinstance(windows, torch.Tensor) or windows.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8,
+                                                                          torch.uint8):
+            raise ValueError("time windows must be an integer tensor, got %s" % (getattr(windows, "dtype", type(windows)),))
+        if tuple(windows.shape) != (self.batch_size, self.num_states, 2):
+            raise ValueError("time windows must have the shape [batch_size, num_states, 2] = [%d, %d, 2], got %s"
+                             % (self.batch_size, self.num_states, list(windows.shape)))
+        if windows.dtype == torch.int64:
+            windows = windows.clamp(-2 ** 31, 2 ** 31 - 1)      # (any int32 value is legal: saturate, do not wrap)
+        self.time_windows = windows.to(torch.int32).contiguous()
+
+    def device_time_windows(self, device):
+        """The time windows on `device` (None without), copied once and cached like device_tensors: keyed by the tensor's
+        data_ptr and _version, so an in-place edit or set_time_windows re-stages them."""
+        tw = self.time_windows
+        if tw is None:
+            return None
+        device = torch.device(device)
+        if tw.device == device:
+            return tw
+        key = (str(device), tw.data_ptr(), tw._version)
+        hit = self.__dict__.get("_tw_device")
+        if hit is None or hit[0] != key:
+            hit = (key, tw.to(device, non_blocking=True))
+            self._tw_device = hit
+        return hit[1]
+
     def reorder(self, new_order):
         """Permute (or select from) the batch (pychain/graph.py:177-194).  A batch built from a list is re-gathered
         natively in its one buffer, and a copy already staged on a device is re-gathered THERE by one launch instead of
-        being dropped and uploaded again."""
+        being dropped and uploaded again.  Time windows (set_time_windows) follow their sequences."""
+        tw = self.time_windows
+        if tw is not None:
+            order = torch.as_tensor(new_order).to(device=tw.device, dtype=torch.int64)
+            self.time_windows = tw.index_select(0, order).contiguous()
+            self.__dict__.pop("_tw_device", None)
         if self.shared_graph is None and self._packed_consistent():
             L = _native()
             from . import _lib

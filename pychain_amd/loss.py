@@ -48,10 +48,12 @@ class ChainFunction(torch.autograd.Function):
         `report["totals"]` - the caller attaches them to the tensor it returns - and the sum is returned in place of the
         per-sequence values (no reduction launch behind the call)."""
         D = x.size(2)
+        # alignment time windows of a numerator batch (ChainGraphBatch.set_time_windows; objects without them: None)
+        tw = getattr(graphs, "time_windows", None) if graphs.log_domain else None
         if not x.is_cuda:
             # CPU tensors: the library's host twins (pychain_amd/csrc/cpu.cpp) - what the reference does with them
             # (chain-computation.cc:40,136-175); device tensors never come here
-            return native.cpu_forward_backward(graphs, x, input_lengths, leaky_coefficient)
+            return native.cpu_forward_backward(graphs, x, input_lengths, leaky_coefficient, windows=tw)
         if not graphs.log_domain:   # usually the denominator
             if graphs.shared_graph is not None:
                 plan = _plan.graph_plan(graphs.shared_graph, D, x.device)
@@ -82,7 +84,8 @@ class ChainFunction(torch.autograd.Function):
             gt = graphs.device_tensors(x.device)
             gstride = 0 if graphs.shared_graph is not None else 1
             objf, input_grad, bad = native.num_forward_backward(
-                gt, gstride, graphs.num_states, x, input_lengths, grad_mode=_lib.GRAD_LINEAR)
+                gt, gstride, graphs.num_states, x, input_lengths, grad_mode=_lib.GRAD_LINEAR,
+                windows=None if tw is None else graphs.device_time_windows(x.device))
         return objf, input_grad, bad
 
     @staticmethod
@@ -184,6 +187,8 @@ class ChainLossFunction(torch.autograd.Function):
         plan = _plan.graph_plan(den_graph, D, x.device)
         gt = num_graphs.device_tensors(x.device)
         gstride = 0 if num_graphs.shared_graph is not None else 1
+        # (alignment time windows of the numerator, or None)
+        tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
         # avg=True divides by the frame count (loss.py:103-104): a host scalar when the lengths
         # live on the host, else a device scalar - never a sync
         ctx.host_scale, ctx.dev_norm = 1.0, None
@@ -201,7 +206,7 @@ class ChainLossFunction(torch.autograd.Function):
         den_objf, num_objf, bad, state, totals = native.chain_loss_forward(
             plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
             with_grad=ctx.speculative, grad_scale=ctx.host_scale, loss_scale=ctx.host_scale, norm_dev=ctx.dev_norm,
-            half_ok=half_ok)
+            half_ok=half_ok, windows=tw)
         # -(num - den) [/ frames], loss.py:100-104, comes with the call (the last workgroup of its last kernel adds the
         # per-sequence objectives up): no reduction / subtraction / scaling launches behind it
         objf = native.totals_scalar(totals)    # (no launch; not a view of the statistics: `loss /= n` works)
@@ -210,7 +215,7 @@ class ChainLossFunction(torch.autograd.Function):
         spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closure must not hold ctx)
         ctx.again = _recompute(x, lambda: native.chain_loss_forward(
             plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-            with_grad=spec, grad_scale=hscale, norm_dev=dnorm, half_ok=half_ok), lambda r: (r[3], r[2]))      # (state, bad)
+            with_grad=spec, grad_scale=hscale, norm_dev=dnorm, half_ok=half_ok, windows=tw), lambda r: (r[3], r[2]))   # (state, bad)
         ctx.in_dtype = input.dtype
         ctx.bad_count = bad                      # int32[2]: denominator, numerator; never synced here
         return _attach(objf, totals, bad)

@@ -43,10 +43,12 @@ def _cpu_graph(graphs, with_leaky):
     return ts, stride
 
 
-def cpu_forward_backward(graphs, x, lengths, leaky_coefficient=1e-5, input_is_exp=False, grad_mode=_lib.GRAD_LINEAR, clamp=True):
+def cpu_forward_backward(graphs, x, lengths, leaky_coefficient=1e-5, input_is_exp=False, grad_mode=_lib.GRAD_LINEAR, clamp=True,
+                         windows=None):
     """ChainFunction's computation on CPU tensors: (objf_per_seq[B], grad[B,T,D] fp32, bad_count int32[1]).  Denominator
     (probability-domain graphs) or numerator (log-domain graphs) by `graphs.log_domain`.  `clamp` False (numerator): the network
-    output as it is - what pychain_C.forward_backward_log_domain computes on (the reference clamps in Python, loss.py:30)."""
+    output as it is - what pychain_C.forward_backward_log_domain computes on (the reference clamps in Python, loss.py:30).
+    `windows` (numerator only): int [B, H, 2] alignment time windows (include/pychain_hip.h: pychain_hip_*_tw), None = none."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_forward_backward is for CPU tensors; device tensors run on the HIP kernels")
     xf = x.detach().to(torch.float32).contiguous()
@@ -65,11 +67,26 @@ def cpu_forward_backward(graphs, x, lengths, leaky_coefficient=1e-5, input_is_ex
             *ptrs, stride, xf.data_ptr(), int(bool(input_is_exp)), lc.data_ptr(), B, T, D, H, K,
             float(leaky_coefficient), 1.0, objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), int(CPU_THREADS)),
             "pychain_hip_cpu_den_forward_backward")
-    else:
+    elif windows is None:
         _lib.check(L.pychain_hip_cpu_num_forward_backward(
             *ptrs, stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K, int(grad_mode) | (0 if clamp else _lib.CPU_NO_CLAMP), 1.0,
             objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_num_forward_backward")
+    else:
+        tw = _check_windows(windows.cpu(), B, H)
+        _lib.check(L.pychain_hip_cpu_num_forward_backward_tw(
+            *ptrs, stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K, int(grad_mode) | (0 if clamp else _lib.CPU_NO_CLAMP), 1.0,
+            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), int(CPU_THREADS), tw.data_ptr()),
+            "pychain_hip_cpu_num_forward_backward_tw")
     return objf, grad, bad
+
+
+def _check_windows(windows, B, H, device=None):
+    """The int32 [B, H, 2] time windows a *_tw entry point reads (its kernels index them by sequence and state: checked here)."""
+    if windows.dtype != torch.int32 or tuple(windows.shape) != (B, H, 2):
+        raise ValueError("time windows must be int32 [%d, %d, 2], got %s %s" % (B, H, windows.dtype, tuple(windows.shape)))
+    if device is not None and windows.device != device:
+        raise ValueError("time windows live on %s, the call on %s" % (windows.device, device))
+    return windows.contiguous()
 
 
 def _workspace(nbytes, device, tag="a"):
@@ -169,9 +186,9 @@ def den_forward_backward(plan, x, lengths, leaky_coefficient=1e-5, input_is_exp=
 
 
 def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_lib.GRAD_LINEAR,
-                         grad_scale=1.0, grad_out=None):
-    """Numerator on the GPU.  `gt`: dict of device graph tensors.  Returns
-    (objf_per_seq[B], grad[B,T,D], bad_count[1])."""
+                         grad_scale=1.0, grad_out=None, windows=None):
+    """Numerator on the GPU.  `gt`: dict of device graph tensors; `windows`: int32 [B, H, 2] device time windows or None.
+    Returns (objf_per_seq[B], grad[B,T,D], bad_count[1])."""
     _require_device(x, "nnet_output")
     x = x.contiguous()
     B, T, D = x.shape
@@ -192,14 +209,17 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         nws = L.pychain_hip_num_workspace_bytes(B, T, int(num_states), K, D)
         ws = _workspace(nws, dev, "num")
-        _lib.check(L.pychain_hip_num_forward_backward(
+        fn, name, tail = L.pychain_hip_num_forward_backward, "pychain_hip_num_forward_backward", ()
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states), dev)
+            fn, name, tail = L.pychain_hip_num_forward_backward_tw, "pychain_hip_num_forward_backward_tw", (windows.data_ptr(),)
+        _lib.check(fn(
             gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
             gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
             gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
             gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(grad_mode), float(grad_scale),
-            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-            "pychain_hip_num_forward_backward")
+            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), *tail), name)
     return objf, grad, bad
 
 
@@ -254,9 +274,10 @@ def cpu_align(graphs, x, lengths):
 
 
 def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengths,
-                                leaky_coefficient=1e-5, grad_scale=1.0):
+                                leaky_coefficient=1e-5, grad_scale=1.0, windows=None):
     """Fused ChainLoss: returns (den_objf[B], num_objf[B], grad[B,T,D] = grad_scale*(gamma_den - gamma_num),
-    bad_count[2]).  The numerator recursion overlaps the denominator on a side stream."""
+    bad_count[2]).  The numerator recursion overlaps the denominator on a side stream.  `windows`: the numerator's device time
+    windows (int32 [B, H, 2]) or None."""
     _require_device(x, "nnet_output")
     x = x.contiguous()
     B, T, D = x.shape
@@ -274,7 +295,11 @@ def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengt
         bad = torch.empty(2, dtype=torch.int32, device=dev)
         dws = _workspace(L.pychain_hip_den_workspace_min_bytes(B, T, plan.num_states, D), dev, "den")   # (the fused loss never exp's rows ahead)
         nws = _workspace(L.pychain_hip_num_workspace_bytes(B, T, int(num_states_num), K, D), dev, "num")
-        _lib.check(L.pychain_hip_chain_loss_forward_backward(
+        fn, name, tail = L.pychain_hip_chain_loss_forward_backward, "pychain_hip_chain_loss_forward_backward", ()
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states_num), dev)
+            fn, name, tail = L.pychain_hip_chain_loss_forward_backward_tw, "pychain_hip_chain_loss_forward_backward_tw", (windows.data_ptr(),)
+        _lib.check(fn(
             plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient),
             gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
             gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
@@ -283,8 +308,7 @@ def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengt
             int(num_states_num), K,
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, float(grad_scale),
             den_objf.data_ptr(), num_objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), 1.0, 0, 0,
-            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev)),
-            "pychain_hip_chain_loss_forward_backward")
+            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), *tail), name)
     return den_objf, num_objf, grad, bad
 
 
@@ -296,11 +320,12 @@ class ChainLossState(object):
 
 
 def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient=1e-5,
-                       with_grad=False, grad_scale=1.0, loss_scale=1.0, norm_dev=None, half_ok=True):
+                       with_grad=False, grad_scale=1.0, loss_scale=1.0, norm_dev=None, half_ok=True, windows=None):
     """Recursions (and, `with_grad`, the occupancy passes overlapped with them: state.grad =
     grad_scale * (gamma_den - gamma_num)).  Returns (den_objf[B], num_objf[B], bad_count[2], state, totals) with
     totals = device float[4] [(sum den - sum num) * loss_scale [/ norm_dev], frames, bad count, sum den - sum num]
-    written by the call's last kernel (include/pychain_hip.h)."""
+    written by the call's last kernel (include/pychain_hip.h).  `windows`: the numerator's device time windows (int32
+    [B, H, 2]) or None; chain_loss_backward reads the rows they shaped and needs them no more."""
     _require_device(x, "nnet_output")
     x = x.contiguous()
     B, T, D = x.shape
@@ -325,7 +350,11 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
         nws = torch.empty(L.pychain_hip_num_workspace_bytes(B, T, int(num_states_num), K, D), dtype=torch.uint8,
                           device=dev)
         grad = torch.empty_like(x) if with_grad else None
-        _lib.check(L.pychain_hip_chain_loss_forward(
+        fn, name, tail = L.pychain_hip_chain_loss_forward, "pychain_hip_chain_loss_forward", ()
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states_num), dev)
+            fn, name, tail = L.pychain_hip_chain_loss_forward_tw, "pychain_hip_chain_loss_forward_tw", (windows.data_ptr(),)
+        _lib.check(fn(
             plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient),
             gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
             gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
@@ -334,8 +363,7 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
             int(num_states_num), K, x.data_ptr(), xcode, ld.data_ptr(), B, T, D,
             den_objf.data_ptr(), num_objf.data_ptr(), grad.data_ptr() if with_grad else 0, float(grad_scale),
             bad.data_ptr(), float(loss_scale), 0 if norm_dev is None else norm_dev.data_ptr(), totals.data_ptr(),
-            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev)),
-            "pychain_hip_chain_loss_forward")
+            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), *tail), name)
     st.grad = grad
     # (which numerator wrote the stored rows: backward runs on autograd's thread, where the caller's thread options do not reach)
     st.num_compat = _lib.get_option("num_compat") or "0"
