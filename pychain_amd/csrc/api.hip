@@ -14,6 +14,7 @@
 #include "align.h"
 #include "common.h"
 #include "den_kernels.h"
+#include "den_policy.h"
 #include "device_utils.h"
 #include "num_kernels.h"
 #include "plan_format.h"
@@ -29,13 +30,17 @@ std::mutex g_option_lock;
 typedef std::map<std::string, std::string> OptionTable;
 OptionTable& process_options() { static OptionTable t; return t; }
 OptionTable& thread_options() { static thread_local OptionTable t; return t; }     // "" = unset for this thread
-const char* const kKnownOptions[] = {"verbose", "den_phase_mask", "den_lazy", "den_dma", "den_segments", "den_pair", "gamma16",
-                                     "debug_corrupt_row", "num_compat", "den_tseg", "den_tburn", "plan_split", "chain_slices", "den_sg", "den_cross", "den_q"};
-bool known_option(const char* name) {
-  if (!name) return false;
-  for (const char* k : kKnownOptions) if (strcmp(k, name) == 0) return true;
-  return false;
+// every option of the library and what call_knobs() takes where it is unset ("debug_corrupt_row": parsed there; "gamma16": set = on)
+struct OptionSpec { const char* name; int dflt; };
+const OptionSpec kOptions[] = {{"verbose", 0}, {"den_phase_mask", 3}, {"den_lazy", 1}, {"den_dma", -1}, {"den_segments", 0}, {"den_pair", -1},
+                               {"gamma16", 0}, {"debug_corrupt_row", 0}, {"num_compat", 0}, {"den_tseg", -1}, {"den_tburn", 192},
+                               {"plan_split", -1}, {"chain_slices", -1}, {"den_sg", 1}, {"den_cross", 0}, {"den_q", 0}};
+const OptionSpec* find_option(const char* name) {
+  if (!name) return nullptr;
+  for (const OptionSpec& o : kOptions) if (strcmp(o.name, name) == 0) return &o;
+  return nullptr;
 }
+bool known_option(const char* name) { return find_option(name) != nullptr; }
 // effective value of one option as a COPY (the tables may change under another thread's set_option)
 bool option_value(const char* name, std::string* out) {
   const OptionTable& th = thread_options();
@@ -48,33 +53,32 @@ bool option_value(const char* name, std::string* out) {
   *out = ip->second;
   return true;
 }
-int option_int(const char* name, int dflt) {
+int option_int(const char* name) {            // (a name of kOptions)
   std::string v;
-  return option_value(name, &v) ? atoi(v.c_str()) : dflt;
+  return option_value(name, &v) ? atoi(v.c_str()) : find_option(name)->dflt;
 }
 bool option_set(const char* name) { std::string v; return option_value(name, &v); }
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-int roundup64(int x) { return (x + 63) / 64 * 64; }
 }  // namespace
 
 CallKnobs call_knobs() {
   CallKnobs k;
   memset(&k, 0, sizeof(k));
-  k.verbose = option_int("verbose", 0);
-  k.den_phase_mask = option_int("den_phase_mask", 3) & 3;
-  k.den_lazy = option_int("den_lazy", 1) ? 1 : 0;
-  k.den_segments = option_int("den_segments", 0);
+  k.verbose = option_int("verbose");
+  k.den_phase_mask = option_int("den_phase_mask") & 3;
+  k.den_lazy = option_int("den_lazy") ? 1 : 0;
+  k.den_segments = option_int("den_segments");
   k.gamma16 = option_set("gamma16");
-  k.den_pair = option_int("den_pair", -1);
-  k.den_dma = option_int("den_dma", -1);
-  k.num_compat = option_int("num_compat", 0) ? 1 : 0;
-  k.den_tseg = option_int("den_tseg", -1);
-  k.den_tburn = option_int("den_tburn", 192);
-  k.plan_split = option_int("plan_split", -1);
-  k.chain_slices = option_int("chain_slices", -1);
-  k.den_sg = option_int("den_sg", 1) ? 1 : 0;
-  k.den_q = option_int("den_q", 0) ? 1 : 0;          // (off by default: the frame is bound by VALU issue, not by the LDS time it saves - DESIGN.md 3.16)
-  k.den_cross = option_int("den_cross", 0) ? 1 : 0;   // (off by default: measured slower than the streamed occupancy launch - DESIGN.md 3.15)
+  k.den_pair = option_int("den_pair");
+  k.den_dma = option_int("den_dma");
+  k.num_compat = option_int("num_compat") ? 1 : 0;
+  k.den_tseg = option_int("den_tseg");
+  k.den_tburn = option_int("den_tburn");
+  k.plan_split = option_int("plan_split");
+  k.chain_slices = option_int("chain_slices");
+  k.den_sg = option_int("den_sg") ? 1 : 0;
+  k.den_q = option_int("den_q") ? 1 : 0;          // (off by default: the frame is bound by VALU issue, not by the LDS time it saves - DESIGN.md 3.16)
+  k.den_cross = option_int("den_cross") ? 1 : 0;   // (off by default: measured slower than the streamed occupancy launch - DESIGN.md 3.15)
   std::string v;
   if (option_value("debug_corrupt_row", &v)) {   // "den,b,t,scale" / "num,b,t,scale"
     char what[8] = ""; int b = 0, t = 0; float sc = 1.f;
@@ -119,35 +123,19 @@ extern "C" int pychain_hip_get_verbose_level(void) { return call_knobs().verbose
 extern "C" void pychain_hip_set_den_phase_mask(int mask) { set_process_int("den_phase_mask", mask & 3); }
 extern "C" void pychain_hip_set_den_lazy(int on) { set_process_int("den_lazy", on ? 1 : 0); }
 
-namespace {
-bool den_call_is_pair(const DenArgs& a, int resident_slot_rows);
-bool den_call_is_lazy(const DenArgs& a, int resident_slot_rows);
-int den_call_shape(const DenArgs& a, int resident_slot_rows);
-int device_cu_count();
-}  // namespace
-extern "C" int pychain_hip_den_kernel_names(int resident_slot_rows, int H, int D, int B, int plans_shared,
+extern "C" int pychain_hip_den_kernel_names(int hint, int H, int D, int B, int plans_shared,
                                             char* buf, size_t buf_bytes) {
   if (!buf || buf_bytes == 0 || H <= 0 || D <= 0 || B <= 0) return fail(PYCHAIN_HIP_EINVAL, "den_kernel_names: bad arguments");
-  DenArgs a;
-  memset(&a, 0, sizeof(a));
-  a.knobs = call_knobs();
-  a.H = H; a.Hp = roundup64(H); a.D = D; a.B = B; a.frames_per_block = 32;
-  a.plan_stride = (plans_shared & 1) ? 0 : 256;
-  a.fused = (plans_shared & 2) ? 1 : 0;                  // (bit 1: the call is a fused loss)
-  a.coef = 1e-5f;                                        // (the usual leaky-HMM coefficient: option den_q asks for one in [1e-8, 1])
-  if (resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL) {
+  if (hint == PYCHAIN_HIP_HINT_GENERAL) {
     snprintf(buf, buf_bytes, "den_general_recursion_kernel,den_general_gamma_kernel");
     return PYCHAIN_HIP_OK;
   }
-  a.pair = den_call_is_pair(a, resident_slot_rows) ? 1 : 0;
-  a.lazy = den_call_is_lazy(a, resident_slot_rows) ? 1 : 0;
-  a.shape = a.lazy ? den_call_shape(a, resident_slot_rows) : 0;
-  a.sg = (a.lazy && a.shape == kShapeDma && den_sg_eligible(a, resident_slot_rows)) ? 1 : 0;
-  // (the names of a call of the denominator alone that evaluates both launches: the crossing where option den_cross asks for it)
-  { DenArgs long_call = a; long_call.T = 1 << 14;        // (of sequences long enough to have two halves)
-    a.xf = (a.sg && !a.fused && 2 * a.B <= device_cu_count() && den_xf_eligible(long_call, resident_slot_rows)) ? den_xf_band() : 0; }
-  snprintf(buf, buf_bytes, "%s,%s", den_recursion_kernel_name(a, resident_slot_rows),
-           den_occupancy_kernel_name(a, (D + 63) / 64, resident_slot_rows));
+  // (the names of a call of the denominator alone that evaluates both launches, of sequences long enough to have two halves: the
+  // crossing where option den_cross asks for it; plans_shared bit 1: the call is a fused loss)
+  DenArgs a = den_query_args((plans_shared & 1) ? 0 : 256, hint, H, D, B, 1 << 14, (plans_shared & 2) != 0);
+  a.xf = (a.sg && !a.fused && 2 * a.B <= device_cu_count() && den_xf_eligible(a, hint)) ? den_xf_band() : 0;
+  snprintf(buf, buf_bytes, "%s,%s", den_recursion_kernel_name(a, hint),
+           den_occupancy_kernel_name(a, (D + 63) / 64, hint));
   return PYCHAIN_HIP_OK;
 }
 
@@ -191,53 +179,65 @@ extern "C" int pychain_hip_den_plan_info(const void* host_blob, size_t blob_byte
     return fail(PYCHAIN_HIP_EINVAL, "den_plan_info: a table of the plan lies outside the blob");
   memset(info, 0, 8 * sizeof(int32_t));
   info[0] = hd->H; info[1] = hd->K; info[2] = hd->D; info[3] = hd->total_bytes;
-  int m = hd->alpha.max_wave_slot_rows;
-  if (hd->beta.max_wave_slot_rows > m) m = hd->beta.max_wave_slot_rows;
-  int gmm = hd->gamma.max_wave_slot_rows, gm2 = hd->gamma2.max_wave_slot_rows;
-  if (m > 1023) m = 1023;
-  if (gmm > 511) gmm = 511;                        // (9 bits since ABI 17: anything beyond the resident row counts means "stream the tail")
-  if (gm2 > 1023) gm2 = 1023;
-  // launch hint: recursion rows (10 bits) | occupancy rows, 16 waves (9 bits) << 10 | occupancy rows, 8 waves (7 bits) << 20
-  if (gm2 > 127) gm2 = 127;                        // (7 bits since plan format 14; the two-frame kernel keeps at most 64 rows per wave)
-  // bit 29: the plan holds the recursion tiles dealt to FOUR waves (small graphs: den_recursion_lazy_kernel<small>); the
+  // the launch hint (plan_format.h: LaunchHint; encode_hint saturates the row counts at their widths)
+  LaunchHint lh;
+  lh.rows = std::max(hd->alpha.max_wave_slot_rows, hd->beta.max_wave_slot_rows);
+  lh.occ_rows = hd->gamma.max_wave_slot_rows;
+  lh.occ2_rows = hd->gamma2.max_wave_slot_rows;
+  // the plan holds the recursion tiles dealt to FOUR waves (small graphs: den_recursion_lazy_kernel<small>); the
   // recursion field is then the row count of THAT dealing (>= the 16-wave one: a kernel sized by it fits either)
-  const bool small = hd->alpha4.nwaves == PLAN_REC4_WAVES && hd->beta4.nwaves == PLAN_REC4_WAVES &&
-                     hd->rec4_max_wave_groups >= 1 && hd->rec4_max_wave_groups <= 4;
-  if (small) m = std::max(m, std::max(hd->alpha4.max_wave_slot_rows, hd->beta4.max_wave_slot_rows));
-  info[4] = m | (gmm << 10) | (gm2 << 20);
-  if (small) info[4] |= 1 << 29;
-  // bit 30: every recursion wave owns at most 4 groups (what den_recursion_lazy_kernel keeps in registers)
-  if (hd->rec_max_wave_groups >= 1 && hd->rec_max_wave_groups <= 4) info[4] |= 1 << 30;
-  // bit 28: a state sits on several positions of the beta numbering (plan.cpp, "states on several lanes"): not for
+  lh.four_waves = hd->alpha4.nwaves == PLAN_REC4_WAVES && hd->beta4.nwaves == PLAN_REC4_WAVES &&
+                  hd->rec4_max_wave_groups >= 1 && hd->rec4_max_wave_groups <= 4;
+  if (lh.four_waves) lh.rows = std::max(lh.rows, std::max(hd->alpha4.max_wave_slot_rows, hd->beta4.max_wave_slot_rows));
+  // every recursion wave owns at most 4 groups (what den_recursion_lazy_kernel keeps in registers)
+  lh.four_groups = hd->rec_max_wave_groups >= 1 && hd->rec_max_wave_groups <= 4;
+  // a state sits on several positions of the beta numbering (plan.cpp, "states on several lanes"): not for
   // den_recursion_pair_kernel, whose normalise pass gives every position the constant c(t)
-  if (hd->n_no_const > 0) info[4] |= 1 << 28;
-  // bit 19: every state sits on ONE position of either numbering and every leaky probability is positive (>= 1e-12): the lazy
+  lh.no_const = hd->n_no_const > 0;
+  // every state sits on ONE position of either numbering and every leaky probability is positive (>= 1e-12): the lazy
   // recursions' one-word state vectors (den_lazy.inc.h: MAP::kQ - alpha gathers a / cl, which needs cl > 0 everywhere)
-  if (hd->n_no_const == 0 && hd->H == hd->graph_states) {
+  lh.one_word = hd->n_no_const == 0 && hd->H == hd->graph_states;
+  if (lh.one_word) {
     const float* lk = (const float*)((const char*)host_blob + hd->off_leaky_a);
-    bool pos = true;
-    for (int i = 0; i < hd->H; i++) pos = pos && lk[i] >= 1e-12f && lk[i] <= 1e12f;
-    if (pos) info[4] |= 1 << 19;
+    for (int i = 0; i < hd->H; i++) lh.one_word = lh.one_word && lk[i] >= 1e-12f && lk[i] <= 1e12f;
   }
-  // bit 27: "pdf by state" - every arc entering a state carries one pdf: the lazy recursions' one-gather form (den_lazy.inc.h: SG)
-  if (hd->flags & PLAN_FLAG_PDF_BY_STATE) info[4] |= 1 << 27;
+  // "pdf by state" - every arc entering a state carries one pdf: the lazy recursions' one-gather form (den_lazy.inc.h: SG)
+  lh.pdf_by_state = (hd->flags & PLAN_FLAG_PDF_BY_STATE) != 0;
+  info[4] = encode_hint(lh);
   info[6] = hd->graph_states;                     // the graph's states (info[0]: positions of the longer side = what calls pass as num_states)
   info[7] = hd->H - hd->graph_states;            // positions added by states on several lanes (the longer side)
   return PYCHAIN_HIP_OK;
 }
 
+namespace {
+// The denominator workspace: byte offsets of its regions from the 256-aligned base - the size queries and fill_den_args read this.
+struct DenCarve { size_t alpha, beta, seq_progress, progress, xprog, tot_a, tot_b, gtot, fin_dot, splice, ex, min_total, total; };
+// words of the counter block `progress` (256 bytes; the first kMaxSegments: the gates' counters, DenArgs::progress)
+enum { kCtrOccDone = 24 /* a cache line of its own: polled while the queue head is drawn from */, kCtrStreamNext = 32, kCtrFinishCount = 40,
+       kCtrRedo = 48, kCtrInvNorm = 56 /* the reciprocal normaliser of the fused loss (chain_loss_forward_one) */ };
+DenCarve den_carve(int B, int T, int H, int D) {
+  const size_t b = B, Hp = roundup64(H);
+  DenCarve c;
+  c.alpha = 0;                                                   // [B,T,Hp]
+  c.beta = c.alpha + align256(4 * b * T * Hp);                   // [B,T+1,Hp]
+  c.seq_progress = c.beta + align256(4 * b * (T + 1) * Hp);      // [2][B]; from here to tot_a: the counters every call zeroes
+  c.progress = c.seq_progress + align256(8 * b);
+  c.xprog = c.progress + 256;                                    // [2][B][kExMaxQ], then xnan [B]
+  c.tot_a = c.xprog + align256(4 * (2 * kExMaxQ + 1) * b);       // per-frame totals of the two recursions, [B,T+2] each
+  c.tot_b = c.tot_a + align256(4 * b * (T + 2));
+  c.gtot = c.tot_b + align256(4 * b * (T + 2));                  // frame totals to check
+  c.fin_dot = c.gtot + align256(4 * b * T);                      // final dot products; den_finish_kernel's per-sequence side of the check
+  c.splice = c.fin_dot + align256(8 * b) + 256;                  // time segments: the speculated rows next to the segments (DenArgs::splice)
+  c.ex = c.min_total = c.splice + align256(4 * b * 2 * kMaxTimeSegs * 2 * Hp);
+  c.total = c.ex + align256(4 * b * T * D);                      // rows exp'd ahead of the recursions (DenArgs::ex): optional
+  return c;
+}
+}  // namespace
 extern "C" size_t pychain_hip_den_workspace_min_bytes(int B, int T, int H, int D) {
-  if (B <= 0 || T <= 0 || H <= 0 || D <= 0) return 0;
-  const size_t Hp = roundup64(H);
-  return align256(4 * (size_t)B * T * Hp) + align256(4 * (size_t)B * (T + 1) * Hp) +
-         align256(8 * (size_t)B) + 256 + align256(36 * (size_t)B) /* progress counters (zeroed by every call) */ +
-         2 * align256(4 * (size_t)B * (T + 2)) /* per-frame totals of the two recursions */ +
-         align256(4 * (size_t)B * T) /* frame totals to check */ + align256(8 * (size_t)B) /* final dot products; den_finish_kernel's per-sequence side of the check */ + 256 +
-         align256(4 * (size_t)B * 2 * kMaxTimeSegs * 2 * Hp) /* time segments: the speculated rows next to the segments (DenArgs::splice) */;
+  return (B <= 0 || T <= 0 || H <= 0 || D <= 0) ? 0 : den_carve(B, T, H, D).min_total;
 }
 extern "C" size_t pychain_hip_den_workspace_bytes(int B, int T, int H, int D) {
-  const size_t base = pychain_hip_den_workspace_min_bytes(B, T, H, D);
-  return base ? base + align256(4 * (size_t)B * T * D) /* rows exp'd ahead of the recursions (DenArgs::ex) */ : 0;
+  return (B <= 0 || T <= 0 || H <= 0 || D <= 0) ? 0 : den_carve(B, T, H, D).total;
 }
 
 namespace {
@@ -264,235 +264,38 @@ int fill_den_args(DenArgs& a, const void* plans_dev, int64_t plan_stride_bytes, 
     return fail(PYCHAIN_HIP_EINVAL, "%s: plan stride must be a non-negative multiple of 16", who);
   if (((uintptr_t)plans_dev | (uintptr_t)nnet_output | (uintptr_t)grad | (uintptr_t)workspace) & 15)
     return fail(PYCHAIN_HIP_EINVAL, "%s: plan, nnet_output, grad and workspace must be 16-byte aligned", who);
-  if (workspace_bytes < pychain_hip_den_workspace_min_bytes(B, T, H, D))
-    return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes,
-                pychain_hip_den_workspace_min_bytes(B, T, H, D));
-  memset(&a, 0, sizeof(a));
-  a.plans = (const char*)plans_dev; a.plan_stride = plan_stride_bytes;
+  const DenCarve c = den_carve(B, T, H, D);
+  if (workspace_bytes < c.min_total)
+    return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, c.min_total);
+  den_shape_args(a, plan_stride_bytes, H, D, B, T);      // (zeroes `a`: what is not set below is 0 / null)
+  a.plans = (const char*)plans_dev;
   a.x = (const float*)nnet_output; a.x_half = x_dtype; a.lengths = seq_lengths; a.objf = objf_per_seq; a.grad = (float*)grad; a.bad = bad_count;
-  a.B = B; a.T = T; a.D = D; a.H = H; a.Hp = roundup64(H);
   a.input_is_exp = input_is_exp ? 1 : 0;
-  a.frames_per_block = 32;      // measured at C3: 16 and 64 are both 1-3 % slower
-  a.knobs = call_knobs();
   a.phase_mask = a.knobs.den_phase_mask;
   a.coef = leaky_hmm_coefficient; a.grad_scale = grad_scale;
+  a.loss_scale = 1.f; a.bad_words = 1;
   char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  a.alpha_store = (float*)ws;
-  a.beta_store = (float*)(ws + align256(4 * (size_t)B * T * a.Hp));
-  a.seq_progress = (int32_t*)(ws + align256(4 * (size_t)B * T * a.Hp) + align256(4 * (size_t)B * (T + 1) * a.Hp));   // [2][B]
-  a.progress = (int32_t*)((char*)a.seq_progress + align256(8 * (size_t)B));
-  a.stream_next = a.progress + 32;
-  a.finish_count = a.progress + 40;
-  a.occ_done = a.progress + 24; a.occ_done_target = 0;     // (a cache line of its own: polled while the queue head is drawn from)
-  a.loss_out = nullptr; a.loss_num_objf = nullptr; a.loss_scale = 1.f; a.loss_norm_dev = nullptr; a.bad_words = 1;
-  a.stream = 0;
-  a.xprog = (int32_t*)((char*)a.progress + 256);           // [2][B][kExMaxQ], then xnan [B]
-  a.xnan = a.xprog + 2 * (size_t)B * kExMaxQ;
-  a.ex_nr = 0; a.ex_q = 0;
-  a.use_ex = 0;
-  a.tot_a = (float*)((char*)a.xprog + align256(36 * (size_t)B));
-  a.tot_b = (float*)((char*)a.tot_a + align256(4 * (size_t)B * (T + 2)));
-  a.gtot = (float*)((char*)a.tot_b + align256(4 * (size_t)B * (T + 2)));
-  a.fin_dot = (float*)((char*)a.gtot + align256(4 * (size_t)B * T));
+  a.alpha_store = (float*)(ws + c.alpha); a.beta_store = (float*)(ws + c.beta);
+  a.seq_progress = (int32_t*)(ws + c.seq_progress);
+  a.progress = (int32_t*)(ws + c.progress);
+  a.occ_done = a.progress + kCtrOccDone; a.stream_next = a.progress + kCtrStreamNext;
+  a.finish_count = a.progress + kCtrFinishCount; a.redo = a.progress + kCtrRedo;
+  a.xprog = (int32_t*)(ws + c.xprog); a.xnan = a.xprog + 2 * (size_t)B * kExMaxQ;
+  a.tot_a = (float*)(ws + c.tot_a); a.tot_b = (float*)(ws + c.tot_b); a.gtot = (float*)(ws + c.gtot); a.fin_dot = (float*)(ws + c.fin_dot);
+  a.splice = (float*)(ws + c.splice);
   // (behind everything else, and only in a workspace of the full size: DenArgs::ex)
-  a.splice = (float*)((char*)a.fin_dot + align256(8 * (size_t)B) + 256);
-  a.redo = a.progress + 48; a.redo_if = 0; a.tseg = 0; a.tburn = 0;
+  a.ex = workspace_bytes >= c.total ? (float*)(ws + c.ex) : nullptr;
   // (the plan's burn-in controller, unless the caller pins the cut or the burn-in with an option of its own)
   a.tstate = (option_set("den_tseg") || option_set("den_tburn")) ? nullptr : tstate_of(plans_dev);
-  a.ex = workspace_bytes >= pychain_hip_den_workspace_bytes(B, T, H, D) ? (float*)((char*)a.splice + align256(4 * (size_t)B * 2 * kMaxTimeSegs * 2 * a.Hp)) : nullptr;
-  a.lazy = 0;
-  a.check = 0; a.check_all = a.knobs.verbose >= 1 ? 1 : 0;
-  a.sig_n = 0;
-  a.gam_seg = 0; a.gam_nseg = 0;
   return PYCHAIN_HIP_OK;
 }
 }  // namespace
 
-// ---- library-owned side streams (the only hidden state besides the option table): one for the numerator
-// recursion, one for the occupancy launches that overlap the denominator recursion ------------------
 namespace {
-constexpr int kMaxSegments = 16;
-struct SideStream {
-  hipStream_t stream = nullptr, stream2 = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr, seg[kMaxSegments] = {}, join2 = nullptr;
-  bool ready = false;       // every stream and event below was created
-};
-// One set per (device, caller's stream): two calls in flight on two streams of one device must not share
-// the side streams' events (a second hipEventRecord would move the event the first call still waits for),
-// and calls on ONE stream are ordered, so they may.  Entries live for the life of the process.
-SideStream* side_streams_for(hipStream_t caller) {
-  static std::map<std::pair<int, hipStream_t>, SideStream> table;
-  static std::mutex create_lock;              // first use may come from several host threads
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> guard(create_lock);
-  SideStream& s = table[std::make_pair(dev, caller)];
-  if (!s.ready) {
-    if (hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) != hipSuccess) return nullptr;
-    // stream2: den_exp_rows_kernel, whose rows the recursions wait for (dispatched first: highest priority), then the gate(s)
-    // and the occupancy launches that overlap the recursions
-    int least = 0, greatest = 0;
-    if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) greatest = 0;
-    if (hipStreamCreateWithPriority(&s.stream2, hipStreamNonBlocking, greatest) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&s.fork, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&s.join, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
-    if (hipEventCreateWithFlags(&s.join2, hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
-    for (int i = 0; i < kMaxSegments; i++)
-      if (hipEventCreateWithFlags(&s.seg[i], hipEventDisableTiming | hipEventReleaseToDevice) != hipSuccess) return nullptr;
-    s.ready = true;
-  }
-  return &s;
-}
-
-// Number of time segments the denominator is cut into so that the occupancy pass of the frames
-// whose alpha'/beta rows already exist runs on idle CUs WHILE the recursions continue
-// (2B persistent workgroups leave the other CUs free).  1 = no overlap.
-int den_segments(const DenArgs& a) {
-  const int T = a.T;
-  if (a.knobs.den_segments >= 1 && a.knobs.den_segments <= kMaxSegments) return a.knobs.den_segments;
-  // What limits the overlap is CU time: after T/2 the occupancy pass has the ~128 idle CUs only (less the
-  // numerator's), on which its ~1 ms of whole-chip work takes longer than the rest of the recursion, so
-  // the last launch (the frames that only become computable at the very end) is exposed.  Each further
-  // segment halves that launch but costs a launch (gate + kernel, ~0.05 ms of side-stream time).
-  // Measured at C3 (T=1500), whole step, gated schedule with compact grids:
-  //   3 -> 3.85 ms, 4 -> 3.74, 5 -> 3.81, 6 -> 3.90   (C4, T=2000: 3 -> 6.86, 4 -> 6.84, 5 -> 7.03)
-  // (history: with one recursion launch per segment and full occupancy grids it was 3 -> 4.43, 4 -> 4.52)
-  // shorter batches (B=64, same graph; ms per step for 1 / 2 / 3 / 4 segments): T=896: 2.79 / 2.71 / 2.42 / 2.37,
-  // T=640: 2.01 / 1.93 / 1.72 / 1.72, T=384: 1.21 / 1.22 / 1.07 / 1.11
-  if (T >= 768) return 4;
-  if (T >= 256) return 3;
-  // small graphs in four-wave workgroups leave most of the chip idle and their frames are short: the occupancy pass
-  // overlaps from 64 frames on (C2, T = 150)
-  if (a.lazy && a.shape == kShapeSmall && T >= 64) return 2;
-  return 1;
-}
-
-// Which form the stored rows of this call have (decided from the same inputs by the forward call and by a
-// later chain_loss_backward on its workspace).
-// Two sequences per recursion workgroup (den_pair.inc.h) pay once the 2B one-sequence workgroups would fill the
-// chip: the recursions then run on half of it and the occupancy launches and the numerator on the other half.
-// Option den_pair: "1" wherever the shape allows (the tests), "0" never.
-int device_cu_count() {
-  static std::mutex lock;
-  static std::map<int, int> cus;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return 256;
-  std::lock_guard<std::mutex> guard(lock);
-  auto it = cus.find(dev);
-  if (it != cus.end()) return it->second;
-  int n = 0;
-  if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-  return cus[dev] = n;
-}
-bool den_call_is_small(const DenArgs& a, int resident_slot_rows) {
-  return a.knobs.den_dma != 0 && den_small_eligible(a, resident_slot_rows);
-}
-bool den_call_is_pair(const DenArgs& a, int resident_slot_rows) {
-  if (!den_pair_eligible(a, resident_slot_rows)) return false;
-  if (a.knobs.den_pair >= 0) return a.knobs.den_pair != 0;
-  // small graphs run in four-wave workgroups, several to a CU: nothing to gain from pairing sequences
-  if (a.knobs.den_lazy && den_call_is_small(a, resident_slot_rows)) return false;
-  // measured on the C3 graph (round 5, 256 CUs).  Fused step: B = 96 one-sequence workgroups 4.40 ms, pairs 4.58; B = 104:
-  // 5.36 / 4.58; B = 128: 6.60 / 5.24 - below about 100 sequences the one-sequence workgroups leave enough of the chip to the
-  // occupancy launches and the numerator, and their chain is shorter.  The denominator ALONE has the chip to itself: one-
-  // sequence workgroups while they all fit (B = 104: 3.77 against 4.63 with pairs, 112: 3.95 / 4.62, 128: 4.36 / 4.80)
-  if (a.fused) return 64 * a.B >= 25 * device_cu_count();
-  return 2 * a.B > device_cu_count();
-}
-// the nnet-output rows of the lazy recursions come in by LDS-direct loads (default wherever a lazy shape fits: on the
-// 16-wave map of C3 it is 2 % faster than rows through registers and bit-identical, and it is what makes rows of
-// 4096 < D <= 9216 pdfs - C4 - fit a 128-VGPR wave at all); option den_dma = "0": rows through registers, i.e. the
-// 16-wave map for D <= 4096 and den_recursion_kernel beyond
-bool den_call_is_dma(const DenArgs& a, int resident_slot_rows) {
-  return a.knobs.den_dma != 0 && den_dma_eligible(a, resident_slot_rows);
-}
-int den_call_shape(const DenArgs& a, int resident_slot_rows) {     // DenArgs::shape
-  if (den_call_is_small(a, resident_slot_rows)) return kShapeSmall;
-  return den_call_is_dma(a, resident_slot_rows) ? kShapeDma : kShapeRegs;
-}
-bool den_call_is_lazy(const DenArgs& a, int resident_slot_rows) {
-  return a.knobs.den_lazy && !den_call_is_pair(a, resident_slot_rows) &&
-         (den_lazy_eligible(a, resident_slot_rows) || den_call_is_small(a, resident_slot_rows) || den_call_is_dma(a, resident_slot_rows));
-}
-
-// Time segments (DenArgs::tseg): how many a call's (sequence, direction) recursions are cut into.  With few
-// sequences the chain of T dependent frames IS the step and most CUs idle; S segments started `burn` frames outside
-// themselves run T / S + burn frames each on 2 B S workgroups.  The price: the burn-in frames (CU-time) and the occupancy launch no
-// longer overlapping the recursions (a frame's rows come from four workgroups, not two).  Chosen where the estimate says it
-// pays by more than 5 %: per frame ~1.94 us (2.2 us for rows beyond 4096 pdfs), occupancy ~3.5 ps per frame and pdf of whole-chip
-// time; the grid must leave every workgroup a CU (a fused call: half of the chip stays with the numerator).  The fused loss at
-// B = 64 is never cut (CU-time-bound: DESIGN.md §4); the denominator alone at B = 64 runs two segments, C4 (B = 32) four.
-int den_time_segments(const DenArgs& a, bool fused) {
-  const int want = a.knobs.den_tseg;
-  // (not a function of the verbose level: a debug run computes what production computes - ADVICE r5; the per-frame check of
-  // verbose >= 1 reads the totals and occupancy sums a cut call stores like an uncut one)
-  if (want == 0 || want == 1 || !a.lazy || a.shape != kShapeDma) return 1;
-  const int burn = a.knobs.den_tburn;
-  if (burn < 1) return 1;
-  // (a fused call: a quarter of the chip stays with the numerator - measured on 256 CUs, the C3 graph: B = 24 in 4 segments
-  // (192 workgroups) 1.58 ms against 2.25 in 2; B = 40 / 48 in 2 (160 / 192): 2.53 / 2.67 against 3.02 uncut; B = 32 in 4 (256): 2.59
-  // against 2.41 in 2; B = 56 in 2 (224): as uncut)
-  const int cus = fused ? device_cu_count() * 3 / 4 : device_cu_count();
-  int best = 1;
-  const double f = a.D > 4096 ? 2.2e-6 : 1.94e-6, occ = 3.5e-12 * (double)a.D * (double)a.B * (double)a.T;
-  // (not cut: the chain, 5 % of head and tail, and the part of the streamed occupancy launch that is left when the recursions
-  // end - about a third of it with sequences of one length; cut: the occupancy launch follows the recursions, + three launches)
-  double best_t = 0.95 * (1.05 * (double)a.T * f + (fused ? 0.1 : 0.35) * occ);
-  for (int S = 2; S <= kMaxTimeSegs; S *= 2) {
-    // (a forced count only has to fit the chip: the segments wait for nobody)
-    if (2 * a.B * S > (want == S ? device_cu_count() : cus) || a.T < 2 * burn) continue;
-    if (want == S) return S;
-    const double t = ((double)a.T / S + burn) * f + occ + 6e-5;
-    if (want < 0 && t < best_t) { best = S; best_t = t; }
-  }
-  return best;
-}
-
-// Would a call of the denominator alone, given a workspace with the [B,T,D] buffer, exp its rows ahead of the recursions (§3.9)?
-// (a.lazy / a.shape / a.pair decided.)  The recursion workgroups spin on rows that launch writes and each takes a whole CU, so the
-// launch must find CUs of its own whatever the order of dispatch: at least a quarter of the chip stays free of recursion
-// workgroups, else the recursions exp their rows themselves (2B >= the CU count with pairing off could hang).
-bool den_would_exp_rows_ahead(const DenArgs& a) {
-  // (not where the call is cut into time segments: the rows are written from the sequence ends inwards, a segment starts inside;
-  // not for the one-gather form of a "pdf by state" plan: its beta recursion reads its rows a frame ahead of the others)
-  // (round 6: NOT for the 16-wave maps any more - since the rows' clamp / exp sits late in the arc phase and the frame lost a dozen
-  // instructions, the recursions with their own rows are the faster ones in the only calls that still took them, the uncut ones of
-  // 65 .. 96 sequences: C3 graph, denominator alone, B = 80: 3.35 -> 3.23 ms, B = 96: 4.0 -> 3.6 ms; C4's graph and rows, B = 80,
-  // T <= 1000: 4.25 -> 3.25 ms (profiles/r06_rows_ahead.txt); four-wave workgroups keep them (C2: 0.208 against 0.214 ms); option
-  // den_dma = 3: wherever the shape allows)
-  const bool pays = a.shape == kShapeSmall || a.knobs.den_dma == 3;
-  return a.lazy && !a.sg && (a.shape == kShapeDma || a.shape == kShapeSmall) && a.knobs.den_dma != 2 && pays && !a.input_is_exp &&
-         a.D % 4 == 0 && a.D <= 4 * 5 * 512 && a.T >= 64 && 4 * den_recursion_blocks(a) <= 3 * device_cu_count() &&
-         den_time_segments(a, false) == 1;
-}
-
-// 2-byte network outputs (DenArgs::x_half) are read as they are - and the gradient written in the same type - by the lazy
-// recursions with LDS-direct rows, the pair recursion and both occupancy kernels in their float4-chunk forms; rows of a
-// multiple of 8 pdfs (a lane's 16 raw bytes are 8 elements: all inside the row or all past it).  Every other kernel family
-// (general plans, the two-barrier recursion, rows through registers, per-sequence plans of the gated schedule included)
-// reads fp32: the caller up-casts (pychain_amd/native.py does).
-bool den_call_half_native(const DenArgs& a0, int hint) {
-  if (hint == PYCHAIN_HIP_HINT_GENERAL || a0.D % 8 != 0) return false;
-  DenArgs a = a0;
-  a.lazy = den_call_is_lazy(a, hint) ? 1 : 0;
-  a.shape = a.lazy ? den_call_shape(a, hint) : 0;
-  a.pair = den_call_is_pair(a, hint) ? 1 : 0;
-  const bool rec_ok = a.pair || (a.lazy && (a.shape == kShapeDma || a.shape == kShapeSmall));
-  return rec_ok && den_occupancy_half_ok(a, (a.D + 63) / 64, hint);
-}
 // the numerator's tile recursions stage 2-byte rows in their float4-chunk forms (num_fb_kernel); the general and the
 // reference-arithmetic kernels read fp32
 bool num_half_native(const NumArgs& a) {
   return !a.general && !a.compat && a.D % 4 == 0 && a.D <= 4 * 8 * 512;
-}
-
-// option debug_corrupt_row: row[0..n) *= scale, between the recursion and the occupancy launches
-__global__ void scale_row_kernel(float* row, int n, float scale) {
-  for (int i = threadIdx.x; i < n; i += blockDim.x) row[i] *= scale;
-}
-hipError_t launch_scale_row(float* row, int n, float scale, hipStream_t st) {
-  hipLaunchKernelGGL(scale_row_kernel, dim3(1), dim3(256), 0, st, row, n, scale);
-  return hipGetLastError();
 }
 
 // Every word a call's launches count in - the caller's bad count(s) and the workspace's counters (per-sequence progress, gate
@@ -512,190 +315,9 @@ hipError_t launch_zero_words(int32_t* p0, int n0, int32_t* p1, int n1, hipStream
   hipLaunchKernelGGL(zero_words_kernel, dim3(1), dim3(256), 0, st, p0, n0, p1, n1, norm, inv_out);
   return hipGetLastError();
 }
-int den_counter_words(const DenArgs& a) { return (int)((align256(8 * (size_t)a.B) + 256 + align256(36 * (size_t)a.B)) / 4); }
+// (DenCarve: seq_progress up to tot_a)
+int den_counter_words(const DenArgs& a) { return (int)(((const char*)a.tot_a - (const char*)a.seq_progress) / 4); }
 
-// recursion + occupancy launches of one denominator call; `occupancy` = false: recursion only
-// `gamma_wait`: event every occupancy launch has to wait for (the numerator rows it folds in), or null
-// `zeroed`: an event the caller recorded on `st` behind the zeroing of the counters (the fused loss forks its numerator
-// stream there), or null: recorded here.  An event record costs the caller's stream ~7 us in front of the recursion launch.
-// `finish_early`: in/out - in: den_finish_kernel may be launched here (the caller has nothing else it must wait for);
-// out: it was (behind the recursion launch of the streamed schedule, DenArgs::occ_done), the caller must not launch it again
-hipError_t run_den_launches(DenArgs& a, int resident_slot_rows, bool occupancy, hipStream_t st, const char** why,
-                            hipEvent_t gamma_wait, hipEvent_t zeroed = nullptr, bool* finish_early = nullptr) {
-  const bool may_finish = finish_early && *finish_early;
-  if (finish_early) *finish_early = false;
-  const int gmax = (a.D + 63) / 64;
-  const int user_mask = a.phase_mask;
-  // (the counters the launches of a call share were zeroed with the bad count by the caller: launch_zero_words)
-  if (resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL) {
-    // a plan in the general format: den_general.hip, no overlap (rows in den_recursion_kernel's normalised form)
-    a.lazy = 0; a.pair = 0; a.shape = 0;
-    a.check = (occupancy && user_mask == 3) ? 1 : 0;
-    const bool corrupt_g = a.knobs.corrupt_what == 1 && a.knobs.corrupt_b < a.B && a.knobs.corrupt_t < a.T;
-    a.phase_mask = user_mask & 1;
-    hipError_t eg = a.phase_mask ? launch_den_general(a, st) : hipSuccess;
-    if (eg == hipSuccess && corrupt_g && a.phase_mask)
-      eg = launch_scale_row(a.alpha_store + ((size_t)a.knobs.corrupt_b * a.T + a.knobs.corrupt_t) * a.Hp, a.Hp, a.knobs.corrupt_scale, st);
-    if (eg == hipSuccess && gamma_wait) eg = hipStreamWaitEvent(st, gamma_wait, 0);
-    a.phase_mask = occupancy ? (user_mask & 2) : 0;
-    if (eg == hipSuccess && a.phase_mask) eg = launch_den_general(a, st);
-    a.phase_mask = user_mask;
-    return eg;
-  }
-  // (a corrupted row - option debug_corrupt_row - is written between the recursion and the occupancy launches: no overlap)
-  const bool corrupt = a.knobs.corrupt_what == 1 && a.knobs.corrupt_b < a.B && a.knobs.corrupt_t < a.T;
-  a.lazy = den_call_is_lazy(a, resident_slot_rows) ? 1 : 0;
-  a.shape = a.lazy ? den_call_shape(a, resident_slot_rows) : 0;
-  // two sequences per workgroup once the 2B one-sequence workgroups would fill the chip (option den_pair: 1 always
-  // where the shape allows, 0 never); rows in den_recursion_kernel's form
-  a.pair = den_call_is_pair(a, resident_slot_rows) ? 1 : 0;
-  a.sg = (a.lazy && a.shape == kShapeDma && den_sg_eligible(a, resident_slot_rows)) ? 1 : 0;   // (a "pdf by state" plan in the one-gather form)
-  // ... whose recursions emit the occupancies of their own second halves themselves (DenArgs::xf): a call of the denominator alone
-  // that evaluates both launches; the occupancy launch then follows the recursions and handles the bands around the middles
-  // (each direction waits for rows of the other: every workgroup of the launch must be resident at once)
-  a.xf = (a.sg && occupancy && user_mask == 3 && !corrupt && zeroed == nullptr && 2 * a.B <= device_cu_count() &&
-          den_xf_eligible(a, resident_slot_rows)) ? den_xf_band() : 0;
-  const int nseg = (occupancy && user_mask == 3 && !a.check_all && !corrupt && !a.xf) ? den_segments(a) : 1;
-  // the invariant check (DenArgs::tot_a) needs the recursions and the occupancy launches of ONE call
-  a.check = (occupancy && user_mask == 3) ? 1 : 0;
-  hipError_t e = hipSuccess;
-  // Rows exp'd ahead of the lazy recursions by a launch of its own on the side stream (DenArgs::ex), whichever schedule
-  // follows (option den_dma = 2: the recursions clamp / exp their rows themselves, as they do for short sequences, rows
-  // that are not a multiple of four pdfs and callers that hand in exp'd rows) - in a call of the denominator alone and a
-  // workspace that holds the buffer.  NOT in the fused loss (`zeroed`): there the CUs the recursions leave idle are booked - the
-  // numerator until T/2, the occupancy launch from there to the end - and the launch's registers and HBM traffic held the
-  // numerator back by 1 ms (C3: 3.02 -> 3.31 ms per step with it, although the recursion itself ran 4 % faster:
-  // profiles/r04_u_C3_step_timeline_rows_exp_ahead_in_the_fused_step.txt).
-  const bool exp_ahead = a.ex != nullptr && zeroed == nullptr && den_would_exp_rows_ahead(a) && (user_mask & 1) != 0;
-  SideStream* const side_pre = exp_ahead ? side_streams_for(st) : nullptr;
-  if (exp_ahead && !side_pre) { *why = "cannot create the side streams"; return hipErrorInvalidValue; }
-  bool forked = false;                                      // stream2 waits for the zeroed counters (and the caller's x)
-  auto fork_stream2 = [&](SideStream* side) -> hipError_t {
-    if (forked) return hipSuccess;
-    forked = true;
-    hipError_t ef = zeroed ? hipSuccess : hipEventRecord(side->seg[0], st);
-    if (ef == hipSuccess) ef = hipStreamWaitEvent(side->stream2, zeroed ? zeroed : side->seg[0], 0);
-    return ef;
-  };
-  if (exp_ahead) {
-    e = fork_stream2(side_pre);
-    den_exp_rows_shape(a, device_cu_count(), &a.ex_nr, &a.ex_q);
-    if (e == hipSuccess) e = launch_den_exp_rows(a, side_pre->stream2);
-    a.use_ex = 1;
-  }
-  // Time segments: recursion launch over 2 B S workgroups, the check of every speculated row, the ordinary recursion launch as
-  // a fallback that runs only if a row did not verify, then the occupancy launch (no overlap: den_time_segments)
-  const int tseg = exp_ahead ? 1 : den_time_segments(a, zeroed != nullptr);   // (den_would_exp_rows_ahead: false where this says > 1)
-  if (tseg > 1) {
-    const int mask = occupancy ? user_mask : (user_mask & 1);
-    if (mask & 1) {
-      a.phase_mask = 1; a.tseg = tseg; a.tburn = a.knobs.den_tburn;
-      e = launch_den(a, gmax, resident_slot_rows, st, why);
-      if (e == hipSuccess) e = launch_den_splice_check(a, st);
-      const int keep = a.tseg;
-      a.tseg = 0; a.redo_if = 1;
-      if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, st, why);
-      a.redo_if = 0; a.tseg = keep;                       // (den_finish_kernel: an inner segment's NaN report)
-      if (e == hipSuccess && corrupt)
-        e = launch_scale_row(a.alpha_store + ((size_t)a.knobs.corrupt_b * a.T + a.knobs.corrupt_t) * a.Hp, a.Hp, a.knobs.corrupt_scale, st);
-    }
-    if (e == hipSuccess && gamma_wait && (mask & 2)) e = hipStreamWaitEvent(st, gamma_wait, 0);
-    if (e == hipSuccess && (mask & 2)) { a.phase_mask = 2; e = launch_den(a, gmax, resident_slot_rows, st, why); }
-    a.phase_mask = user_mask;
-    return e;
-  }
-  if (nseg <= 1) {
-    const int mask = occupancy ? user_mask : (user_mask & 1);
-    if ((gamma_wait || corrupt) && (mask & 2)) {
-      a.phase_mask = mask & 1;
-      if (a.phase_mask) e = launch_den(a, gmax, resident_slot_rows, st, why);
-      if (e == hipSuccess && corrupt && a.phase_mask)
-        e = launch_scale_row(a.alpha_store + ((size_t)a.knobs.corrupt_b * a.T + a.knobs.corrupt_t) * a.Hp, a.Hp, a.knobs.corrupt_scale, st);
-      if (e == hipSuccess && gamma_wait) e = hipStreamWaitEvent(st, gamma_wait, 0);
-      a.phase_mask = 2;
-      if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, st, why);
-    } else {
-      a.phase_mask = mask;
-      e = launch_den(a, gmax, resident_slot_rows, st, why);
-    }
-    a.phase_mask = user_mask;
-    if (exp_ahead) {                                        // (long done: the recursions have read every row of it)
-      a.use_ex = 0;
-      if (e == hipSuccess) e = hipEventRecord(side_pre->join2, side_pre->stream2);
-      if (e == hipSuccess) e = hipStreamWaitEvent(st, side_pre->join2, 0);
-    }
-    return e;
-  }
-  SideStream* side = side_streams_for(st);
-  if (!side) { *why = "cannot create the side streams"; return hipErrorInvalidValue; }
-  // Frame t becomes computable after max(t, L-1-t) recursion steps, i.e. nothing before T/2 and
-  // then ever faster: segment ends at T/2, 3T/4, 7T/8, ... so every occupancy launch but the
-  // last overlaps the next recursion segment and the last one holds ~2^-(nseg-1) of the frames.
-  for (int s = 0; s < nseg; s++) {
-    const double frac = s == nseg - 1 ? 1.0 : 1.0 - 1.0 / (double)(2 << s);
-    a.seg_bound[s] = s == nseg - 1 ? a.T : ((int)(frac * a.T) + 31) / 32 * 32;
-  }
-  if (a.knobs.den_segments == 0 && den_stream_eligible(a, gmax, resident_slot_rows)) {
-    // Streamed schedule (DenArgs::stream, den_kernels.hip: stream_take): ONE recursion launch whose workgroups report
-    // per-sequence progress, ONE persistent occupancy launch on the side stream - released when every recursion
-    // workgroup has passed T/2 (nothing is computable before; the numerator has the idle CUs until then) - that draws
-    // rings of frames from a queue in the order in which they become computable.  No segment granularity, no exposed last
-    // launch: what is left when the recursions end is the last ring of every sequence.
-    a.stream = 1; a.sig_n = 1; a.stream_blocks = device_cu_count();
-    a.seg_bound[0] = std::min(a.T, (a.T / 2 + 31) / 32 * 32);
-    // (The other way round - the recursion launch on the side stream, gate and occupancy launch on the caller's, so that the
-    // launch that ends last is followed in queue order - was measured: the wake-up of a queue that waits for another queue's
-    // event costs 11-19 us wherever it sits, and there the recursion paid it at the head of the step:
-    // profiles/r04_i_C3_step_timeline_recursion_on_side_stream.txt.)
-    if (e == hipSuccess) e = fork_stream2(side);              // (the occupancy launch must see the zeroed counters)
-    a.phase_mask = 1;
-    if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, st, why);
-    if (e == hipSuccess) e = launch_den_gate(a.progress, den_recursion_blocks(a), a.bad, side->stream2);
-    if (e == hipSuccess && gamma_wait) e = hipStreamWaitEvent(side->stream2, gamma_wait, 0);
-    a.phase_mask = 2; a.gam_nseg = 0; a.gam_seg = 0; a.stream = 3;
-    a.occ_done_target = may_finish ? a.stream_blocks : 0;
-    if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, side->stream2, why);
-    if (e == hipSuccess) e = hipEventRecord(side->join2, side->stream2);
-    a.phase_mask = user_mask; a.sig_n = 0; a.stream = 0; a.use_ex = 0;
-    if (e == hipSuccess && may_finish) { e = launch_den_finish(a, st); *finish_early = true; }   // (DenArgs::occ_done)
-    a.occ_done_target = 0;
-    if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join2, 0);
-    return e;
-  }
-  // Gated schedule (rounds 1-2; the fallback for the two-barrier recursion and per-sequence plans, and what option
-  // den_segments = n asks for): ONE recursion launch; its workgroups count themselves into progress[s] when their steps
-  // below seg_bound[s] are done, and a one-wave gate kernel in front of occupancy launch s (side stream) waits for all
-  // of them.  (One recursion launch per segment with stream events in between - the first form of this schedule - measured
-  // 2 % slower and is gone: profiles/r01_*.)
-  a.sig_n = nseg - 1;
-  if (e == hipSuccess) e = fork_stream2(side);                // the gates must see the zeroed counters
-  a.phase_mask = 1;
-  if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, st, why);
-  a.phase_mask = 2; a.gam_nseg = nseg;
-  for (int s = 0; s < nseg - 1 && e == hipSuccess; s++) {
-    a.gam_seg = s;
-    e = launch_den_gate(a.progress + s, den_recursion_blocks(a), a.bad, side->stream2);
-    if (e == hipSuccess && s == 0 && gamma_wait) e = hipStreamWaitEvent(side->stream2, gamma_wait, 0);
-    if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, side->stream2, why);
-  }
-  // the last occupancy launch follows the recursion in stream order on the caller's stream
-  a.gam_seg = nseg - 1;
-  if (e == hipSuccess && gamma_wait) e = hipStreamWaitEvent(st, gamma_wait, 0);
-  if (e == hipSuccess) e = launch_den(a, gmax, resident_slot_rows, st, why);
-  if (e == hipSuccess) e = hipEventRecord(side->join2, side->stream2);
-  if (e == hipSuccess) e = hipStreamWaitEvent(st, side->join2, 0);
-  a.phase_mask = user_mask; a.gam_nseg = 0; a.sig_n = 0; a.use_ex = 0;
-  return e;
-}
-// ... and, behind all of them on the caller's stream, den_finish_kernel: objf from the per-frame totals and
-// the reference's invariant check (DenArgs::tot_a)
-hipError_t run_den(DenArgs& a, int resident_slot_rows, bool occupancy, hipStream_t st, const char** why,
-                   hipEvent_t gamma_wait = nullptr) {
-  bool finished = gamma_wait == nullptr;                 // (a caller with an event of its own launches den_finish_kernel itself)
-  hipError_t e = run_den_launches(a, resident_slot_rows, occupancy, st, why, gamma_wait, nullptr, &finished);
-  if (e == hipSuccess && (a.phase_mask & 1) && !finished) e = launch_den_finish(a, st);   // objf (+ the check) from the stored totals
-  return e;
-}
 }  // namespace
 
 // ---- the burn-in controller state of a plan (DenArgs::tstate): a caller-owned device blob, attached by plan address
@@ -717,47 +339,24 @@ extern "C" int pychain_hip_den_tseg_state(const void* plans_dev, void* state_dev
 }
 extern "C" size_t pychain_hip_den_tseg_state_bytes(void) { return kTsegStateWords * sizeof(int32_t); }
 
-extern "C" int pychain_hip_den_uses_row_buffer(int64_t plan_stride_bytes, int resident_slot_rows, int H, int D, int B, int T,
+extern "C" int pychain_hip_den_uses_row_buffer(int64_t plan_stride_bytes, int hint, int H, int D, int B, int T,
                                               int input_is_exp) {
-  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL) return 0;
-  DenArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan_stride = plan_stride_bytes; a.B = B; a.T = T; a.D = D; a.H = H; a.Hp = roundup64(H); a.input_is_exp = input_is_exp ? 1 : 0;
-  a.knobs = call_knobs();
-  a.lazy = den_call_is_lazy(a, resident_slot_rows) ? 1 : 0;
-  a.shape = a.lazy ? den_call_shape(a, resident_slot_rows) : 0;
-  a.pair = den_call_is_pair(a, resident_slot_rows) ? 1 : 0;
-  a.sg = (a.lazy && a.shape == kShapeDma && den_sg_eligible(a, resident_slot_rows)) ? 1 : 0;
-  return den_would_exp_rows_ahead(a) ? 1 : 0;
+  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || hint == PYCHAIN_HIP_HINT_GENERAL) return 0;
+  return den_would_exp_rows_ahead(den_query_args(plan_stride_bytes, hint, H, D, B, T, false, input_is_exp != 0)) ? 1 : 0;
 }
 
-extern "C" int pychain_hip_den_time_segments(int64_t plan_stride_bytes, int resident_slot_rows, int H, int D, int B, int T, int fused) {
-  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL) return 1;
-  DenArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan_stride = plan_stride_bytes; a.B = B; a.T = T; a.D = D; a.H = H; a.Hp = roundup64(H); a.frames_per_block = 32;
-  a.knobs = call_knobs();
-  a.fused = fused ? 1 : 0;
-  a.check_all = a.knobs.verbose >= 1 ? 1 : 0;
-  a.lazy = den_call_is_lazy(a, resident_slot_rows) ? 1 : 0;
-  a.shape = a.lazy ? den_call_shape(a, resident_slot_rows) : 0;
-  a.pair = den_call_is_pair(a, resident_slot_rows) ? 1 : 0;
-  a.sg = (a.lazy && a.shape == kShapeDma && den_sg_eligible(a, resident_slot_rows)) ? 1 : 0;
-  return den_time_segments(a, fused != 0);
+extern "C" int pychain_hip_den_time_segments(int64_t plan_stride_bytes, int hint, int H, int D, int B, int T, int fused) {
+  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || hint == PYCHAIN_HIP_HINT_GENERAL) return 1;
+  return den_time_segments(den_query_args(plan_stride_bytes, hint, H, D, B, T, fused != 0), fused != 0);
 }
 namespace {
-int den_half_native_q(int64_t plan_stride_bytes, int resident_slot_rows, int H, int D, int B, int T, int fused) {
+int den_half_native_q(int64_t plan_stride_bytes, int hint, int H, int D, int B, int T, bool fused) {
   if (B <= 0 || T <= 0 || H <= 0 || D <= 0) return 0;
-  DenArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan_stride = plan_stride_bytes; a.B = B; a.T = T; a.D = D; a.H = H; a.Hp = roundup64(H); a.frames_per_block = 32;
-  a.knobs = call_knobs();
-  a.fused = fused;
-  return den_call_half_native(a, resident_slot_rows) ? 1 : 0;
+  return den_call_half_native(den_query_args(plan_stride_bytes, hint, H, D, B, T, fused), hint) ? 1 : 0;
 }
 }  // namespace
-extern "C" int pychain_hip_den_half_native(int64_t plan_stride_bytes, int resident_slot_rows, int H, int D, int B, int T) {
-  return den_half_native_q(plan_stride_bytes, resident_slot_rows, H, D, B, T, 0);
+extern "C" int pychain_hip_den_half_native(int64_t plan_stride_bytes, int hint, int H, int D, int B, int T) {
+  return den_half_native_q(plan_stride_bytes, hint, H, D, B, T, false);
 }
 extern "C" int pychain_hip_num_half_native(int H, int K, int D) {
   if (H <= 0 || K <= 0 || D <= 0) return 0;
@@ -766,16 +365,12 @@ extern "C" int pychain_hip_num_half_native(int H, int K, int D) {
   n.H = H; n.K = K; n.D = D; n.general = num_needs_general(H, K, D) ? 1 : 0; n.compat = call_knobs().num_compat;
   return num_half_native(n) ? 1 : 0;
 }
-extern "C" int pychain_hip_chain_loss_half_native(int64_t plan_stride_bytes, int resident_slot_rows, int den_H, int D, int B, int T,
+extern "C" int pychain_hip_chain_loss_half_native(int64_t plan_stride_bytes, int hint, int den_H, int D, int B, int T,
                                                   int num_H, int num_K) {
-  if (!den_half_native_q(plan_stride_bytes, resident_slot_rows, den_H, D, B, T, 1) || !pychain_hip_num_half_native(num_H, num_K, D)) return 0;
-  DenArgs a;
-  memset(&a, 0, sizeof(a));
-  a.plan_stride = plan_stride_bytes; a.B = B; a.T = T; a.D = D; a.H = den_H; a.Hp = roundup64(den_H); a.frames_per_block = 32;
-  a.knobs = call_knobs();
-  a.fused = 1;
+  if (!den_half_native_q(plan_stride_bytes, hint, den_H, D, B, T, true) || !pychain_hip_num_half_native(num_H, num_K, D)) return 0;
+  DenArgs a = den_query_args(plan_stride_bytes, hint, den_H, D, B, T, true);
   a.fold_rows = (const float*)1;                          // (the fold's extra LDS counts: gamma2_lds_bytes)
-  return den_uses_gamma2(a, (D + 63) / 64, resident_slot_rows) ? 1 : 0;
+  return den_uses_gamma2(a, (D + 63) / 64, hint) ? 1 : 0;
 }
 
 // ---- test hook: a long-lived kernel that pins CUs on another stream of the same process, as the channels of an overlapped
@@ -821,24 +416,24 @@ extern "C" int pychain_hip_debug_launch_map(int T, int L, int t, int frames_per_
 }
 
 extern "C" int pychain_hip_den_forward_backward(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int H, int D,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int H, int D,
     const void* nnet_output, int nnet_output_dtype, int input_is_exp, const int64_t* seq_lengths,
     int B, int T, float leaky_hmm_coefficient, float grad_scale,
     float* objf_per_seq, void* grad, int32_t* bad_count, float* totals,
     void* workspace, size_t workspace_bytes, void* stream) {
   DenArgs a;
-  int rc = fill_den_args(a, plans_dev, plan_stride_bytes, resident_slot_rows, H, D, nnet_output, nnet_output_dtype, input_is_exp, seq_lengths, B, T,
+  int rc = fill_den_args(a, plans_dev, plan_stride_bytes, hint, H, D, nnet_output, nnet_output_dtype, input_is_exp, seq_lengths, B, T,
                          leaky_hmm_coefficient, grad_scale, objf_per_seq, grad, bad_count, workspace,
                          workspace_bytes, "den_forward_backward");
   if (rc != PYCHAIN_HIP_OK) return rc;
   a.loss_out = totals;                                 // (sum of the per-sequence objectives, frames, bad count: den_finish_kernel)
-  if (a.x_half && !den_call_half_native(a, resident_slot_rows))
+  if (a.x_half && !den_call_half_native(a, hint))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "den_forward_backward: this shape does not take 2-byte network outputs (pychain_hip_den_half_native)");
   hipStream_t st = (hipStream_t)stream;
   if (launch_zero_words(bad_count, 1, a.seq_progress, den_counter_words(a), st) != hipSuccess)
     return fail(PYCHAIN_HIP_ELAUNCH, "den_forward_backward: cannot zero the counters");
   const char* why = nullptr;
-  hipError_t e = run_den(a, resident_slot_rows, true, st, &why);
+  hipError_t e = run_den(a, hint, true, st, &why);
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "den_forward_backward: %s",
                 why ? why : hipGetErrorString(e));
@@ -1042,7 +637,7 @@ extern "C" int pychain_hip_align(
 namespace {
 // one fused call over the B sequences it is given (pychain_hip_chain_loss_forward: all of them, or one slice of a large batch)
 int chain_loss_forward_one(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
@@ -1053,7 +648,7 @@ int chain_loss_forward_one(
   if (!bad_count) return fail(PYCHAIN_HIP_EINVAL, "%s: null bad_count", who);
   DenArgs da;
   // without `grad` only the recursions run; any non-null aligned pointer then passes the checks
-  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, resident_slot_rows, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, leaky,
+  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, hint, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, leaky,
                          grad_scale, den_objf, grad ? grad : den_ws, bad_count, den_ws, den_ws_bytes, who);
   if (rc != PYCHAIN_HIP_OK) return rc;
   NumArgs na;
@@ -1073,7 +668,7 @@ int chain_loss_forward_one(
   // a device-side normaliser of the loss (loss_norm_dev: ChainLoss(avg=True) with the lengths on the device) also divides the
   // gradient written here: its reciprocal goes into a spare counter word at the head of the call and the occupancy launches
   // of both sides read it (DenArgs / NumArgs::grad_scale_dev) - not a pass over [B, T, D] behind the call
-  float* inv_norm = (loss_norm_dev && grad) ? reinterpret_cast<float*>(da.progress + 56) : nullptr;
+  float* inv_norm = (loss_norm_dev && grad) ? reinterpret_cast<float*>(da.progress + kCtrInvNorm) : nullptr;
   if (inv_norm) { da.grad_scale_dev = inv_norm; na.grad_scale_dev = inv_norm; }
   hipError_t e = launch_zero_words(bad_count, 2, da.seq_progress, den_counter_words(da), st, loss_norm_dev, inv_norm);
   // The two-frame occupancy kernel folds the numerator in (grad = scale * (gamma_den - gamma_num), written
@@ -1081,14 +676,14 @@ int chain_loss_forward_one(
   // launches wait for them.  Otherwise the numerator is accumulated into the gradient afterwards.
   // (decided with the fold's own LDS rows counted in: gamma2_lds_bytes)
   da.fold_rows = na.rows_ws;
-  const bool fold = grad && resident_slot_rows != PYCHAIN_HIP_HINT_GENERAL && !na.general && !na.compat &&
-                    den_uses_gamma2(da, (D + 63) / 64, resident_slot_rows);
+  const bool fold = grad && hint != PYCHAIN_HIP_HINT_GENERAL && !na.general && !na.compat &&
+                    den_uses_gamma2(da, (D + 63) / 64, hint);
   if (fold) {
     da.fold_upd = na.upd_ws; da.fold_ucount = na.ucount_ws; da.fold_K = num_K;
     da.fold_scale = -grad_scale;
   } else da.fold_rows = nullptr;
   // 2-byte network outputs: both sides take them and the gradient is written once, by the fold (chain_loss_half_native)
-  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !(den_call_half_native(da, resident_slot_rows) && num_half_native(na) && (fold || !grad)))
+  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !(den_call_half_native(da, hint) && num_half_native(na) && (fold || !grad)))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_chain_loss_half_native)", who);
   // fork: numerator on the side stream, denominator recursion on the caller's stream
   if (e == hipSuccess) e = hipEventRecord(side->fork, st);
@@ -1104,7 +699,7 @@ int chain_loss_forward_one(
   // (den_finish_kernel reads the numerator's objectives and its bad count for `totals`: the join precedes it)
   // (den_finish_kernel needs the numerator's objectives and bad count: early only where the occupancy launch waits for them)
   bool finished = fold;
-  if (e == hipSuccess) e = run_den_launches(da, resident_slot_rows, grad != nullptr, st, &why, fold ? side->join : nullptr, side->fork, &finished);
+  if (e == hipSuccess) e = run_den_launches(da, hint, grad != nullptr, st, &why, fold ? side->join : nullptr, side->fork, &finished);
   // join (a call whose occupancy launch folded the numerator in has it behind it already: that launch waited for the numerator's
   // event and the caller's stream for that launch - one barrier packet less, ~5 us, between it and den_finish_kernel)
   const bool joined = fold && da.phase_mask == 3;     // (every schedule of run_den_launches puts the wait in front of its first occupancy launch)
@@ -1160,9 +755,9 @@ __global__ void chain_slices_combine_kernel(const SliceLine* lines, int nslices,
   }
 }
 // slices of a fused call over B sequences (1 = the call as it is)
-int chain_loss_slices(int B, int resident_slot_rows, int64_t plan_stride_bytes, bool with_grad) {
+int chain_loss_slices(int B, int hint, int64_t plan_stride_bytes, bool with_grad) {
   const int want = call_knobs().chain_slices;
-  if (!with_grad || want == 0 || want == 1 || resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL || plan_stride_bytes != 0) return 1;
+  if (!with_grad || want == 0 || want == 1 || hint == PYCHAIN_HIP_HINT_GENERAL || plan_stride_bytes != 0) return 1;
   const int cus = device_cu_count();
   int n = 1;
   if (want >= 2) n = want;
@@ -1191,12 +786,12 @@ bool workspace_was_sliced(const void* den_ws) {
 }
 }  // namespace
 
-extern "C" int pychain_hip_chain_loss_slices(int64_t plan_stride_bytes, int resident_slot_rows, int B) {
-  return chain_loss_slices(B, resident_slot_rows, plan_stride_bytes, true);
+extern "C" int pychain_hip_chain_loss_slices(int64_t plan_stride_bytes, int hint, int B) {
+  return chain_loss_slices(B, hint, plan_stride_bytes, true);
 }
 
 extern "C" int pychain_hip_chain_loss_forward_tw(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
@@ -1205,10 +800,10 @@ extern "C" int pychain_hip_chain_loss_forward_tw(
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
   const int nsl = (B > 0 && T > 0 && D > 0 && den_ws && bad_count && den_objf && num_objf && seq_lengths && nnet_output && ft && fi && fp &&
                    bt && bi && bp && initial && final_ && den_ws_bytes > 8192)
-                      ? chain_loss_slices(B, resident_slot_rows, plan_stride_bytes, grad != nullptr) : 1;
+                      ? chain_loss_slices(B, hint, plan_stride_bytes, grad != nullptr) : 1;
   note_forward_workspace(den_ws, nsl > 1);
   if (nsl <= 1)
-    return chain_loss_forward_one(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
+    return chain_loss_forward_one(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
                                   graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, den_objf, num_objf,
                                   grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes,
                                   stream, time_windows);
@@ -1225,7 +820,7 @@ extern "C" int pychain_hip_chain_loss_forward_tw(
     const int nb = std::min(per, B - b0);
     const size_t g = graph_batch_stride ? (size_t)b0 : 0;     // per-sequence numerator graphs: [G, K, 3] / [G, H, 2] / [G, K] / [G, H]
     const int rc = chain_loss_forward_one(
-        plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky,
+        plans_dev, plan_stride_bytes, hint, den_H, leaky,
         ft + g * num_K * 3, fi + g * num_H * 2, fp + g * num_K, bt + g * num_K * 3, bi + g * num_H * 2, bp + g * num_K,
         initial + g * num_H, final_ + g * num_H, graph_batch_stride, num_H, num_K,
         (const char*)nnet_output + (size_t)b0 * T * D * esz, nnet_output_dtype, seq_lengths + b0, nb, T, D,
@@ -1242,14 +837,14 @@ extern "C" int pychain_hip_chain_loss_forward_tw(
 }
 
 extern "C" int pychain_hip_chain_loss_forward(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
-  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp, initial,
+  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial,
                                            final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D,
                                            den_objf, num_objf, grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws,
                                            den_ws_bytes, num_ws, num_ws_bytes, stream, nullptr);
@@ -1330,7 +925,7 @@ extern "C" int pychain_hip_loss_total(const float* den_objf_per_seq, const float
 
 namespace {
 int chain_loss_backward_impl(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H,
     const int32_t* ft, const int32_t* fi, const float* fp, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float grad_scale, const float* grad_scale_dev, void* grad, int32_t* bad_count,
@@ -1345,14 +940,12 @@ int chain_loss_backward_impl(
   float dummy_coef = 0.5f;       // the occupancy launch does not use the leaky coefficient
   if (nnet_output_dtype != PYCHAIN_HIP_F32)              // (the numerator's occupancy launch accumulates into an fp32 gradient)
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: 2-byte network outputs are taken by the forward call that also writes the gradient", who);
-  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, resident_slot_rows, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, dummy_coef,
+  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, hint, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, dummy_coef,
                          grad_scale, (float*)den_ws, grad, bad_count, den_ws, den_ws_bytes, who);
   if (rc != PYCHAIN_HIP_OK) return rc;
   da.grad_scale_dev = grad_scale_dev;
   da.fused = 1;                                          // (the forward call that stored the rows decided as a fused call)
-  da.lazy = den_call_is_lazy(da, resident_slot_rows) ? 1 : 0;
-  da.shape = da.lazy ? den_call_shape(da, resident_slot_rows) : 0;
-  da.sg = (da.lazy && da.shape == kShapeDma && den_sg_eligible(da, resident_slot_rows)) ? 1 : 0;   // (what the stored alpha rows ARE: DenArgs::sg)
+  den_decide_family(da, hint);                           // (what the stored rows ARE: DenArgs::lazy, DenArgs::sg)
   NumArgs na;
   // the occupancy launch reads only the forward transitions / indices / log-probs of the graphs
   rc = fill_num_args(na, ft, fi, fp, ft, fi, fp, fp, fp,
@@ -1365,7 +958,7 @@ int chain_loss_backward_impl(
   hipError_t e = zero_bad ? hipMemsetAsync(bad_count, 0, 2 * sizeof(int32_t), st) : hipSuccess;
   da.phase_mask = 2;
   if (e == hipSuccess)
-    e = resident_slot_rows == PYCHAIN_HIP_HINT_GENERAL ? launch_den_general(da, st) : launch_den(da, (D + 63) / 64, resident_slot_rows, st, &why);
+    e = hint == PYCHAIN_HIP_HINT_GENERAL ? launch_den_general(da, st) : launch_den(da, (D + 63) / 64, hint, st, &why);
   if (e == hipSuccess) e = na.compat ? launch_num_compat(na, 2, st) : launch_num_occ(na, false, st, &why);
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
@@ -1375,18 +968,18 @@ int chain_loss_backward_impl(
 }  // namespace
 
 extern "C" int pychain_hip_chain_loss_backward(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H,
     const int32_t* ft, const int32_t* fi, const float* fp, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float grad_scale, const float* grad_scale_dev, void* grad, int32_t* bad_count,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
-  return chain_loss_backward_impl(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, ft, fi, fp, graph_batch_stride,
+  return chain_loss_backward_impl(plans_dev, plan_stride_bytes, hint, den_H, ft, fi, fp, graph_batch_stride,
                                   num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, grad_scale, grad_scale_dev, grad,
                                   bad_count, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, true);
 }
 
 extern "C" int pychain_hip_chain_loss_forward_backward_tw(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D, float grad_scale,
@@ -1394,21 +987,21 @@ extern "C" int pychain_hip_chain_loss_forward_backward_tw(
     float loss_scale, const float* loss_norm_dev, float* totals,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
   if (!grad) return fail(PYCHAIN_HIP_EINVAL, "chain_loss_forward_backward: null grad");
-  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt,
+  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt,
                                            bi, bp, initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
                                            seq_lengths, B, T, D, den_objf, num_objf, grad, grad_scale, bad_count, loss_scale,
                                            loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows);
 }
 
 extern "C" int pychain_hip_chain_loss_forward_backward(
-    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_H, float leaky,
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D, float grad_scale,
     float* den_objf, float* num_objf, void* grad, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
-  return pychain_hip_chain_loss_forward_backward_tw(plans_dev, plan_stride_bytes, resident_slot_rows, den_H, leaky, ft, fi, fp, bt, bi, bp,
+  return pychain_hip_chain_loss_forward_backward_tw(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp,
                                                     initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
                                                     seq_lengths, B, T, D, grad_scale, den_objf, num_objf, grad, bad_count, loss_scale,
                                                     loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, nullptr);

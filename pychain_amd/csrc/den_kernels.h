@@ -12,6 +12,10 @@ namespace pychain_hip {
 enum { kShapeRegs = 0, kShapeDma = 2, kShapeSmall = 3 };
 constexpr int kMaxTimeSegs = 4;
 
+// Who writes what (den_policy.hip).  The CALL decides once, in the caller's struct, and every launch of the call - den_finish_kernel
+// behind them included - sees it: lazy, pair, shape, sg (den_decide_family), xf, check, check_all, tseg / tburn, ex_nr / ex_q,
+// seg_bound, stream_blocks.  One LAUNCH gets, in a copy of its own that a schedule forms: phase_mask (the caller's struct keeps the
+// caller's mask), stream, sig_n, gam_seg / gam_nseg, use_ex, redo_if (and tseg = 0 with it), occ_done_target.
 struct DenArgs {
   const char* plans;         // device plan(s)
   int64_t plan_stride;       // bytes between per-sequence plans, 0 = shared
@@ -30,7 +34,7 @@ struct DenArgs {
   // b(t,.) + c(t), each in a per-frame scale of its own; 0: as den_recursion_kernel (rows normalised).  The
   // occupancy kernels read either form as it is; den_finish_kernel needs to know which scales were divided out.
   int lazy;
-  int fused;                  // the call is a fused loss (a numerator runs beside it): api.hip decides pair / time segments by it
+  int fused;                  // the call is a fused loss (a numerator runs beside it): den_policy.hip decides pair / time segments by it
   // 1: the recursions run as den_recursion_pair_kernel (den_pair.inc.h): two sequences per workgroup, ceil(B/2)
   // workgroups per direction; rows as den_recursion_kernel stores them (lazy = 0).  Shared plan only.
   int pair;
@@ -163,24 +167,24 @@ __device__ __forceinline__ bool den_tseg_off(const DenArgs& a) {
 
 // true if the recursion of this call runs as den_recursion_lazy_kernel (decided once per call; the occupancy
 // launches - also those of a later chain_loss_backward on the same workspace - must be told: DenArgs::lazy)
-bool den_lazy_eligible(const DenArgs& a, int resident_slot_rows);
+bool den_lazy_eligible(const DenArgs& a, int hint);
 // ... with LDS-direct rows (16 waves), and in four-wave workgroups (DenArgs::shape)
-bool den_dma_eligible(const DenArgs& a, int resident_slot_rows);
-bool den_small_eligible(const DenArgs& a, int resident_slot_rows);
+bool den_dma_eligible(const DenArgs& a, int hint);
+bool den_small_eligible(const DenArgs& a, int hint);
 // true if the occupancy pass of this call can run as ONE persistent launch beside the recursion (DenArgs::stream): the
 // recursion kernel of the call reports per-sequence progress (lazy and pair forms), one plan for all sequences
-bool den_stream_eligible(const DenArgs& a, int gamma_max_groups, int resident_slot_rows);
+bool den_stream_eligible(const DenArgs& a, int gamma_max_groups, int hint);
 // names of the kernels launch_den would run for this call: recursion, occupancy (measurement tools and the
 // kernel-selection test label by them)
-const char* den_recursion_kernel_name(const DenArgs& a, int resident_slot_rows);
-const char* den_occupancy_kernel_name(const DenArgs& a, int gamma_max_groups, int resident_slot_rows);
+const char* den_recursion_kernel_name(const DenArgs& a, int hint);
+const char* den_occupancy_kernel_name(const DenArgs& a, int gamma_max_groups, int hint);
 // ... as den_recursion_pair_kernel (DenArgs::pair); den_pair_blocks: its grid = what a progress counter reaches
-bool den_pair_eligible(const DenArgs& a, int resident_slot_rows);
+bool den_pair_eligible(const DenArgs& a, int hint);
 // ... in the one-gather form of a "pdf by state" plan (launch hint bit 27; a.shape == kShapeDma, a.use_ex / a.x_half decided)
-bool den_sg_eligible(const DenArgs& a, int resident_slot_rows);
+bool den_sg_eligible(const DenArgs& a, int hint);
 // ... with the crossing (DenArgs::xf); the band half-width it uses
-bool den_xf_eligible(const DenArgs& a, int resident_slot_rows);
-bool den_q_eligible(const DenArgs& a, int resident_slot_rows);    // one-word state vectors (option den_q; den_lazy.inc.h: MAP::kQ)
+bool den_xf_eligible(const DenArgs& a, int hint);
+bool den_q_eligible(const DenArgs& a, int hint);    // one-word state vectors (option den_q; den_lazy.inc.h: MAP::kQ)
 int den_xf_band();
 // is frame t of a length-L sequence one the occupancy launch of a crossing call evaluates (DenArgs::xf)?  `cut`: the call's rows
 // come from its time segments (else from the uncut recursion - also after a splice miss)
@@ -196,10 +200,10 @@ __host__ __device__ inline bool den_xf_band_frame(int t, int L, int nseg, int w)
 }
 int den_recursion_blocks(const DenArgs& a);
 hipError_t launch_den_splice_check(const DenArgs& a, hipStream_t st);
-bool den_occupancy_half_ok(const DenArgs& a, int gamma_max_groups, int resident_slot_rows);
+bool den_occupancy_half_ok(const DenArgs& a, int gamma_max_groups, int hint);
 
 // true if launch_den would run the two-frame occupancy kernel (the only one that can fold the numerator in)
-bool den_uses_gamma2(const DenArgs& a, int gamma_max_groups, int resident_slot_rows);
+bool den_uses_gamma2(const DenArgs& a, int gamma_max_groups, int hint);
 
 // the recursion launch of a call by its kernel family (den_lazy.hip: lazy / pair by a.pair, a.shape; den_rec.hip: the two-
 // barrier kernel): called by launch_den
@@ -208,7 +212,7 @@ hipError_t launch_den_rec2b(const DenArgs& a, int hint, size_t lds_rec, hipStrea
 
 // Enqueues the two launches on `st`.  On failure returns the HIP error and, when the
 // shape is unsupported, a reason in *why.
-hipError_t launch_den(const DenArgs& a, int gamma_max_groups, int resident_slot_rows, hipStream_t st,
+hipError_t launch_den(const DenArgs& a, int gamma_max_groups, int hint, hipStream_t st,
                       const char** why);
 
 // test hook behind pychain_hip_debug_launch_map (host code only)

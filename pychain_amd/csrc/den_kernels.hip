@@ -991,8 +991,8 @@ hipError_t launch_gamma_stream(const DenArgs& a, int r, size_t lds, dim3 grid, h
 }
 inline bool gamma_stream_shape_ok(const DenArgs& a, int hint, int gamma_max_groups) {
   if (a.plan_stride != 0) return false;
-  if (gamma2_eligible(a, (hint >> 20) & 127, gamma_max_groups)) return true;
-  const int r = pick_r(a, (hint >> 10) & 511, 2 * a.Hp);
+  if (gamma2_eligible(a, decode_hint(hint).occ2_rows, gamma_max_groups)) return true;
+  const int r = pick_r(a, decode_hint(hint).occ_rows, 2 * a.Hp);
   return a.D % 4 == 0 && a.D <= 4 * 4 * kNT && r > 0;
 }
 
@@ -1006,13 +1006,13 @@ hipError_t launch_r(const DenArgs& a, int hint, size_t lds_rec, size_t lds_gam, 
   if (a.phase_mask & 2) {
     const bool stream = (a.stream & 2) != 0;            // ONE persistent launch over the whole queue (DenArgs::stream)
     const dim3 grid = stream ? dim3(a.stream_blocks) : dim3(gx, a.B);
-    if (gamma2_eligible(a, (hint >> 20) & 127, gamma_max_groups)) {
+    if (gamma2_eligible(a, decode_hint(hint).occ2_rows, gamma_max_groups)) {
       const size_t lds2 = gamma2_lds_bytes(a, gamma_max_groups);
-      const int r2 = a.sg ? PLAN_RESIDENT_0 : (hint >> 20) & 127;       // (the tile over states: at most PLAN_RESIDENT_0 rows per wave)
+      const int r2 = a.sg ? PLAN_RESIDENT_0 : decode_hint(hint).occ2_rows;       // (the tile over states: at most PLAN_RESIDENT_0 rows per wave)
       if (stream) return a.D <= 4 * kNT2 ? launch_gamma2<1, true>(a, r2, lds2, grid, st) : launch_gamma2<2, true>(a, r2, lds2, grid, st);
       return a.D <= 4 * kNT2 ? launch_gamma2<1, false>(a, r2, lds2, grid, st) : launch_gamma2<2, false>(a, r2, lds2, grid, st);
     }
-    const int r = a.sg ? PLAN_RESIDENT_0 : pick_r(a, (hint >> 10) & 511, 2 * a.Hp);
+    const int r = a.sg ? PLAN_RESIDENT_0 : pick_r(a, decode_hint(hint).occ_rows, 2 * a.Hp);
     if (stream) {
       if constexpr (VEC == 4 && XCH > 0) return launch_gamma_stream<XCH>(a, r, lds_gam, grid, st);
       else return hipErrorInvalidValue;                 // (den_stream_eligible said no)
@@ -1219,30 +1219,30 @@ hipError_t launch_den_gate(const int32_t* progress, int target, int32_t* bad, hi
   return hipGetLastError();
 }
 
-bool den_stream_eligible(const DenArgs& a, int gamma_max_groups, int resident_slot_rows) {
-  return (a.lazy || a.pair) && gamma_stream_shape_ok(a, resident_slot_rows, gamma_max_groups);
+bool den_stream_eligible(const DenArgs& a, int gamma_max_groups, int hint) {
+  return (a.lazy || a.pair) && gamma_stream_shape_ok(a, hint, gamma_max_groups);
 }
-const char* den_recursion_kernel_name(const DenArgs& a, int resident_slot_rows) {
+const char* den_recursion_kernel_name(const DenArgs& a, int hint) {
   if (a.pair) return "den_recursion_pair_kernel";
-  if (a.lazy && a.shape == kShapeDma && !a.sg && den_q_eligible(a, resident_slot_rows)) return "den_recursion_lazy_kernel<dma; one-word states>";
+  if (a.lazy && a.shape == kShapeDma && !a.sg && den_q_eligible(a, hint)) return "den_recursion_lazy_kernel<dma; one-word states>";
   if (a.lazy) return a.shape == kShapeSmall ? "den_recursion_lazy_kernel<small>" : (a.shape == kShapeDma ? (a.sg ? (a.xf ? "den_recursion_lazy_kernel<dma; one gather per arc; crossing>" : "den_recursion_lazy_kernel<dma; one gather per arc>") : "den_recursion_lazy_kernel<dma>") : "den_recursion_lazy_kernel");
   return "den_recursion_kernel";
 }
-const char* den_occupancy_kernel_name(const DenArgs& a, int gamma_max_groups, int resident_slot_rows) {
-  return gamma2_eligible(a, (resident_slot_rows >> 20) & 127, gamma_max_groups) ? "den_gamma2_kernel" : "den_gamma_kernel";
+const char* den_occupancy_kernel_name(const DenArgs& a, int gamma_max_groups, int hint) {
+  return gamma2_eligible(a, decode_hint(hint).occ2_rows, gamma_max_groups) ? "den_gamma2_kernel" : "den_gamma_kernel";
 }
 int den_recursion_blocks(const DenArgs& a) { return a.pair ? 2 * ((a.B + 1) / 2) : 2 * a.B; }
 
-bool den_uses_gamma2(const DenArgs& a, int gamma_max_groups, int resident_slot_rows) {
-  return gamma2_eligible(a, (resident_slot_rows >> 20) & 127, gamma_max_groups);
+bool den_uses_gamma2(const DenArgs& a, int gamma_max_groups, int hint) {
+  return gamma2_eligible(a, decode_hint(hint).occ2_rows, gamma_max_groups);
 }
 // 2-byte network output and gradient (DenArgs::x_half): the two-frame kernel, or the one-frame kernel in its float4-chunk forms
-bool den_occupancy_half_ok(const DenArgs& a, int gamma_max_groups, int resident_slot_rows) {
-  if (gamma2_eligible(a, (resident_slot_rows >> 20) & 127, gamma_max_groups)) return true;
-  return a.D % 4 == 0 && a.D <= 4 * 4 * kNT && pick_r(a, (resident_slot_rows >> 10) & 511, 2 * a.Hp) > 0;
+bool den_occupancy_half_ok(const DenArgs& a, int gamma_max_groups, int hint) {
+  if (gamma2_eligible(a, decode_hint(hint).occ2_rows, gamma_max_groups)) return true;
+  return a.D % 4 == 0 && a.D <= 4 * 4 * kNT && pick_r(a, decode_hint(hint).occ_rows, 2 * a.Hp) > 0;
 }
 
-hipError_t launch_den(const DenArgs& a, int gamma_max_groups, int resident_slot_rows, hipStream_t st,
+hipError_t launch_den(const DenArgs& a, int gamma_max_groups, int hint, hipStream_t st,
                       const char** why) {
   const int Dp = (a.D + 3) & ~3;
   const bool db = a.D % 4 == 0 && a.D <= 4 * kNT;        // the <4, 1> instantiation: two 16 KiB nnet-output buffers
@@ -1258,7 +1258,7 @@ hipError_t launch_den(const DenArgs& a, int gamma_max_groups, int resident_slot_
     return hipErrorInvalidValue;
   }
   const int gx = den_compact_grid_x(a);
-  const int D = a.D, r = resident_slot_rows;
+  const int D = a.D, r = hint;
   if (D % 4 == 0) {
     if (D <= 4 * 1 * kNT) return launch_r<4, 1>(a, r, lds_rec, lds_gam, gx, st, gamma_max_groups);
     if (D <= 4 * 2 * kNT) return launch_r<4, 2>(a, r, lds_rec, lds_gam, gx, st, gamma_max_groups);

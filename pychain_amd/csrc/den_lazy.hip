@@ -23,20 +23,18 @@ namespace {
 // per wave (bit 30 of the plan hint), the whole sequence in one launch.
 // (`dma`: rows by LDS-direct loads, which take any row length; rows through registers are float4 loads: D % 4 == 0)
 inline bool lazy_shape_ok(const DenArgs& a, int hint, bool dma = false) {
-  const int rows = hint & 1023;
-  return ((hint >> 30) & 1) && (dma || a.D % 4 == 0) && a.D <= (int)LzNarrow::kMaxPdfs && a.Hp <= (int)LzNarrow::kMaxStates && rows > 0 &&
+  const int rows = decode_hint(hint).rows;
+  return decode_hint(hint).four_groups && (dma || a.D % 4 == 0) && a.D <= (int)LzNarrow::kMaxPdfs && a.Hp <= (int)LzNarrow::kMaxStates && rows > 0 &&
          rows <= kMaxResident && PLAN_REC_WAVES == 16 && a.plan_stride >= 0;
 }
 // (launch hint bit 28: the plan has beta positions that take no constant - the kernels' NC form, den_lazy.inc.h)
-inline bool hint_no_const(int hint) { return hint >= 0 && ((hint >> 28) & 1); }   // (negative: PYCHAIN_HIP_HINT_GENERAL)
 // (launch hint bit 27: a "pdf by state" plan - the one-gather form of the recursions, den_lazy.inc.h: SG.  Taken where the form
 // is instantiated: the 16-wave map of C3 with LDS-direct fp32 rows the kernel clamps / exp's itself, loops of up to 32 rows, no
 // beta position without the constant; everything else runs such a plan like any other.)
-inline bool hint_pdf_by_state(int hint) { return hint >= 0 && ((hint >> 27) & 1); }
 inline bool sg_shape_ok(const DenArgs& a, int hint) {
   // (at most 32 slot-rows per wave: with two registers per arc the 40-row loop does not fit 128 registers - it compiled to 300
   // reloads from scratch per frame; such a plan runs the ordinary kernels)
-  return hint_pdf_by_state(hint) && (hint & 1023) <= 32 && !hint_no_const(hint) && a.knobs.den_sg != 0 && !a.input_is_exp && !a.x_half && !a.use_ex &&
+  return decode_hint(hint).pdf_by_state && decode_hint(hint).rows <= 32 && !decode_hint(hint).no_const && a.knobs.den_sg != 0 && !a.input_is_exp && !a.x_half && !a.use_ex &&
          a.plan_stride == 0 && a.D <= (int)LzNarrow::kMaxPdfs;
 }
 template <int R, typename M, bool TS>
@@ -46,7 +44,7 @@ hipError_t launch_lz_sg(const DenArgs& a, const dim3 grid, hipStream_t st) {
 // ... with the crossing (DenArgs::xf; LzCross: state vectors of up to 3072 positions)
 inline bool xf_shape_ok(const DenArgs& a, int hint) {
   // (at most 32 slot-rows per wave: the 40-row form of this kernel spills thirty registers inside its loop)
-  return sg_shape_ok(a, hint) && (hint & 1023) <= 32 && a.knobs.den_cross != 0 && !a.fused && a.Hp <= (int)LzCross::kMaxStates && a.D % 4 == 0 &&
+  return sg_shape_ok(a, hint) && decode_hint(hint).rows <= 32 && a.knobs.den_cross != 0 && !a.fused && a.Hp <= (int)LzCross::kMaxStates && a.D % 4 == 0 &&
          a.D <= (int)LzCross::kMaxPdfs && a.T >= 4 * kCrossBand + 8;
 }
 template <int R, bool TS>
@@ -56,10 +54,9 @@ hipError_t launch_lz_xf(const DenArgs& a, const dim3 grid, hipStream_t st) {
 // (launch hint bit 19: one position per state on both sides, every leaky probability positive - the one-word state vectors of
 // den_lazy.inc.h: MAP::kQ.  Instantiated for the 32-row loop of the 16-wave map with LDS-direct fp32 rows, uncut sequences; coef >= 1e-8
 // keeps 1 / (coef leaky) <= 1e20.  Option den_q, off by default: measured, it does not pay - DESIGN.md 3.16.)
-inline bool hint_one_word(int hint) { return hint >= 0 && ((hint >> 19) & 1); }
 inline bool q_shape_ok(const DenArgs& a, int hint) {
-  const int rows = hint & 1023;
-  return hint_one_word(hint) && !hint_no_const(hint) && rows > 16 && rows <= 32 && a.knobs.den_q != 0 && a.coef >= 1e-8f && a.coef <= 1.f &&
+  const int rows = decode_hint(hint).rows;
+  return decode_hint(hint).one_word && !decode_hint(hint).no_const && rows > 16 && rows <= 32 && a.knobs.den_q != 0 && a.coef >= 1e-8f && a.coef <= 1.f &&
          a.tseg <= 1 && !a.x_half;
 }
 template <int R, typename M, int XM, bool TS>
@@ -69,8 +66,8 @@ hipError_t launch_lz(const DenArgs& a, const dim3 grid, hipStream_t st, bool nc)
 }
 hipError_t launch_lazy(const DenArgs& a, int hint, hipStream_t st) {
   const dim3 grid(2 * a.B);
-  const int rows = hint & 1023;
-  const bool nc = hint_no_const(hint);
+  const int rows = decode_hint(hint).rows;
+  const bool nc = decode_hint(hint).no_const;
   if (rows <= 16) return launch_lz<16, LzNarrow, kLzRowsF32, false>(a, grid, st, nc);
   if (rows <= 32) return launch_lz<32, LzNarrow, kLzRowsF32, false>(a, grid, st, nc);
   if (rows <= PLAN_RESIDENT_FIT) return launch_lz<PLAN_RESIDENT_FIT, LzNarrow, kLzRowsF32, false>(a, grid, st, nc);
@@ -78,8 +75,8 @@ hipError_t launch_lazy(const DenArgs& a, int hint, hipStream_t st) {
 }
 // the 16-wave shape with LDS-direct nnet-output rows (LzDma): D <= 9216, Hp <= 3072
 inline bool dma_shape_ok(const DenArgs& a, int hint) {
-  const int rows = hint & 1023;
-  return ((hint >> 30) & 1) && a.D <= (int)LzDma::kMaxPdfs && a.Hp <= (int)LzDma::kMaxStates && rows > 0 &&
+  const int rows = decode_hint(hint).rows;
+  return decode_hint(hint).four_groups && a.D <= (int)LzDma::kMaxPdfs && a.Hp <= (int)LzDma::kMaxStates && rows > 0 &&
          rows <= kMaxResident && PLAN_REC_WAVES == 16 && a.plan_stride >= 0;
 }
 template <typename M, int XM, bool TS = false>
@@ -112,14 +109,14 @@ hipError_t launch_dma(const DenArgs& a, int hint, hipStream_t st) {
     if (a.use_ex) return launch_lz<32, M, kLzRowsPre, false>(a, grid, st, false);
     return launch_lz<32, M, kLzRowsF32, false>(a, grid, st, false);
   }
-  if (lazy_shape_ok(a, hint, true)) return launch_dma_x<LzNarrowDma>(a, hint & 1023, st, hint_no_const(hint));
-  return launch_dma_x<LzDma>(a, hint & 1023, st, hint_no_const(hint));
+  if (lazy_shape_ok(a, hint, true)) return launch_dma_x<LzNarrowDma>(a, decode_hint(hint).rows, st, decode_hint(hint).no_const);
+  return launch_dma_x<LzDma>(a, decode_hint(hint).rows, st, decode_hint(hint).no_const);
 }
 // Four-wave workgroups over the plan's four-wave dealing (hint bit 29: every plan of the call holds alpha4 / beta4, and the
 // hint's row count is that dealing's): small graphs, LDS-direct rows.
 inline bool small_shape_ok(const DenArgs& a, int hint) {
-  const int rows = hint & 1023;
-  return ((hint >> 29) & 1) && a.D <= (int)LzSmall::kMaxPdfs && a.Hp <= (int)LzSmall::kMaxStates && rows > 0 && rows <= kMaxResident &&
+  const int rows = decode_hint(hint).rows;
+  return decode_hint(hint).four_waves && a.D <= (int)LzSmall::kMaxPdfs && a.Hp <= (int)LzSmall::kMaxStates && rows > 0 && rows <= kMaxResident &&
          a.plan_stride >= 0;
 }
 // A frame of a small graph is the arc loop's chunks, one dependent LDS round trip each with one wave per SIMD, whatever the
@@ -127,9 +124,9 @@ inline bool small_shape_ok(const DenArgs& a, int hint) {
 template <int PRE>
 hipError_t launch_small_p(const DenArgs& a, int hint, hipStream_t st) {
   const dim3 grid(2 * a.B);
-  const int rows = hint & 1023;
+  const int rows = decode_hint(hint).rows;
   typedef LzSmall M;
-  const bool nc = hint_no_const(hint);
+  const bool nc = decode_hint(hint).no_const;
   if (rows <= 16) return launch_lz<16, M, PRE, false>(a, grid, st, nc);
   if (rows <= 24) return launch_lz<24, M, PRE, false>(a, grid, st, nc);
   if (rows <= 32) return launch_lz<32, M, PRE, false>(a, grid, st, nc);
@@ -143,13 +140,13 @@ hipError_t launch_small(const DenArgs& a, int hint, hipStream_t st) {
 // Two sequences per workgroup (den_pair.inc.h): one plan for all sequences, nnet-output rows and state vectors
 // within its fixed LDS map, every arc of a plan wave in registers, the whole sequence in one launch.
 inline bool pair_shape_ok(const DenArgs& a, int hint) {
-  const int rows = hint & 1023;
+  const int rows = decode_hint(hint).rows;
   return a.plan_stride == 0 && a.D % 4 == 0 && a.D <= 4096 && a.Hp <= 4096 && rows > 0 && rows <= kMaxResident &&
-         PLAN_REC_WAVES == 16 && a.B >= 2 && !hint_no_const(hint);   // (its normalise pass gives every position the constant c(t))
+         PLAN_REC_WAVES == 16 && a.B >= 2 && !decode_hint(hint).no_const;   // (its normalise pass gives every position the constant c(t))
 }
 hipError_t launch_pair(const DenArgs& a, int hint, hipStream_t st) {
   const dim3 grid(2 * ((a.B + 1) / 2));
-  const int rows = hint & 1023;
+  const int rows = decode_hint(hint).rows;
   if (a.x_half) {                                        // 2-byte nnet-output rows (DenArgs::x_half)
     if (rows <= 16) return launch_one(den_recursion_pair_kernel<16, true>, a, grid, kPrBytes, st, kPrNT);
     if (rows <= 32) return launch_one(den_recursion_pair_kernel<32, true>, a, grid, kPrBytes, st, kPrNT);
@@ -162,14 +159,14 @@ hipError_t launch_pair(const DenArgs& a, int hint, hipStream_t st) {
 
 }  // namespace
 
-bool den_lazy_eligible(const DenArgs& a, int resident_slot_rows) { return lazy_shape_ok(a, resident_slot_rows); }
-bool den_small_eligible(const DenArgs& a, int resident_slot_rows) { return small_shape_ok(a, resident_slot_rows); }
-bool den_dma_eligible(const DenArgs& a, int resident_slot_rows) { return lazy_shape_ok(a, resident_slot_rows, true) || dma_shape_ok(a, resident_slot_rows); }
-bool den_pair_eligible(const DenArgs& a, int resident_slot_rows) { return pair_shape_ok(a, resident_slot_rows); }
-bool den_sg_eligible(const DenArgs& a, int resident_slot_rows) { return lazy_shape_ok(a, resident_slot_rows, true) && sg_shape_ok(a, resident_slot_rows); }
-bool den_xf_eligible(const DenArgs& a, int resident_slot_rows) { return lazy_shape_ok(a, resident_slot_rows, true) && xf_shape_ok(a, resident_slot_rows); }
-bool den_q_eligible(const DenArgs& a, int resident_slot_rows) {
-  return lazy_shape_ok(a, resident_slot_rows, true) && !sg_shape_ok(a, resident_slot_rows) && q_shape_ok(a, resident_slot_rows);
+bool den_lazy_eligible(const DenArgs& a, int hint) { return lazy_shape_ok(a, hint); }
+bool den_small_eligible(const DenArgs& a, int hint) { return small_shape_ok(a, hint); }
+bool den_dma_eligible(const DenArgs& a, int hint) { return lazy_shape_ok(a, hint, true) || dma_shape_ok(a, hint); }
+bool den_pair_eligible(const DenArgs& a, int hint) { return pair_shape_ok(a, hint); }
+bool den_sg_eligible(const DenArgs& a, int hint) { return lazy_shape_ok(a, hint, true) && sg_shape_ok(a, hint); }
+bool den_xf_eligible(const DenArgs& a, int hint) { return lazy_shape_ok(a, hint, true) && xf_shape_ok(a, hint); }
+bool den_q_eligible(const DenArgs& a, int hint) {
+  return lazy_shape_ok(a, hint, true) && !sg_shape_ok(a, hint) && q_shape_ok(a, hint);
 }
 int den_xf_band() { return kCrossBand; }
 

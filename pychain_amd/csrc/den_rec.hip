@@ -251,7 +251,7 @@ static hipError_t launch_rec_vx(const DenArgs& a, int hint, size_t lds_rec, hipS
   const dim3 grid(2 * a.B);
   // <4, 1> (D <= 4096, D % 4 == 0) double-buffers the nnet-output row: gathered operands end at 32 KiB + 4 Hp
   constexpr bool DB = VEC == 4 && XCH == 1;
-  switch (pick_r(a, hint & 1023, DB ? 2 * (kXOff / 4) + a.Hp : a.Hp + ((a.D + 3) & ~3))) {
+  switch (pick_r(a, decode_hint(hint).rows, DB ? 2 * (kXOff / 4) + a.Hp : a.Hp + ((a.D + 3) & ~3))) {
     case 0: return launch_one(den_recursion_kernel<VEC, XCH, 0, DB>, a, grid, lds_rec, st);
     case 16: return launch_one(den_recursion_kernel<VEC, XCH, 16, DB>, a, grid, lds_rec, st);
     case 32: return launch_one(den_recursion_kernel<VEC, XCH, 32, DB>, a, grid, lds_rec, st);

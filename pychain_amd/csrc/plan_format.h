@@ -200,6 +200,31 @@ inline bool plan_header_in_bounds(const PlanHeader& hd) {
   }
   return hd.off_row_pdf >= 0 && (size_t)hd.off_row_pdf + (size_t)hd.gamma.ngroups * 64 * 4 <= n;
 }
+// ---- the launch hint: info[4] of pychain_hip_den_plan_info, the int the ABI calls `resident_slot_rows` - what the launch code needs
+// to know of a plan without reading it (the plan lives on the device).  Negative: a plan in the general format
+// (PYCHAIN_HIP_HINT_GENERAL = bit 31 alone: every field 0).  Per-field max over the plans of a call with per-sequence plans.
+struct LaunchHint {
+  int rows = 0;                // bits 0-9: most slot-rows a wave of the alpha / beta tiles owns (four_waves: of THAT dealing)
+  int occ_rows = 0;            // bits 10-18: ... of the gamma tile (one-frame occupancy kernel; beyond the resident row counts: "stream the tail")
+  int occ2_rows = 0;           // bits 20-26: ... of the gamma2 tile (two-frame occupancy kernel: at most 64 rows per wave; 0: not in the plan)
+  bool one_word = false;       // bit 19: one position per state on both sides, every leaky probability positive (den_lazy.inc.h: MAP::kQ)
+  bool pdf_by_state = false;   // bit 27: PLAN_FLAG_PDF_BY_STATE (den_lazy.inc.h: SG)
+  bool no_const = false;       // bit 28: the plan has beta positions that take no constant (the kernels' NC form)
+  bool four_waves = false;     // bit 29: every plan of the call holds alpha4 / beta4 (den_lazy.inc.h: LzSmall)
+  bool four_groups = false;    // bit 30: every recursion wave owns at most 4 groups
+};
+inline int encode_hint(const LaunchHint& h) {                    // (row counts saturate at their widths)
+  const int rows = h.rows > 1023 ? 1023 : h.rows, occ = h.occ_rows > 511 ? 511 : h.occ_rows, occ2 = h.occ2_rows > 127 ? 127 : h.occ2_rows;
+  return rows | (occ << 10) | ((int)h.one_word << 19) | (occ2 << 20) | ((int)h.pdf_by_state << 27) | ((int)h.no_const << 28) |
+         ((int)h.four_waves << 29) | ((int)h.four_groups << 30);
+}
+inline LaunchHint decode_hint(int hint) {
+  LaunchHint h;
+  h.rows = hint & 1023; h.occ_rows = (hint >> 10) & 511; h.occ2_rows = (hint >> 20) & 127;
+  h.one_word = hint >= 0 && ((hint >> 19) & 1); h.pdf_by_state = hint >= 0 && ((hint >> 27) & 1); h.no_const = hint >= 0 && ((hint >> 28) & 1);
+  h.four_waves = (hint >> 29) & 1; h.four_groups = (hint >> 30) & 1;
+  return h;
+}
 }  // namespace pychain_hip
 #endif
 

@@ -371,3 +371,27 @@ def test_policy_queries_answer_without_a_device():
     assert ts(32, 1500, 0) == 4 and ts(64, 1500, 0) == 2 and ts(128, 1500, 0) == 1 and ts(8, 300, 0) == 1
     with _lib.option("den_tseg", "0"):
         assert ts(16, 1500, 1) == 1
+
+
+def test_den_decisions_match_the_recorded_grid():
+    """Which kernels, how many time segments / slices, whether the row buffer and 2-byte rows are taken and how large the workspace
+    is, over a grid of launch hints, shapes and options on both sides of every limit (tests/golden/make_den_decisions.py): every
+    answer of the query entry points is the recorded one.  A change of policy regenerates the file on purpose; a refactor does not."""
+    import importlib.util
+    import json
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_den_decisions", os.path.join(golden, "make_den_decisions.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "den_decisions.json")) as f:
+        recorded = json.load(f)
+    assert recorded["columns"] == gen.COLUMNS and recorded["names"] == gen.NAMES
+    got, grid = gen.compute(_lib), gen.grid()
+    want = [recorded["answers"][i] for i in recorded["rows"]]
+    assert len(got["rows"]) == len(want) == len(grid) >= 3000
+    wrong = [(cfg, w, g) for cfg, w, g in zip(grid, want, got["rows"]) if w != g]
+    for cfg, w, g in wrong[:20]:
+        print(dict(zip(gen.CONFIG, cfg)), "recorded", dict(zip(gen.COLUMNS, w)), "got", {c: y for c, x, y in zip(gen.COLUMNS, w, g) if x != y})
+    assert not wrong, "%d of %d rows differ" % (len(wrong), len(want))
+    sizes = {k: list(v) for k, v in got["workspace"].items()}
+    assert sizes == recorded["workspace"], {k: (recorded["workspace"].get(k), v) for k, v in sizes.items() if recorded["workspace"].get(k) != v}
