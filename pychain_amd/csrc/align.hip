@@ -422,7 +422,9 @@ int align_walk_bytes(int H, int K, int D) {
   const size_t room = 160 * 1024 > align_fixed_lds_bytes(K) ? 160 * 1024 - align_fixed_lds_bytes(K) : 0;
   size_t w = kAlWalkCap < room ? kAlWalkCap : room;
   if (w < fwd) w = fwd;
-  return (int)((w + 15) & ~(size_t)15);
+  // (rounded DOWN: `room` is 8 mod 16 for an odd K, and rounding it up took 8 bytes more than the CU has - a graph of 4000
+  // states and 8399 arcs was refused; fwd is a multiple of 16, so the forward's buffers still fit)
+  return (int)(w & ~(size_t)15);
 }
 size_t align_lds_bytes(int H, int K, int D) { return (size_t)align_walk_bytes(H, K, D) + align_fixed_lds_bytes(K); }
 
@@ -448,7 +450,6 @@ hipError_t launch_align(const AlignArgs& a, hipStream_t st, const char** why) {
   if (D % 4 == 0) {
     if (D <= 4 * 4 * kAlLd) return launch_align_t<4, 4, kAlLd>(a, lds, st);
     if (D <= 4 * 8 * kAlLd) return launch_align_t<4, 8, kAlLd>(a, lds, st);
-    if (D <= 4 * 2 * kAlNT) return launch_align_t<4, 2>(a, lds, st);
     if (D <= 4 * 8 * kAlNT) return launch_align_t<4, 8>(a, lds, st);
   } else if (D <= 8 * kAlNT) {
     return launch_align_t<1, 8>(a, lds, st);

@@ -645,7 +645,6 @@ hipError_t launch_num_fb(const NumArgs& a, hipStream_t st, const char** why) {
   if (D % 4 == 0) {
     if (D <= 4 * 4 * kFbLd) return launch_fb<4, 4, kFbLd>(a, lds, st);       // (row-staging waves: 0.95 ms against 1.46 ms without them at C3)
     if (D <= 4 * 8 * kFbLd) return launch_fb<4, 8, kFbLd>(a, lds, st);
-    if (D <= 4 * 2 * kFbNT) return launch_fb<4, 2>(a, lds, st);
     if (D <= 4 * 8 * kFbNT) return launch_fb<4, 8>(a, lds, st);
   } else if (D <= 8 * kFbNT) {
     return launch_fb<1, 8>(a, lds, st);

@@ -1,5 +1,5 @@
-"""viterbi_align on CPU tensors (the host twin, csrc/cpu.cpp: pychain_hip_cpu_align) against a plain numpy Viterbi written here
-in fp64 with the association and tie rules of include/pychain_hip.h, against brute force on tiny graphs, hand-predicted ties, a
+"""viterbi_align on CPU tensors (the host twin, csrc/cpu.cpp: pychain_hip_cpu_align) against a plain numpy Viterbi (tests/num_reference.py:
+np_viterbi) in fp64 with the association and tie rules of include/pychain_hip.h, against brute force on tiny graphs, hand-predicted ties, a
 planted path, the numerator objective (log-sum >= max) and its error contract.  No GPU."""
 import itertools
 
@@ -8,68 +8,13 @@ import pytest
 import torch
 
 from helpers import _rand_num_fst, long_case
+from num_reference import np_viterbi
 from pychain_amd import Alignment, ChainGraph, ChainGraphBatch, native, viterbi_align, synthetic as syn
 from pychain_amd.simplefst import StdVectorFst
 
 
-def _graph_rows(graphs, b):
-    g = graphs.shared_graph if graphs.shared_graph is not None else None
-    pick = (lambda n: getattr(g, n)) if g is not None else (lambda n: getattr(graphs, n)[b])
-    return dict(bt=pick("backward_transitions").numpy().astype(np.int64), bi=pick("backward_transition_indices").numpy().astype(np.int64),
-                lp=pick("backward_transition_probs").numpy().astype(np.float32).astype(np.float64),
-                init=pick("initial_probs").numpy().astype(np.float32).astype(np.float64),
-                fin=pick("final_probs").numpy().astype(np.float32).astype(np.float64))
-
-
-def np_viterbi(graphs, x, lengths):
-    """(score[B] f64, states[B,T+1], pdfs[B,T]): s(t+1,h) = max_k s(t,src_k) + (lp_k + x(t,pdf_k)), first k wins ties;
-    score = max_h s(L,h) + final(h), lowest h wins ties; NaN if an emitted column is NaN; rows -1 where there is no path."""
-    x = x.float().numpy()
-    B, T, D = x.shape
-    xc = np.clip(x, np.float32(-30), np.float32(30))             # (keeps a NaN, as torch.clamp does)
-    score = np.zeros(B)
-    states = np.full((B, T + 1), -1, dtype=np.int32)
-    pdfs = np.full((B, T), -1, dtype=np.int64)
-    for b in range(B):
-        r = _graph_rows(graphs, b)
-        L, H = int(lengths[b]), r["bi"].shape[0]
-        lo, hi = r["bi"][:, 0], r["bi"][:, 1]
-        has = np.nonzero(hi > lo)[0]
-        ks = np.concatenate([np.arange(lo[h], hi[h]) for h in has]) if has.size else np.zeros(0, np.int64)
-        starts = np.concatenate([[0], np.cumsum((hi - lo)[has])[:-1]]).astype(np.int64)
-        seg = np.repeat(np.arange(has.size), (hi - lo)[has])
-        src, pdf, lp = r["bt"][ks, 0], r["bt"][ks, 2], r["lp"][ks]
-        s = r["init"].copy()
-        bk = np.zeros((L, H), dtype=np.int64)
-        nan = False
-        for t in range(L):
-            te = s[src] + (lp + xc[b, t].astype(np.float64)[pdf])
-            nan = nan or bool(np.isnan(te).any())
-            new = np.full(H, -np.inf)
-            if has.size:
-                m = np.maximum.reduceat(te, starts)
-                pos = np.where(te == m[seg], np.arange(te.size), te.size)
-                first = np.minimum(np.minimum.reduceat(pos, starts), te.size - 1)
-                new[has] = m
-                bk[t, has] = ks[first]
-            s = new
-        e = s + r["fin"]
-        nan = nan or bool(np.isnan(e).any())
-        h = int(np.argmax(e)) if not nan else 0
-        score[b] = np.nan if nan else e[h]
-        if nan or not np.isfinite(score[b]):
-            continue
-        states[b, L] = h
-        for t in range(L - 1, -1, -1):
-            k = bk[t, h]
-            pdfs[b, t] = r["bt"][k, 2]
-            h = int(r["bt"][k, 0])
-            states[b, t] = h
-    return score, states, pdfs
-
-
 def _assert_identical(ali, ref):
-    score, states, pdfs = ref
+    score, states, pdfs = ref[:3]
     assert isinstance(ali, Alignment)
     assert ali.score.dtype == torch.float64 and ali.states.dtype == torch.int32 and ali.pdfs.dtype == torch.int64
     assert np.array_equal(ali.score.numpy(), score, equal_nan=True)

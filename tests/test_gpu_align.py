@@ -1,6 +1,8 @@
 """viterbi_align on the MI355X: the HIP kernels (csrc/align.hip) give the same bits as the host twin (csrc/cpu.cpp) - scores
 (compared as int64 words), states and pdfs - on the C3 numerator batch, on the long numerator cases, on a graph beyond the tile
-kernel, for 2-byte inputs (against the host twin on their exact fp32 up-cast), on a side stream and from run to run."""
+kernel, for 2-byte inputs (against the host twin on their exact fp32 up-cast), on a side stream and from run to run.  Every
+launch form of align_kernel, the block backtrace at every length, the largest tile graph, ties and the clamp / NaN row tails
+run against the float64 reference of the ABI in tests/test_gpu_align_forms.py."""
 import numpy as np
 import pytest
 import torch

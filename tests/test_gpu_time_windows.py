@@ -1,7 +1,9 @@
 """Alignment time windows on the MI355X (include/pychain_hip.h: pychain_hip_*_tw): the windowed numerator kernels against the host
 twin (csrc/cpu.cpp) on the C3 batch, a shared graph of 700 states, the fused loss and a graph on the general kernels; full
 windows bit-identical to none; the windowed fused loss against the windowed two-call path and across its schedules; 2-byte
-rows; infeasible windows and the num_compat refusal."""
+rows; infeasible windows and the num_compat refusal.  The windowed and the free numerator against a plain float64
+forward-backward - every launch form of num_fb_kernel, arbitrary and empty windows, an infeasible sequence among feasible
+ones - run in tests/test_gpu_num_forms.py."""
 import numpy as np
 import pytest
 import torch
