@@ -35,7 +35,7 @@ from pychain_amd.parallel import ShardedChainLoss  # noqa: E402
 
 
 class TDNN(nn.Module):
-    def __init__(self, feat_dim, hidden, num_pdfs, layers=4):
+    def __init__(self, feat_dim, hidden, num_pdfs, layers=4, xent_head=False):
         super().__init__()
         blocks, d = [], feat_dim
         for i in range(layers):
@@ -44,9 +44,16 @@ class TDNN(nn.Module):
             d = hidden
         self.net = nn.Sequential(*blocks)
         self.out = nn.Conv1d(hidden, num_pdfs, kernel_size=1)
+        # --xent-regularize: a second linear head on the same hidden layer, trained by cross-entropy against the numerator
+        # posteriors of the step (Kaldi's "output-xent")
+        self.out_xent = nn.Conv1d(hidden, num_pdfs, kernel_size=1) if xent_head else None
 
-    def forward(self, feats):                       # [B,T,F] -> [B,T,D]
-        return self.out(self.net(feats.transpose(1, 2))).transpose(1, 2).contiguous()
+    def forward(self, feats):                       # [B,T,F] -> [B,T,D]  (with the xent head: a pair of them)
+        h = self.net(feats.transpose(1, 2))
+        y = self.out(h).transpose(1, 2).contiguous()
+        if self.out_xent is None:
+            return y
+        return y, self.out_xent(h).transpose(1, 2).contiguous()
 
 
 def main():
@@ -67,6 +74,8 @@ def main():
                     help="ONE rank under a launcher (torch.distributed.run --nproc-per-node 1): initialise the backend, wrap the model in "
                          "DDP and run the loss's all-reduce although the world is one - RCCL beside the loss's side streams and "
                          "spin-wait kernels on a box with a single GPU")
+    ap.add_argument("--xent-regularize", type=float, default=0.0,
+                    help="c > 0: a second output head trained by cross-entropy against the numerator posteriors, loss = LF-MMI - c * xent")
     ap.add_argument("--loss-cls", default=None,
                     help="module:Class of a ChainLoss(den_graph, leaky, avg=False) stand-in for the per-rank loss")
     args = ap.parse_args()
@@ -94,12 +103,13 @@ def main():
         loss_cls = getattr(importlib.import_module(mod), attr)
 
     torch.manual_seed(0)
-    model = TDNN(args.feat_dim, args.hidden, args.pdfs).to(dev)
+    model = TDNN(args.feat_dim, args.hidden, args.pdfs, xent_head=args.xent_regularize > 0).to(dev)
     if use_dist:
         model = nn.parallel.DistributedDataParallel(model, device_ids=[dev.index] if args.device == "cuda" else None)
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr)
     den_graph = syn.make_den_graph(args.states, args.arcs, args.pdfs, seed=0)      # the shared "phone LM"
-    criterion = ShardedChainLoss(den_graph, leaky_coefficient=1e-5, avg=True, loss_cls=loss_cls, force_collective=use_dist and world == 1)
+    criterion = ShardedChainLoss(den_graph, leaky_coefficient=1e-5, avg=True, loss_cls=loss_cls, force_collective=use_dist and world == 1,
+                                 xent_regularize=args.xent_regularize)
 
     # a fixed synthetic training set per rank: features correlated with the numerator alignment
     gen = torch.Generator(device=dev).manual_seed(100 + rank)
@@ -109,7 +119,11 @@ def main():
     first = last = None
     for step in range(args.steps):
         opt.zero_grad(set_to_none=True)
-        loss = criterion(model(feats), lengths, num_graphs)
+        if args.xent_regularize > 0:
+            y, z = model(feats)
+            loss = criterion(y, lengths, num_graphs, xent_output=z)
+        else:
+            loss = criterion(model(feats), lengths, num_graphs)
         loss.backward()
         torch.nn.utils.clip_grad_norm_(model.parameters(), 5.0)
         opt.step()

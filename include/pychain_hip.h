@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 19
+#define PYCHAIN_HIP_ABI_VERSION 20
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -434,6 +434,90 @@ int pychain_hip_cpu_num_forward_backward_tw(
     const float* nnet_output, const int64_t* seq_lengths,
     int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows);
+
+/* ------------------------------------------------------------------------
+ * Numerator posteriors as cross-entropy targets (ABI 20): the "xent regularisation" of chain training.  A second output of the
+ * network, z [B,T,D] (raw, NOT clamped; its own dtype), is trained by cross-entropy against the numerator occupancies of the same
+ * call.  With gamma_b(t,d) the numerator occupancy of the call (under its time windows, if any) and s_b(t) = sum_d gamma_b(t,d):
+ *   xent_objf[b]       = sum_{t < L_b} ( sum_d gamma_b(t,d) z(t,d)  -  s_b(t) logsumexp_d z(t,.) )
+ *   d xent / d z(b,t,d) = gamma_b(t,d) - s_b(t) softmax(z(t,.))_d        for t < L_b, exactly 0 for t >= L_b
+ * gamma is a constant target: nothing flows back to the chain output through it (Kaldi copies the numerator posteriors and does
+ * not differentiate them).  A sequence whose logP is not finite (no admissible path) has gamma = 0: objective 0, zero gradient
+ * rows.  The row of z is read once; maximum, sum and the row itself stay on chip in fp32 between the reduction and the store
+ * (exp and log in fp32); terms with gamma = 0 are left out of the dot product.  A NaN or an infinity in a live row of z makes that
+ * sequence's xent objective what torch.log_softmax would make it (NaN); the LF-MMI objectives, the LF-MMI gradient and bad_count do
+ * not see z at all.  Frame objectives are added up per sequence in fp64 in a fixed order: the same call gives the same bits.
+ *
+ * The *_xent entry points are the *_tw entry points of the same name with one argument more, last: a pointer to the struct below
+ * (host memory, read during the call only).  NULL = exactly the call without it: same launches, same bits.
+ *   z, z_dtype         dev [B,T,D] (the host twin: host, fp32 only), PYCHAIN_HIP_F32 / _BF16 / _F16; 2-byte rows are read as they are
+ *   xent_grad          dev [B,T,D] in z_dtype, or NULL (no store: z needs no gradient).  Every element is written ONCE:
+ *                      xent_grad = grad_scale [* *grad_scale_dev] [/ *loss_norm_dev] * (gamma - s softmax(z)), rounded at the store;
+ *                      rows t >= L_b are zeros.  A trainer passes grad_scale = -c * upstream [/ frames].
+ *   xent_objf_per_seq  dev float [B]
+ *   xent_totals        dev float [2] or NULL: [0] = loss_scale * S [/ *loss_norm_dev] with S = sum_b xent_objf[b] (fp64, fixed order;
+ *                      loss_scale, loss_norm_dev: those of a fused call, 1 and none elsewhere), [1] = S
+ *   loss_coef          fused calls with `totals`: totals[0] and totals[4] become the full loss, LF-MMI + loss_coef * xent_totals[0]
+ *                      (a trainer passes -c); totals[1..3], totals[5..7] keep their meaning and their bits
+ *   workspace          dev, pychain_hip_xent_workspace_bytes(B, T, num_states, num_transitions, num_pdfs) bytes, 16-byte aligned:
+ *                      the frame objectives (8 B T bytes) and, for numerator graphs on the general kernels - which leave no compact
+ *                      occupancy rows - a dense fp32 [B,T,D] posterior buffer (slow but complete, like every general path).  The
+ *                      workspaces of the call itself are as large as without xent.  (The host twin takes none.)
+ * pychain_hip_num_forward_backward_xent: `grad` may be NULL when xent is given (only the cross-entropy is wanted: the dense
+ * occupancy pass is left out).  The fused calls run the row kernel on the numerator's side stream, behind the compact occupancy
+ * launch and behind the event the denominator's occupancy launch waits for, and join it to `stream` before they return;
+ * pychain_hip_chain_loss_forward without `grad` then runs the compact occupancy launch in forward as well.  A call in slices
+ * (pychain_hip_chain_loss_slices) runs it slice by slice.  Option num_compat = 1 takes no xent: PYCHAIN_HIP_EUNSUPPORTED. */
+typedef struct pychain_hip_xent {
+  const void*  z;
+  int          z_dtype;
+  void*        xent_grad;
+  float        grad_scale;
+  const float* grad_scale_dev;
+  float        loss_coef;
+  float*       xent_objf_per_seq;
+  float*       xent_totals;
+  void*        workspace;
+  size_t       workspace_bytes;
+} pychain_hip_xent;
+size_t pychain_hip_xent_workspace_bytes(int B, int T, int num_states, int num_transitions, int num_pdfs);
+int pychain_hip_num_forward_backward_xent(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* time_windows, const pychain_hip_xent* xent);
+int pychain_hip_chain_loss_forward_xent(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_num_states, float leaky_hmm_coefficient,
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride, int num_num_states, int num_num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float* den_objf_per_seq, float* num_objf_per_seq, void* grad, float grad_scale, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_workspace, size_t den_workspace_bytes, void* num_workspace, size_t num_workspace_bytes, void* stream,
+    const int32_t* time_windows, const pychain_hip_xent* xent);
+int pychain_hip_chain_loss_forward_backward_xent(
+    const void* plans_dev, int64_t plan_stride_bytes, int resident_slot_rows, int den_num_states, float leaky_hmm_coefficient,
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride, int num_num_states, int num_num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs, float grad_scale,
+    float* den_objf_per_seq, float* num_objf_per_seq, void* grad, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_workspace, size_t den_workspace_bytes, void* num_workspace, size_t num_workspace_bytes, void* stream,
+    const int32_t* time_windows, const pychain_hip_xent* xent);
+/* the host twin: fp64 accumulation (occupancies, log-sum-exp, objective), host threads as the other twins */
+int pychain_hip_cpu_num_forward_backward_xent(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows,
+    const pychain_hip_xent* xent);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 19
+ABI_VERSION = 20
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -18,6 +18,14 @@ CPU_NO_CLAMP = 0x100     # (host twin of the numerator only: include/pychain_hip
 F32, BF16, F16 = 0, 1, 2        # include/pychain_hip.h: PYCHAIN_HIP_F32 / _BF16 / _F16
 
 _lib = None
+
+
+class Xent(ctypes.Structure):
+    """include/pychain_hip.h: pychain_hip_xent (the last argument of the *_xent entry points)."""
+    _fields_ = [("z", ctypes.c_void_p), ("z_dtype", ctypes.c_int), ("xent_grad", ctypes.c_void_p), ("grad_scale", ctypes.c_float),
+                ("grad_scale_dev", ctypes.c_void_p), ("loss_coef", ctypes.c_float), ("xent_objf_per_seq", ctypes.c_void_p),
+                ("xent_totals", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t)]
+
 
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
@@ -66,6 +74,17 @@ _SIGNATURES = {
                                           + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
                                           + [_vp, _sz, _vp, _sz, _vp, _vp]),
     "pychain_hip_cpu_num_forward_backward_tw": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    # (ABI 20: the same four with the numerator posteriors as cross-entropy targets, a pointer to a pychain_hip_xent more, last)
+    "pychain_hip_xent_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pychain_hip_num_forward_backward_xent": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f,
+                                                   _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
+    "pychain_hip_chain_loss_forward_backward_xent": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
+                                                     + [_vp, _i, _vp, _i, _i, _i, _f] + [_vp] * 4 + [_f, _vp, _vp]
+                                                     + [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "pychain_hip_chain_loss_forward_xent": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
+                                            + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
+                                            + [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
+    "pychain_hip_cpu_num_forward_backward_xent": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),

@@ -18,6 +18,7 @@
 #include "device_utils.h"
 #include "num_kernels.h"
 #include "plan_format.h"
+#include "xent.h"
 
 namespace pychain_hip {
 char* last_error_buffer() {
@@ -506,22 +507,100 @@ int fill_num_args(NumArgs& a, const int32_t* ft, const int32_t* fi, const float*
 }
 }  // namespace
 
+
+// ---- numerator posteriors as cross-entropy targets (include/pychain_hip.h: pychain_hip_xent; xent.hip) ------------------
+namespace {
+// a checked pychain_hip_xent with the pointers of the sequences ONE call (or one slice of a call) is given
+struct XentCall {
+  const char* z; int z_dtype; char* grad; float grad_scale; const float* grad_scale_dev; float* objf;
+  double* frame_objf;        // [B,T] frame objectives (workspace)
+  float* dense;              // [B,T,D] dense posteriors: numerator graphs on the general kernels only (workspace)
+  int32_t* scratch_bad;      // where an occupancy launch made for xent alone counts (the caller's bad count stays as it was)
+};
+struct XentCarve { size_t scratch, frames, dense, total; };
+XentCarve xent_carve(int B, int T, int H, int K, int D) {
+  XentCarve c;
+  c.scratch = 0;
+  c.frames = 256;
+  c.dense = c.frames + align256(xent_frame_bytes(B, T));
+  c.total = c.dense + (num_needs_general(H, K, D) ? align256(4 * (size_t)B * T * D) : 0) + 256;
+  return c;
+}
+int xent_check(const pychain_hip_xent* x, int B, int T, int H, int K, int D, const char* who, XentCall& out) {
+  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
+  if (!x->z || !x->xent_objf_per_seq || !x->workspace) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: null z, xent_objf_per_seq or workspace", who);
+  if (x->z_dtype < PYCHAIN_HIP_F32 || x->z_dtype > PYCHAIN_HIP_F16) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: unknown z_dtype %d", who, x->z_dtype);
+  if (((uintptr_t)x->z | (uintptr_t)x->xent_grad | (uintptr_t)x->workspace) & 15)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: xent: z, xent_grad and workspace must be 16-byte aligned", who);
+  if (call_knobs().num_compat)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: option num_compat (the reference's own arithmetic) takes no cross-entropy output", who);
+  const XentCarve c = xent_carve(B, T, H, K, D);
+  if (x->workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: xent workspace too small (%zu < %zu)", who, x->workspace_bytes, c.total);
+  char* ws = (char*)(((uintptr_t)x->workspace + 255) & ~(uintptr_t)255);
+  out.z = (const char*)x->z; out.z_dtype = x->z_dtype; out.grad = (char*)x->xent_grad;
+  out.grad_scale = x->grad_scale; out.grad_scale_dev = x->grad_scale_dev; out.objf = x->xent_objf_per_seq;
+  out.scratch_bad = (int32_t*)(ws + c.scratch);
+  out.frame_objf = (double*)(ws + c.frames);
+  out.dense = num_needs_general(H, K, D) ? (float*)(ws + c.dense) : nullptr;
+  return PYCHAIN_HIP_OK;
+}
+// the same call over the sequences from b0 on (a slice: the workspace is reused, slice after slice in stream order)
+XentCall xent_slice(const XentCall& x, int b0, int T, int D) {
+  XentCall s = x;
+  const size_t esz = x.z_dtype == PYCHAIN_HIP_F32 ? 4 : 2, off = (size_t)b0 * T * D * esz;
+  s.z = x.z + off;
+  if (x.grad) s.grad = x.grad + off;
+  s.objf = x.objf + b0;
+  return s;
+}
+// the row kernel over the occupancies `na`'s launches left: the compact rows of the tile path, or (general kernels) a dense
+// posterior buffer an occupancy launch of its own fills first - everything on `st`, behind the recursions
+hipError_t run_xent(const NumArgs& na, const XentCall& xc, const float* norm_dev, hipStream_t st, const char** why) {
+  XentArgs xa;
+  memset(&xa, 0, sizeof(xa));
+  xa.z = xc.z; xa.z_half = xc.z_dtype; xa.grad = xc.grad; xa.scale = xc.grad_scale; xa.scale_dev = xc.grad_scale_dev; xa.norm_dev = norm_dev;
+  xa.lengths = na.lengths; xa.logp = na.logp_ws; xa.frame_objf = xc.frame_objf; xa.objf = xc.objf;
+  xa.B = na.B; xa.T = na.T; xa.D = na.D;
+  if (na.general) {
+    NumArgs d = na;
+    d.grad = xc.dense; d.grad_mode = PYCHAIN_HIP_GRAD_LINEAR; d.grad_scale = 1.f; d.grad_scale_dev = nullptr; d.bad = xc.scratch_bad;
+    hipError_t e = launch_num_occ(d, false, st, why);
+    if (e != hipSuccess) return e;
+    xa.dense = xc.dense;
+  } else {
+    xa.rows = na.rows_ws; xa.upd = na.upd_ws; xa.ucount = na.ucount_ws; xa.K = na.K;
+  }
+  return launch_xent_rows(xa, st, why);
+}
+}  // namespace
+
+extern "C" size_t pychain_hip_xent_workspace_bytes(int B, int T, int H, int K, int D) {
+  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
+  return xent_carve(B, T, H, K, D).total;
+}
+
 extern "C" size_t pychain_hip_num_workspace_bytes(int B, int T, int H, int K, int D) {
   if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
   return num_carve(B, T, H, K, D, call_knobs().num_compat != 0).total;   // (the calling thread's options, as the call will read them)
 }
 
-extern "C" int pychain_hip_num_forward_backward_tw(
+extern "C" int pychain_hip_num_forward_backward_xent(
     const int32_t* ft, const int32_t* fi, const float* fp,
     const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
     int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows, const pychain_hip_xent* xent) {
   NumArgs a;
+  XentCall xc;
+  if (xent) {
+    const int xrc = xent_check(xent, B, T, H, K, D, "num_forward_backward", xc);
+    if (xrc != PYCHAIN_HIP_OK) return xrc;
+  }
+  const bool dense_grad = grad != nullptr || !xent;      // (with xent `grad` may be NULL: only the cross-entropy is wanted)
   int rc = fill_num_args(a, ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
-                         B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, workspace,
+                         B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, dense_grad ? (void*)grad : workspace, bad_count, workspace,
                          workspace_bytes, "num_forward_backward", time_windows);
   if (rc != PYCHAIN_HIP_OK) return rc;
   // (2-byte network outputs are READ as they are by the tile recursions; the gradient of this entry point stays fp32)
@@ -537,12 +616,37 @@ extern "C" int pychain_hip_num_forward_backward_tw(
   } else {
     e = launch_num_fb(a, st, &why);
     if (e == hipSuccess && a.corrupt_b >= 0) e = launch_num_corrupt(a, st);
-    if (e == hipSuccess) e = launch_num_occ(a, false, st, &why);
+    if (e == hipSuccess && dense_grad) e = launch_num_occ(a, false, st, &why);
+    if (e == hipSuccess && xent) {
+      // the compact rows of the tile path for the row kernel (their own checks count into a scratch word: bad_count is the
+      // call's without xent), then the rows and the sums
+      NumArgs c = a;
+      c.bad = xc.scratch_bad;
+      if (!a.general) {
+        e = launch_num_prep(c, st, &why);
+        if (e == hipSuccess) e = launch_num_occ(c, true, st, &why);
+      }
+      if (e == hipSuccess) e = run_xent(a, xc, nullptr, st, &why);
+      if (e == hipSuccess && xent->xent_totals) e = launch_xent_totals(xc.objf, B, 1.f, nullptr, 0.f, xent->xent_totals, nullptr, st);
+    }
   }
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "num_forward_backward: %s",
                 why ? why : hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_num_forward_backward_tw(
+    const int32_t* ft, const int32_t* fi, const float* fp,
+    const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
+  return pychain_hip_num_forward_backward_xent(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype,
+                                               seq_lengths, B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count,
+                                               workspace, workspace_bytes, stream, time_windows, nullptr);
 }
 
 extern "C" int pychain_hip_num_forward_backward(
@@ -643,7 +747,8 @@ int chain_loss_forward_one(
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* windows) {
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* windows,
+    const XentCall* xc) {
   const char* who = "chain_loss_forward";
   if (!bad_count) return fail(PYCHAIN_HIP_EINVAL, "%s: null bad_count", who);
   DenArgs da;
@@ -690,11 +795,28 @@ int chain_loss_forward_one(
   if (e == hipSuccess) e = hipStreamWaitEvent(side->stream, side->fork, 0);
   // (option num_compat: the numerator is ONE launch behind the denominator's occupancy launches - it accumulates into the
   // gradient they wrote - and in front of den_finish_kernel, which reads its log-probabilities)
-  if (e == hipSuccess && grad && !na.compat) e = launch_num_prep(na, side->stream, &why);
+  // (xent on the tile path reads the compact rows: a call without `grad` then produces them too - into the same workspace, its
+  // checks counted into a scratch word, so that bad_count is the call's without xent)
+  const bool xcompact = xc && !na.general;
+  if (e == hipSuccess && (grad || xcompact) && !na.compat) e = launch_num_prep(na, side->stream, &why);
   if (e == hipSuccess && !na.compat) e = launch_num_fb(na, side->stream, &why);
   if (e == hipSuccess && na.corrupt_b >= 0 && !na.compat) e = launch_num_corrupt(na, side->stream);
   if (e == hipSuccess && grad && !na.general && !na.compat) e = launch_num_occ(na, true, side->stream, &why);   // compact rows, off the critical path
+  else if (e == hipSuccess && xcompact) {
+    NumArgs nc = na;
+    nc.bad = xc->scratch_bad;
+    e = launch_num_occ(nc, true, side->stream, &why);
+  }
   if (e == hipSuccess) e = hipEventRecord(side->join, side->stream);
+  // the cross-entropy row kernel: on the side stream BEHIND the event the fold waits for - a memory-bound pass beside the
+  // denominator's recursions -, joined to the caller's stream by an event of its own at the end of the call
+  hipEvent_t xjoin = nullptr;
+  if (e == hipSuccess && xcompact) {
+    xjoin = xent_join_event(st);
+    if (!xjoin) return fail(PYCHAIN_HIP_ELAUNCH, "%s: cannot create the xent event", who);
+    e = run_xent(na, *xc, loss_norm_dev, side->stream, &why);
+    if (e == hipSuccess) e = hipEventRecord(xjoin, side->stream);
+  }
   da.phase_mask = da.knobs.den_phase_mask == 0 ? 0 : 3;     // (mask 0: only the numerator's launches - a measurement aid, outputs not meaningful)
   // (den_finish_kernel reads the numerator's objectives and its bad count for `totals`: the join precedes it)
   // (den_finish_kernel needs the numerator's objectives and bad count: early only where the occupancy launch waits for them)
@@ -708,6 +830,8 @@ int chain_loss_forward_one(
   if (e == hipSuccess && (da.phase_mask & 1) && !finished) e = launch_den_finish(da, st);     // (phase mask 0: the numerator alone - bench.py times it so)
   if (e == hipSuccess && grad && !fold && !na.compat)                               // grad -= grad_scale * gamma_num
     e = na.general ? launch_num_occ(na, false, st, &why) : launch_num_scatter(na, st, &why);
+  if (e == hipSuccess && xjoin) e = hipStreamWaitEvent(st, xjoin, 0);
+  if (e == hipSuccess && xc && na.general) e = run_xent(na, *xc, loss_norm_dev, st, &why);   // (dense posteriors: slow but complete)
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
@@ -790,23 +914,40 @@ extern "C" int pychain_hip_chain_loss_slices(int64_t plan_stride_bytes, int hint
   return chain_loss_slices(B, hint, plan_stride_bytes, true);
 }
 
-extern "C" int pychain_hip_chain_loss_forward_tw(
+extern "C" int pychain_hip_chain_loss_forward_xent(
     const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows,
+    const pychain_hip_xent* xent) {
+  XentCall xcall;
+  const XentCall* xc = nullptr;
+  if (xent) {
+    const int xrc = xent_check(xent, B, T, num_H, num_K, D, "chain_loss_forward", xcall);
+    if (xrc != PYCHAIN_HIP_OK) return xrc;
+    xc = &xcall;
+  }
+  // the sums of the xent objectives and the full loss into totals[0], totals[4]: one small launch behind the call's last kernel
+  auto xent_finish = [&]() -> int {
+    if (!xent || (!xent->xent_totals && !totals)) return PYCHAIN_HIP_OK;
+    const hipError_t xe = launch_xent_totals(xcall.objf, B, loss_scale, loss_norm_dev, xent->loss_coef, xent->xent_totals, totals, (hipStream_t)stream);
+    if (xe != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "chain_loss_forward: %s", hipGetErrorString(xe));
+    return PYCHAIN_HIP_OK;
+  };
   const int nsl = (B > 0 && T > 0 && D > 0 && den_ws && bad_count && den_objf && num_objf && seq_lengths && nnet_output && ft && fi && fp &&
                    bt && bi && bp && initial && final_ && den_ws_bytes > 8192)
                       ? chain_loss_slices(B, hint, plan_stride_bytes, grad != nullptr) : 1;
   note_forward_workspace(den_ws, nsl > 1);
-  if (nsl <= 1)
-    return chain_loss_forward_one(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
-                                  graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, den_objf, num_objf,
-                                  grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes,
-                                  stream, time_windows);
+  if (nsl <= 1) {
+    const int rc1 = chain_loss_forward_one(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
+                                           graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, den_objf, num_objf,
+                                           grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes,
+                                           stream, time_windows, xc);
+    return rc1 != PYCHAIN_HIP_OK ? rc1 : xent_finish();
+  }
   // the scratch lines: the last 4 KiB of the denominator's workspace (sized by the caller for all B sequences; a slice
   // needs about 1 / nsl of it)
   const size_t ws_bytes = (den_ws_bytes - 4096) & ~(size_t)255;
@@ -816,6 +957,7 @@ extern "C" int pychain_hip_chain_loss_forward_tw(
   // 2-byte rows of odd T x D included -, and the pair recursion takes its sequences two by two)
   const int per = ((B + nsl - 1) / nsl + 7) & ~7;
   int c = 0;
+  XentCall xslice;
   for (int b0 = 0; b0 < B; b0 += per, c++) {
     const int nb = std::min(per, B - b0);
     const size_t g = graph_batch_stride ? (size_t)b0 : 0;     // per-sequence numerator graphs: [G, K, 3] / [G, H, 2] / [G, K] / [G, H]
@@ -826,14 +968,29 @@ extern "C" int pychain_hip_chain_loss_forward_tw(
         (const char*)nnet_output + (size_t)b0 * T * D * esz, nnet_output_dtype, seq_lengths + b0, nb, T, D,
         den_objf + b0, num_objf + b0, (char*)grad + (size_t)b0 * T * D * esz, grad_scale, lines[c].bad,
         loss_scale, loss_norm_dev, lines[c].totals, den_ws, ws_bytes, num_ws, num_ws_bytes, stream,
-        time_windows ? time_windows + (size_t)b0 * num_H * 2 : nullptr);     // (one window row per sequence, shared graph or not)
+        time_windows ? time_windows + (size_t)b0 * num_H * 2 : nullptr,      // (one window row per sequence, shared graph or not)
+        xc ? &(xslice = xent_slice(xcall, b0, T, D)) : nullptr);
     if (rc != PYCHAIN_HIP_OK) return rc;
   }
   hipLaunchKernelGGL(chain_slices_combine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lines, c, den_objf, num_objf, seq_lengths,
                      B, T, loss_scale, loss_norm_dev, bad_count, totals);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "chain_loss_forward: %s", hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
+  return xent_finish();
+}
+
+extern "C" int pychain_hip_chain_loss_forward_tw(
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
+  return pychain_hip_chain_loss_forward_xent(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial,
+                                             final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D,
+                                             den_objf, num_objf, grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws,
+                                             den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows, nullptr);
 }
 
 extern "C" int pychain_hip_chain_loss_forward(
@@ -978,6 +1135,22 @@ extern "C" int pychain_hip_chain_loss_backward(
                                   bad_count, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, true);
 }
 
+extern "C" int pychain_hip_chain_loss_forward_backward_xent(
+    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D, float grad_scale,
+    float* den_objf, float* num_objf, void* grad, int32_t* bad_count,
+    float loss_scale, const float* loss_norm_dev, float* totals,
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows,
+    const pychain_hip_xent* xent) {
+  if (!grad) return fail(PYCHAIN_HIP_EINVAL, "chain_loss_forward_backward: null grad");
+  return pychain_hip_chain_loss_forward_xent(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt,
+                                             bi, bp, initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
+                                             seq_lengths, B, T, D, den_objf, num_objf, grad, grad_scale, bad_count, loss_scale,
+                                             loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows, xent);
+}
+
 extern "C" int pychain_hip_chain_loss_forward_backward_tw(
     const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
@@ -986,11 +1159,10 @@ extern "C" int pychain_hip_chain_loss_forward_backward_tw(
     float* den_objf, float* num_objf, void* grad, int32_t* bad_count,
     float loss_scale, const float* loss_norm_dev, float* totals,
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows) {
-  if (!grad) return fail(PYCHAIN_HIP_EINVAL, "chain_loss_forward_backward: null grad");
-  return pychain_hip_chain_loss_forward_tw(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt,
-                                           bi, bp, initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
-                                           seq_lengths, B, T, D, den_objf, num_objf, grad, grad_scale, bad_count, loss_scale,
-                                           loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows);
+  return pychain_hip_chain_loss_forward_backward_xent(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp,
+                                                      initial, final_, graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype,
+                                                      seq_lengths, B, T, D, grad_scale, den_objf, num_objf, grad, bad_count, loss_scale,
+                                                      loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, time_windows, nullptr);
 }
 
 extern "C" int pychain_hip_chain_loss_forward_backward(

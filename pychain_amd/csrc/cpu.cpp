@@ -272,6 +272,30 @@ int check_common(const char* who, const void* ft, const void* fi, const void* fp
     if (lengths[b] < 1 || lengths[b] > T) return fail(PYCHAIN_HIP_EINVAL, "%s: sequence lengths must be in [1, %d]", who, T);
   return PYCHAIN_HIP_OK;
 }
+// ---- the numerator posteriors as cross-entropy targets of z (include/pychain_hip.h: pychain_hip_xent; the device's xent.hip):
+// one sequence, fp64 throughout.  gamma [T, D]: the occupancies of the sequence (zero rows where it has no admissible path).
+double xent_one(const float* gamma, bool feasible, const float* z, int L, int T, int D, float scale, float* zgrad) {
+  double objf = 0.0;
+  if (zgrad) std::fill(zgrad, zgrad + (size_t)T * D, 0.f);
+  if (!feasible) return 0.0;
+  for (int t = 0; t < L; t++) {
+    const float* zr = z + (size_t)t * D;
+    const float* gr = gamma + (size_t)t * D;
+    double m = -std::numeric_limits<double>::infinity(), se = 0.0, s = 0.0, dot = 0.0;
+    for (int d = 0; d < D; d++) if ((double)zr[d] > m) m = (double)zr[d];          // (a NaN is passed by here and met by the sum)
+    for (int d = 0; d < D; d++) {
+      se += std::exp((double)zr[d] - m);
+      if (gr[d] != 0.f) { s += (double)gr[d]; dot += (double)gr[d] * (double)zr[d]; }
+    }
+    const double lse = m + std::log(se);
+    objf += dot - s * lse;
+    if (zgrad) {
+      float* o = zgrad + (size_t)t * D;
+      for (int d = 0; d < D; d++) o[d] = (float)((double)scale * ((double)gr[d] - s * std::exp((double)zr[d] - lse)));
+    }
+  }
+  return objf;
+}
 }  // namespace
 }  // namespace pychain_hip
 
@@ -359,5 +383,39 @@ extern "C" int pychain_hip_cpu_align(
     if (!ok) bad++;
   });
   *bad_count = bad.load();
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_num_forward_backward_xent(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
+    float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows,
+    const pychain_hip_xent* xent) {
+  const char* who = "cpu_num_forward_backward";
+  if (xent && (!xent->z || !xent->xent_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: null z or xent_objf_per_seq", who);
+  if (xent && xent->z_dtype != PYCHAIN_HIP_F32) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: the host twin takes fp32 z", who);
+  const int rc = pychain_hip_cpu_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, seq_lengths,
+                                                         B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, num_threads,
+                                                         time_windows);
+  if (rc != PYCHAIN_HIP_OK || !xent) return rc;
+  // gamma: the occupancies once more, per sequence, as a linear fp32 row buffer of the thread's own; then the rows of z
+  const float sc = xent->grad_scale * (xent->grad_scale_dev ? *xent->grad_scale_dev : 1.f);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const size_t g = (size_t)b * graph_batch_stride;
+    const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
+    std::vector<float> gamma((size_t)T * D);
+    float logp = 0.f;
+    num_one(fwd, bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
+            PYCHAIN_HIP_GRAD_LINEAR | (grad_mode & PYCHAIN_HIP_CPU_NO_CLAMP), 1.f, &logp, gamma.data(),
+            time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
+    xent->xent_objf_per_seq[b] = (float)xent_one(gamma.data(), std::isfinite(logp), (const float*)xent->z + (size_t)b * T * D, (int)seq_lengths[b],
+                                                 T, D, sc, xent->xent_grad ? (float*)xent->xent_grad + (size_t)b * T * D : nullptr);
+  });
+  if (xent->xent_totals) {
+    double S = 0.0;
+    for (int b = 0; b < B; b++) S += (double)xent->xent_objf_per_seq[b];
+    xent->xent_totals[0] = xent->xent_totals[1] = (float)S;
+  }
   return PYCHAIN_HIP_OK;
 }

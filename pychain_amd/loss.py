@@ -24,7 +24,7 @@ import torch.nn as nn
 from . import _lib, _plan, native
 from .graph import ChainGraphBatch
 
-__all__ = ["ChainFunction", "ChainLossFunction", "ChainLoss"]
+__all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent", "ChainLoss"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -242,15 +242,147 @@ class ChainLossFunction(torch.autograd.Function):
         return grad.to(ctx.in_dtype), None, None, None, None, None
 
 
+class NumeratorXentFunction(torch.autograd.Function):
+    """sum_b xent_objf[b] of include/pychain_hip.h (pychain_hip_xent): the numerator posteriors of (nnet_output, num_graphs) as
+    cross-entropy targets of xent_output.  Differentiable in xent_output only - the posteriors are constant targets.  The
+    gradient is written by the forward call for an upstream gradient of 1; backward rescales."""
+
+    @staticmethod
+    def forward(ctx, xent_output, nnet_output, lengths, num_graphs):
+        x, z = nnet_output.detach(), xent_output.detach()
+        if x.size(0) != num_graphs.batch_size:
+            raise ValueError("input batch size ({}) does not equal to graph batch size ({})".format(x.size(0), num_graphs.batch_size))
+        if not num_graphs.log_domain:
+            raise ValueError("numerator_xent takes log-domain numerator graphs")
+        z_grad = bool(ctx.needs_input_grad[0])
+        evaluate = lambda: NumeratorXentFunction._evaluate(z, x, lengths, num_graphs, z_grad)
+        res = evaluate()
+        ctx.grad_buf = res.grad
+        ctx.again = _recompute(z, evaluate, lambda r: r.grad)
+        ctx.in_dtype = xent_output.dtype
+        out = res.totals[1].clone()
+        out.xent_objf_per_seq = res.objf
+        return out
+
+    @staticmethod
+    def _evaluate(z, x, lengths, graphs, z_grad):
+        tw = getattr(graphs, "time_windows", None)
+        if not x.is_cuda:
+            return native.cpu_num_xent(graphs, x, lengths, z, with_grad=z_grad, windows=tw)
+        return native.num_xent(graphs.device_tensors(x.device), 0 if graphs.shared_graph is not None else 1, graphs.num_states,
+                               x, lengths, z, with_grad=z_grad, windows=None if tw is None else graphs.device_time_windows(x.device))
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        grad = _take_grad_buffer(ctx, "grad_buf")
+        if grad is None:
+            grad = ctx.again()                               # second backward over a retained graph: evaluate again
+        grad = native.rescale_(grad, g) if grad.is_cuda else torch.mul(grad, g)
+        return grad.to(ctx.in_dtype), None, None, None
+
+
+def numerator_xent(xent_output, nnet_output, lengths, num_graphs):
+    """The cross-entropy objective of chain training's "xent regularisation" (Kaldi: --chain.xent-regularize): with gamma the
+    numerator posteriors of (nnet_output, num_graphs) - under the batch's time windows, if set -
+        sum_b sum_{t < L_b} sum_d gamma_b(t,d) log_softmax(xent_output)(b,t,d)
+    as a 0-dim tensor, differentiable in xent_output only.  Device tensors run on the HIP kernels (one numerator
+    forward-backward, compact posterior rows, one pass over xent_output), CPU tensors on the host twin.  `.xent_objf_per_seq`
+    of the result: the [B] per-sequence objectives."""
+    return NumeratorXentFunction.apply(xent_output, nnet_output, lengths, num_graphs)
+
+
+class ChainLossXentFunction(torch.autograd.Function):
+    """ChainLossFunction with a second differentiable input, the xent branch's output z: the numerator posteriors of the step
+    become its cross-entropy targets inside the same fused call (include/pychain_hip.h: pychain_hip_xent).
+    loss = LF-MMI - c * xent, both divided by the frame count when `avg`.  The gradient of z is written by the forward call
+    (scale -c [/ frames], an upstream gradient of 1); backward rescales.  The gradient of the chain output is
+    ChainLossFunction's, bit for bit: nothing flows back to it through the posteriors."""
+
+    @staticmethod
+    def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize):
+        x = input.detach()
+        B, D = x.size(0), x.size(2)
+        if B != num_graphs.batch_size:
+            raise ValueError(
+                "input batch size ({}) does not equal to graph batch size ({})"
+                .format(B, num_graphs.batch_size))
+        lengths = torch.as_tensor(input_lengths)
+        plan = _plan.graph_plan(den_graph, D, x.device)
+        gt = num_graphs.device_tensors(x.device)
+        gstride = 0 if num_graphs.shared_graph is not None else 1
+        tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
+        ctx.host_scale, ctx.dev_norm = 1.0, None
+        if avg:
+            if lengths.is_cuda:
+                ctx.dev_norm = lengths.sum().to(torch.float32)
+            else:
+                ctx.host_scale = 1.0 / float(lengths.sum())
+        ctx.speculative = bool(ctx.needs_input_grad[0]) and ChainLossFunction.overlap
+        half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
+        z = xent_output.detach()
+        spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closure must not hold ctx)
+        z_grad, c = bool(ctx.needs_input_grad[1]), float(xent_regularize)
+        evaluate = lambda loss_scale: native.chain_loss_forward(
+            plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+            with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw,
+            xent=(z, z_grad, c))
+        den_objf, num_objf, bad, state, totals = evaluate(hscale)
+        objf = native.totals_scalar(totals)                 # the full loss: LF-MMI - c * xent [/ frames]
+        ctx.state = state
+        ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
+        ctx.z_version, ctx.z = z._version, z
+        ctx.in_dtype, ctx.z_dtype = input.dtype, xent_output.dtype
+        ctx.bad_count = bad
+        out = _attach(objf, totals, bad)
+        out.xent_objf = state.xent.totals[0]                # sum_b xent_objf[b] [/ frames]: detached, for logging
+        out.xent_objf_per_seq = state.xent.objf
+        return out
+
+    @staticmethod
+    def backward(ctx, objf_grad):
+        state = _take_grad_buffer(ctx, "state")
+        if state is None:
+            if ctx.z._version != ctx.z_version:
+                raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                                   "the xent output given to the LF-MMI loss (second backward over a retained graph)")
+            state, ctx.bad_count = ctx.again()
+            ChainFunction.last_bad_count = ctx.bad_count
+        grad = None
+        if ctx.needs_input_grad[0]:
+            if ctx.speculative:
+                grad = native.rescale_(state.grad, objf_grad)
+            else:
+                g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
+                grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
+                ctx.bad_count = ctx.bad_count + bad
+                ChainFunction.last_bad_count = ctx.bad_count
+            grad = grad.to(ctx.in_dtype)
+        zgrad = None
+        if ctx.needs_input_grad[1]:
+            zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
+        state.grad = state.xent = None
+        state.den_ws = state.num_ws = None
+        return grad, zgrad, None, None, None, None, None, None
+
+
 class ChainLoss(nn.Module):
-    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True):
+    """`xent_regularize` = c > 0 and `forward(..., xent_output=z)`: the loss is LF-MMI - c * xent, xent the cross-entropy objective
+    of z against the numerator posteriors of the same step (numerator_xent); `loss.xent_objf` is that objective [/ frames],
+    detached.  c = 0 or no xent_output: exactly the loss without it."""
+
+    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, xent_regularize=0.0):
         super(ChainLoss, self).__init__()
         self.den_graph = den_graph
         self.avg = avg
         self.leaky_coefficient = leaky_coefficient
+        self.xent_regularize = float(xent_regularize)
         self.fused = True   # one-pass kernel path; False = two ChainFunction calls as in the reference
 
-    def forward(self, x, x_lengths, num_graphs):
+    def forward(self, x, x_lengths, num_graphs, xent_output=None):
+        if self.xent_regularize != 0.0 and xent_output is not None:
+            return self._forward_xent(x, x_lengths, num_graphs, xent_output)
         if (self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain):
             return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs,
                                            self.leaky_coefficient, self.avg)
@@ -266,4 +398,19 @@ class ChainLoss(nn.Module):
         objf.totals = objf.totals_all = None
         objf.bad_count = (den_objf.bad_count, num_objf.bad_count)
         ChainFunction.last_totals = ChainFunction.last_totals_all = None
+        return objf
+
+    def _forward_xent(self, x, x_lengths, num_graphs, xent_output):
+        if (self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain):
+            return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
+                                               self.leaky_coefficient, self.avg, self.xent_regularize)
+        # the unfused route: the loss without xent as it is, and the cross-entropy term through numerator_xent
+        lfmmi = self.forward(x, x_lengths, num_graphs)
+        xent = numerator_xent(xent_output, x, x_lengths, num_graphs)
+        if self.avg:
+            xent = xent / x_lengths.sum()
+        objf = lfmmi - self.xent_regularize * xent
+        objf.totals = objf.totals_all = None
+        objf.bad_count = lfmmi.bad_count
+        objf.xent_objf = xent.detach()
         return objf

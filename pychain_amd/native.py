@@ -6,11 +6,12 @@ reference's positional signatures and return `[objf, grad, ok]`; the `den_*` /
 `num_*` functions are what `pychain_amd.loss` calls (device-resident plans, fused
 clamp/exp, per-sequence objf).
 """
+import ctypes
+import threading
+
 import torch
 
 from . import _lib, _plan
-
-import threading
 
 _ws_cache = {}          # (device, stream, tag) -> uint8 tensor, most recently used last
 _ws_lock = threading.Lock()      # (criteria on several host threads share this module)
@@ -223,6 +224,94 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
     return objf, grad, bad
 
 
+class XentResult(object):
+    """What an *_xent entry point leaves (include/pychain_hip.h: pychain_hip_xent): objf [B] fp32, totals fp32[2] = [scaled sum,
+    sum], grad [B,T,D] in z's dtype or None (the form without the store)."""
+    __slots__ = ("objf", "totals", "grad")
+
+
+def _xent_arg(z, shape, H, K, with_grad, grad_scale, loss_coef, res):
+    """(the pychain_hip_xent of a device call, the tensors it points to - to be kept alive over the call).  `z` goes to the
+    kernel in its own dtype (fp32 / bf16 / fp16) whatever the row width; the gradient comes back in the same dtype."""
+    B, T, D = shape
+    _require_device(z, "xent_output")
+    if tuple(z.shape) != (B, T, D):
+        raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(z.shape), (B, T, D)))
+    if z.dtype not in _DTYPE_CODE:
+        raise ValueError("xent_output must be float32, bfloat16 or float16, got %s" % z.dtype)
+    dev = z.device
+    zc = z.detach().contiguous()
+    res.objf = torch.empty(B, dtype=torch.float32, device=dev)
+    res.totals = torch.empty(2, dtype=torch.float32, device=dev)
+    res.grad = torch.empty_like(zc) if with_grad else None
+    ws = _workspace(_lib.lib().pychain_hip_xent_workspace_bytes(B, T, int(H), int(K), D), dev, "xent")
+    arg = _lib.Xent(zc.data_ptr(), _DTYPE_CODE[zc.dtype], res.grad.data_ptr() if with_grad else None, float(grad_scale), None,
+                    float(loss_coef), res.objf.data_ptr(), res.totals.data_ptr(), ws.data_ptr(), ws.numel())
+    return arg, (zc, ws)
+
+
+def num_xent(gt, graph_stride, num_states, x, lengths, z, with_grad=True, windows=None):
+    """The numerator posteriors of (x, graphs) as cross-entropy targets of z on the GPU: pychain_hip_num_forward_backward_xent
+    without a dense numerator gradient.  Returns an XentResult (grad for an upstream gradient of 1)."""
+    _require_device(x, "nnet_output")
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    K = gt["forward_transitions"].shape[1]
+    L = _lib.lib()
+    dev = x.device
+    res = XentResult()
+    with torch.cuda.device(dev):
+        x, xcode = _rows_as_given(x, lambda: L.pychain_hip_num_half_native(int(num_states), K, D))
+        ld = _lengths_dev(lengths, dev)
+        objf = torch.empty(B, dtype=torch.float32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pychain_hip_num_workspace_bytes(B, T, int(num_states), K, D), dev, "num")
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states), dev)
+        arg, keep = _xent_arg(z, (B, T, D), num_states, K, with_grad, 1.0, 0.0, res)
+        _lib.check(L.pychain_hip_num_forward_backward_xent(
+            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
+            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
+            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
+            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
+            x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(_lib.GRAD_LINEAR), 1.0,
+            objf.data_ptr(), 0, bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev),
+            0 if windows is None else windows.data_ptr(), ctypes.addressof(arg)), "pychain_hip_num_forward_backward_xent")
+        del keep
+    return res
+
+
+def cpu_num_xent(graphs, x, lengths, z, with_grad=True, windows=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_num_forward_backward_xent), fp64 accumulation."""
+    if x.is_cuda or z.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_num_xent is for CPU tensors; device tensors run on the HIP kernels")
+    xf = x.detach().to(torch.float32).contiguous()
+    zf = z.detach().to(torch.float32).contiguous()
+    B, T, D = xf.shape
+    if tuple(zf.shape) != (B, T, D):
+        raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(zf.shape), (B, T, D)))
+    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
+    _check_lengths(lc, B, T)
+    ts, stride = _cpu_graph(graphs, False)
+    H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
+    objf = torch.empty(B, dtype=torch.float32)
+    grad = torch.empty(B, T, D, dtype=torch.float32)
+    bad = torch.zeros(1, dtype=torch.int32)
+    res = XentResult()
+    res.objf = torch.empty(B, dtype=torch.float32)
+    res.totals = torch.empty(2, dtype=torch.float32)
+    res.grad = torch.empty(B, T, D, dtype=torch.float32) if with_grad else None
+    tw = None if windows is None else _check_windows(windows.cpu(), B, H)
+    arg = _lib.Xent(zf.data_ptr(), _lib.F32, res.grad.data_ptr() if with_grad else None, 1.0, None, 0.0, res.objf.data_ptr(),
+                    res.totals.data_ptr(), None, 0)
+    _lib.check(_lib.lib().pychain_hip_cpu_num_forward_backward_xent(
+        *[t.data_ptr() for t in ts], stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K, int(_lib.GRAD_LINEAR), 1.0,
+        objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), int(CPU_THREADS), 0 if tw is None else tw.data_ptr(),
+        ctypes.addressof(arg)), "pychain_hip_cpu_num_forward_backward_xent")
+    return res
+
+
 def align(gt, graph_stride, num_states, x, lengths):
     """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
@@ -316,16 +405,19 @@ class ChainLossState(object):
     """What `chain_loss_forward` leaves behind for `chain_loss_backward`: the stored
     trajectories (workspaces) and the handles of everything the occupancy passes read."""
     __slots__ = ("plan", "gt", "graph_stride", "num_states_num", "x", "lengths_dev", "den_ws", "num_ws", "shape",
-                 "grad", "num_compat")
+                 "grad", "num_compat", "xent")
 
 
 def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient=1e-5,
-                       with_grad=False, grad_scale=1.0, loss_scale=1.0, norm_dev=None, half_ok=True, windows=None):
+                       with_grad=False, grad_scale=1.0, loss_scale=1.0, norm_dev=None, half_ok=True, windows=None, xent=None):
     """Recursions (and, `with_grad`, the occupancy passes overlapped with them: state.grad =
     grad_scale * (gamma_den - gamma_num)).  Returns (den_objf[B], num_objf[B], bad_count[2], state, totals) with
     totals = device float[4] [(sum den - sum num) * loss_scale [/ norm_dev], frames, bad count, sum den - sum num]
     written by the call's last kernel (include/pychain_hip.h).  `windows`: the numerator's device time windows (int32
-    [B, H, 2]) or None; chain_loss_backward reads the rows they shaped and needs them no more."""
+    [B, H, 2]) or None; chain_loss_backward reads the rows they shaped and needs them no more.
+    `xent`: None, or (z, with_grad, c) - the numerator posteriors of the call as cross-entropy targets of z (include/pychain_hip.h:
+    pychain_hip_xent): state.xent is then an XentResult (grad = -c * grad_scale [/ norm_dev] * d xent / dz, written by the same
+    call), and totals[0] = totals[4] = the full loss, LF-MMI - c * xent, scaled alike."""
     _require_device(x, "nnet_output")
     x = x.contiguous()
     B, T, D = x.shape
@@ -354,6 +446,13 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
         if windows is not None:
             windows = _check_windows(windows, B, int(num_states_num), dev)
             fn, name, tail = L.pychain_hip_chain_loss_forward_tw, "pychain_hip_chain_loss_forward_tw", (windows.data_ptr(),)
+        st.xent = keep = None
+        if xent is not None:
+            z, z_grad, c = xent
+            st.xent = XentResult()
+            arg, keep = _xent_arg(z, (B, T, D), num_states_num, K, z_grad, -float(c) * float(grad_scale), -float(c), st.xent)
+            fn, name = L.pychain_hip_chain_loss_forward_xent, "pychain_hip_chain_loss_forward_xent"
+            tail = (0 if windows is None else windows.data_ptr(), ctypes.addressof(arg))
         _lib.check(fn(
             plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient),
             gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),

@@ -114,12 +114,16 @@ class ShardedChainLoss(torch.nn.Module):
     no scalar kernels of the host framework around the collective; a world of one does nothing at all here unless
     `force_collective` asks for the collective anyway (one rank under torch.distributed: the RCCL leg of the GPU tests)."""
 
-    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, group=None, loss_cls=None, force_collective=False):
+    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, group=None, loss_cls=None, force_collective=False,
+                 xent_regularize=0.0):
         super().__init__()
         self._native = loss_cls is None or bool(getattr(loss_cls, "reports_bad_count", False))
         if loss_cls is None:
             from .loss import ChainLoss as loss_cls
-        self.local = loss_cls(den_graph, leaky_coefficient, avg=False)
+        # (the xent term - ChainLoss(xent_regularize=c), forward(..., xent_output=z) - rides in the local loss: the totals of the
+        # native call hold the FULL local loss, so the collective below is the same one)
+        self.local = (loss_cls(den_graph, leaky_coefficient, avg=False, xent_regularize=xent_regularize) if xent_regularize
+                      else loss_cls(den_graph, leaky_coefficient, avg=False))
         self.avg = avg
         self.group = group
         self.force_collective = bool(force_collective)
@@ -128,8 +132,9 @@ class ShardedChainLoss(torch.nn.Module):
     def _world(self):
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
-    def forward(self, x, x_lengths, num_graphs):
-        local = self.local(x, x_lengths, num_graphs)                  # sum over local utterances
+    def forward(self, x, x_lengths, num_graphs, xent_output=None):
+        # sum over local utterances
+        local = self.local(x, x_lengths, num_graphs) if xent_output is None else self.local(x, x_lengths, num_graphs, xent_output)
         # [loss, frames, bad, ...] of THIS call, on the device: they came back with the tensor (pychain_amd/loss.py: _attach)
         totals = getattr(local, "totals", None) if self._native else None
         collective = dist.is_available() and dist.is_initialized() and (self._world() > 1 or self.force_collective)
