@@ -76,6 +76,11 @@ def main():
                          "spin-wait kernels on a box with a single GPU")
     ap.add_argument("--xent-regularize", type=float, default=0.0,
                     help="c > 0: a second output head trained by cross-entropy against the numerator posteriors, loss = LF-MMI - c * xent")
+    ap.add_argument("--l2-regularize", type=float, default=0.0,
+                    help="l2 > 0: output L2 (Kaldi: --chain.l2-regularize), the loss gains 0.5 * l2 * sum x^2 / frames over the chain output")
+    ap.add_argument("--out-of-range-regularize", type=float, default=0.0,
+                    help="r > 0: Kaldi's --chain.out-of-range-regularize, the loss gains r * sum max(|x| - 30, 0)^2 / frames - what pulls an "
+                         "output back from beyond the kernels' clamp, where the LF-MMI objective is flat")
     ap.add_argument("--loss-cls", default=None,
                     help="module:Class of a ChainLoss(den_graph, leaky, avg=False) stand-in for the per-rank loss")
     args = ap.parse_args()
@@ -109,7 +114,8 @@ def main():
     opt = torch.optim.AdamW(model.parameters(), lr=args.lr)
     den_graph = syn.make_den_graph(args.states, args.arcs, args.pdfs, seed=0)      # the shared "phone LM"
     criterion = ShardedChainLoss(den_graph, leaky_coefficient=1e-5, avg=True, loss_cls=loss_cls, force_collective=use_dist and world == 1,
-                                 xent_regularize=args.xent_regularize)
+                                 xent_regularize=args.xent_regularize, output_l2_regularize=args.l2_regularize,
+                                 out_of_range_regularize=args.out_of_range_regularize)
 
     # a fixed synthetic training set per rank: features correlated with the numerator alignment
     gen = torch.Generator(device=dev).manual_seed(100 + rank)

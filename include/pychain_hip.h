@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 20
+#define PYCHAIN_HIP_ABI_VERSION 21
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -518,6 +518,53 @@ int pychain_hip_cpu_num_forward_backward_xent(
     int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows,
     const pychain_hip_xent* xent);
+
+/* ------------------------------------------------------------------------
+ * Output regularisers (ABI 21): the two element-wise terms of the chain objective over the network output x [B,T,D] itself,
+ * Kaldi's --chain.l2-regularize and --chain.out-of-range-regularize (PenalizeOutOfRange).  With e(x) = max(|x| - limit, 0) on the
+ * RAW x (limit = 30 is the kernels' own clamp: beyond it the LF-MMI objective is flat and its gradient is the occupancy whatever
+ * x was - the penalty is what pulls such an output back),
+ *   R2_b = sum_{t < L_b} sum_d x(b,t,d)^2          RO_b = sum_{t < L_b} sum_d e(x(b,t,d))^2
+ *   term(x) = l2 * x + 2 * oor * sign(x) * e(x)    = d (0.5 * l2 * x^2 + oor * e(x)^2) / dx
+ * One streaming pass over the live rows (t < L_b) only; rows t >= L_b are NEVER READ (a NaN in padding is harmless).  `grad`:
+ *   NULL                      the objective only: x is read once, nothing else of [B,T,D] size is touched
+ *   PYCHAIN_HIP_GRAD_ACCUM    grad(b,t,d) += s * term(x(b,t,d)) for t < L_b: the stored row is read once and written once, in the
+ *                             gradient's dtype; rows t >= L_b are NOT TOUCHED
+ *   PYCHAIN_HIP_GRAD_LINEAR   grad(b,t,d)  = s * term(x(b,t,d)) for t < L_b, zeros for t >= L_b: every element written once
+ * with s = grad_scale [* *grad_scale_dev] [/ *loss_norm_dev], both scalars read on the device (no host sync).  `grad` has
+ * nnet_output's dtype.  The gradient term is plain fp32 (csrc/outreg.hip writes its operation sequence down: 7 roundings at
+ * most, the add into the stored gradient included).  A 2-BYTE GRADIENT IN ACCUM IS ROUNDED TWICE: the call that stored it rounded
+ * it to bf16 / fp16, and this pass rounds the sum again.  Squares and sums are fp64 from the first add (x is widened first, so
+ * x^2 and |x| - limit are exact), added up in a fixed order - lanes, then one {R2, RO} pair per frame, then the frames of a
+ * sequence -, without float atomics: the same call gives the same bits.  A NaN or an infinity in a live row makes that
+ * sequence's R2_b / RO_b what the torch composition would make them, and leaves the other sequences' values alone.
+ *   reg_per_seq  dev float [B][2] = {R2_b, RO_b}, the fp64 sums rounded once
+ *   reg_totals   dev float [3] or NULL: [0] = loss_scale * (0.5 l2 sum_b R2_b + oor sum_b RO_b) [/ *loss_norm_dev],
+ *                [1] = sum_b R2_b, [2] = sum_b RO_b (fp64 over the unrounded per-sequence sums, rounded once)
+ *   totals       dev float [PYCHAIN_HIP_TOTALS] or NULL: the totals of a fused call on the same stream.  The call's last kernel
+ *                adds reg_totals[0] to totals[0] and totals[4] - one thread, in stream order behind the fused call and behind its
+ *                xent totals - so they hold the full loss; totals[1..3] and totals[5..7] keep their bits.
+ *   workspace    dev, pychain_hip_output_reg_workspace_bytes(B, T) bytes, 16-byte aligned: the frame pairs (fp64 [B,T,2]) and the
+ *                unrounded per-sequence sums
+ * Lengths outside [1,T] are clamped, as everywhere.  Any D >= 1: 16-byte loads and stores where the rows allow (fp32 rows of a
+ * multiple of 4 elements, 2-byte rows of a multiple of 8; 8-byte ones for 2-byte rows of a multiple of 4), else element by
+ * element.  l2 < 0, oor < 0, limit < 0 or a grad_mode other than the two above: PYCHAIN_HIP_EINVAL.  nnet_output, grad and
+ * workspace must be 16-byte aligned.  The entry point is a translation unit of its own: the objects of den_*.hip, num_*.hip,
+ * xent.hip and align.hip do not change, and no existing entry point launches anything it did not launch before. */
+size_t pychain_hip_output_reg_workspace_bytes(int B, int T);
+int pychain_hip_output_reg(
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float l2, float oor, float limit, int grad_mode, void* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* reg_per_seq, float loss_scale, float* reg_totals, float* totals,
+    void* workspace, size_t workspace_bytes, void* stream);
+/* the host twin: the same on host pointers (the two scalars too), fp32 rows, the same fp32 operation sequence of the gradient term
+ * and fp64 sums; no workspace, no stream */
+int pychain_hip_cpu_output_reg(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float l2, float oor, float limit, int grad_mode, float* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* reg_per_seq, float loss_scale, float* reg_totals, float* totals, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

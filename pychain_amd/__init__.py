@@ -1,6 +1,6 @@
 """pychain_amd: MI355X-native LF-MMI loss behind the pychain API.
 
-    from pychain_amd import ChainGraph, ChainGraphBatch, ChainFunction, ChainLoss, viterbi_align, alignment_windows
+    from pychain_amd import ChainGraph, ChainGraphBatch, ChainFunction, ChainLoss, viterbi_align, alignment_windows, output_regularizer
 
 (`import pychain` resolves to the same objects through the alias package at the
 repository root, so code written against the reference imports unchanged.)
@@ -27,5 +27,5 @@ def _more_hardware_queues():
 _more_hardware_queues()
 
 from .graph import ChainGraph, ChainGraphBatch  # noqa: F401
-from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent  # noqa: F401
+from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent, output_regularizer  # noqa: F401
 from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401

@@ -419,3 +419,76 @@ extern "C" int pychain_hip_cpu_num_forward_backward_xent(
   }
   return PYCHAIN_HIP_OK;
 }
+
+// ---- output regularisers (include/pychain_hip.h: pychain_hip_output_reg; the device's outreg.hip): the same fp32 operation
+// sequence of the gradient term - nothing contracted - and fp64 sums, frame by frame in ascending order
+namespace pychain_hip {
+namespace {
+inline float outreg_term(float x, float l2, float oor2, float lim, float s) {
+#pragma clang fp contract(off)
+  const float a = l2 * x;
+  const float d = std::fabs(x) - lim;
+  const float e = d > 0.f ? d : 0.f;
+  const float u = std::fma(oor2, std::copysign(e, x), a);
+  return s * u;
+}
+inline float outreg_add(float g, float term) {
+#pragma clang fp contract(off)
+  return g + term;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_output_reg(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    float l2, float oor, float limit, int grad_mode, float* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* reg_per_seq, float loss_scale, float* reg_totals, float* totals, int num_threads) {
+  const char* who = "cpu_output_reg";
+  if (!nnet_output || !seq_lengths || !reg_per_seq) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (!(l2 >= 0.f) || !(oor >= 0.f) || !(limit >= 0.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: l2, oor and limit must not be negative (got %g, %g, %g)", who, (double)l2, (double)oor, (double)limit);
+  if (grad_mode != PYCHAIN_HIP_GRAD_ACCUM && grad_mode != PYCHAIN_HIP_GRAD_LINEAR)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: grad_mode must be PYCHAIN_HIP_GRAD_ACCUM or PYCHAIN_HIP_GRAD_LINEAR, got %d", who, grad_mode);
+  g_cpu_calls++;
+  float s = grad_scale_dev ? grad_scale * *grad_scale_dev : grad_scale;
+  if (loss_norm_dev) s = s / *loss_norm_dev;
+  const float oor2 = 2.f * oor;
+  const double limd = (double)limit;
+  const bool accum = grad_mode == PYCHAIN_HIP_GRAD_ACCUM;
+  std::vector<double> pairs(2 * (size_t)B);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int64_t l = seq_lengths[b];
+    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const float* x = nnet_output + (size_t)b * T * D;
+    float* g = grad ? grad + (size_t)b * T * D : nullptr;
+    double s2 = 0.0, so = 0.0;
+    for (int t = 0; t < L; t++) {
+      double r2 = 0.0, ro = 0.0;
+      for (int n = 0; n < D; n++) {
+        const float v = x[(size_t)t * D + n];
+        const double xd = (double)v, ad = std::fabs(xd) - limd, ed = !(ad <= 0.0) ? ad : 0.0;
+        r2 = std::fma(xd, xd, r2);
+        ro = std::fma(ed, ed, ro);
+        if (g) {
+          const float term = outreg_term(v, l2, oor2, limit, s);
+          g[(size_t)t * D + n] = accum ? outreg_add(g[(size_t)t * D + n], term) : term;
+        }
+      }
+      s2 += r2; so += ro;
+    }
+    if (g && !accum) memset(g + (size_t)L * D, 0, sizeof(float) * (size_t)(T - L) * D);
+    pairs[2 * (size_t)b] = s2; pairs[2 * (size_t)b + 1] = so;
+    reg_per_seq[2 * b] = (float)s2; reg_per_seq[2 * b + 1] = (float)so;
+  });
+  if (reg_totals || totals) {
+    double s2 = 0.0, so = 0.0;
+    for (int b = 0; b < B; b++) { s2 += pairs[2 * (size_t)b]; so += pairs[2 * (size_t)b + 1]; }
+    double v = (double)loss_scale * ((l2 != 0.f ? 0.5 * (double)l2 * s2 : 0.0) + (oor != 0.f ? (double)oor * so : 0.0));
+    if (loss_norm_dev) v /= (double)*loss_norm_dev;
+    if (reg_totals) { reg_totals[0] = (float)v; reg_totals[1] = (float)s2; reg_totals[2] = (float)so; }
+    if (totals) { const float full = (float)((double)totals[0] + v); totals[0] = full; totals[4] = full; }
+  }
+  return PYCHAIN_HIP_OK;
+}

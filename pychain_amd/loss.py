@@ -24,7 +24,8 @@ import torch.nn as nn
 from . import _lib, _plan, native
 from .graph import ChainGraphBatch
 
-__all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent", "ChainLoss"]
+__all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent",
+           "output_regularizer", "ChainLoss"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -167,6 +168,35 @@ def _take_grad_buffer(ctx, attr):
     return buf
 
 
+def _with_output_reg(result, reg, speculative, host_scale, dev_norm, loss_scale):
+    """`result` of native.chain_loss_forward with the output regularisers `reg` = (l2, oor) on top: native.output_reg on the
+    current stream behind the fused call - ACCUM into the gradient the call wrote for an upstream gradient of 1 (speculative
+    mode), else the objective only -, its scaled term added to the call's totals[0] and totals[4].  state.reg: the RegResult."""
+    state, totals = result[3], result[4]
+    state.reg = native.output_reg(state.x, state.lengths_dev, reg[0], reg[1], grad=state.grad if speculative else None,
+                                  grad_mode=_lib.GRAD_ACCUM, grad_scale=host_scale, norm_dev=dev_norm, loss_scale=loss_scale,
+                                  totals=totals)
+    return result
+
+
+def _accumulate_output_reg(reg, state, grad, host_scale, upstream):
+    """overlap = False: the regularisers' gradient into the one chain_loss_backward just wrote (scale host_scale * upstream)."""
+    if reg is not None:
+        native.output_reg(state.x, state.lengths_dev, reg[0], reg[1], grad=grad, grad_mode=_lib.GRAD_ACCUM,
+                          grad_scale=host_scale, grad_scale_dev=upstream)
+
+
+def _attach_reg(out, res, reg, host_scale, dev_norm):
+    """`out.l2_term`, `out.out_of_range_term`: the two amounts the regularisers added to the loss (detached, for logging)."""
+    if res is None:
+        return out
+    l2t, oort = (0.5 * reg[0] * host_scale) * res.totals[1], (reg[1] * host_scale) * res.totals[2]
+    if dev_norm is not None:
+        l2t, oort = l2t / dev_norm.to(l2t.device), oort / dev_norm.to(oort.device)
+    out.l2_term, out.out_of_range_term = l2t, oort
+    return out
+
+
 class ChainLossFunction(torch.autograd.Function):
     """Denominator + numerator in one pass, split at the autograd
     boundary: forward runs the four recursions (numerator on a side stream) and returns the
@@ -176,7 +206,7 @@ class ChainLossFunction(torch.autograd.Function):
     (loss.py:85,100-104).  Same numbers as the two-call path."""
 
     @staticmethod
-    def forward(ctx, input, input_lengths, den_graph, num_graphs, leaky_coefficient, avg):
+    def forward(ctx, input, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, reg=None):
         x = input.detach()
         B, D = x.size(0), x.size(2)
         if B != num_graphs.batch_size:
@@ -203,22 +233,33 @@ class ChainLossFunction(torch.autograd.Function):
         ctx.speculative = bool(ctx.needs_input_grad[0]) and ChainLossFunction.overlap
         # (2-byte network outputs go to the kernels as they are when the gradient is written here, or never)
         half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
-        den_objf, num_objf, bad, state, totals = native.chain_loss_forward(
-            plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-            with_grad=ctx.speculative, grad_scale=ctx.host_scale, loss_scale=ctx.host_scale, norm_dev=ctx.dev_norm,
-            half_ok=half_ok, windows=tw)
+        spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closures must not hold ctx)
+        if reg is None:
+            den_objf, num_objf, bad, state, totals = native.chain_loss_forward(
+                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+                with_grad=ctx.speculative, grad_scale=ctx.host_scale, loss_scale=ctx.host_scale, norm_dev=ctx.dev_norm,
+                half_ok=half_ok, windows=tw)
+            # a second backward over a retained graph (loss.py:82-87 allows it) runs the recursions again
+            ctx.again = _recompute(x, lambda: native.chain_loss_forward(
+                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+                with_grad=spec, grad_scale=hscale, norm_dev=dnorm, half_ok=half_ok, windows=tw), lambda r: (r[3], r[2]))   # (state, bad)
+        else:
+            # the output regularisers: one more pass on the same stream behind the fused call, over the whole batch (after the
+            # last slice of a call in slices) - into the gradient the call wrote (speculative), else the objective only
+            evaluate = lambda loss_scale: _with_output_reg(native.chain_loss_forward(
+                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+                with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw),
+                reg, spec, hscale, dnorm, loss_scale)
+            den_objf, num_objf, bad, state, totals = evaluate(hscale)
+            ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
+        ctx.reg = reg
         # -(num - den) [/ frames], loss.py:100-104, comes with the call (the last workgroup of its last kernel adds the
         # per-sequence objectives up): no reduction / subtraction / scaling launches behind it
         objf = native.totals_scalar(totals)    # (no launch; not a view of the statistics: `loss /= n` works)
         ctx.state = state
-        # a second backward over a retained graph (loss.py:82-87 allows it) runs the recursions again
-        spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closure must not hold ctx)
-        ctx.again = _recompute(x, lambda: native.chain_loss_forward(
-            plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-            with_grad=spec, grad_scale=hscale, norm_dev=dnorm, half_ok=half_ok, windows=tw), lambda r: (r[3], r[2]))   # (state, bad)
         ctx.in_dtype = input.dtype
         ctx.bad_count = bad                      # int32[2]: denominator, numerator; never synced here
-        return _attach(objf, totals, bad)
+        return _attach_reg(_attach(objf, totals, bad), state.reg, reg, hscale, dnorm)
 
     overlap = True     # class-level switch: False = occupancy passes run in backward (no speculation)
 
@@ -235,11 +276,12 @@ class ChainLossFunction(torch.autograd.Function):
         else:
             g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
             grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
+            _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
             ctx.bad_count = ctx.bad_count + bad              # (the occupancy launches' own checks)
             ChainFunction.last_bad_count = ctx.bad_count
         state.grad = None         # the stored trajectories go with `state`
         state.den_ws = state.num_ws = None
-        return grad.to(ctx.in_dtype), None, None, None, None, None
+        return grad.to(ctx.in_dtype), None, None, None, None, None, None
 
 
 class NumeratorXentFunction(torch.autograd.Function):
@@ -293,6 +335,48 @@ def numerator_xent(xent_output, nnet_output, lengths, num_graphs):
     return NumeratorXentFunction.apply(xent_output, nnet_output, lengths, num_graphs)
 
 
+class OutputRegFunction(torch.autograd.Function):
+    """0.5 * l2 * sum_b R2_b + oor * sum_b RO_b of include/pychain_hip.h (pychain_hip_output_reg) as a 0-dim tensor, differentiable
+    in the network output.  Device tensors: the LINEAR form of csrc/outreg.hip, the gradient written by the forward call for an
+    upstream gradient of 1 (backward rescales); CPU tensors: the host twin."""
+
+    @staticmethod
+    def forward(ctx, input, lengths, l2, oor):
+        x = input.detach()
+        want = bool(ctx.needs_input_grad[0])
+        run = native.output_reg if x.is_cuda else native.cpu_output_reg
+        evaluate = lambda: run(x, lengths, l2, oor, grad_mode=_lib.GRAD_LINEAR, with_grad=want)
+        res = evaluate()
+        ctx.grad_buf = res.grad
+        ctx.again = _recompute(x, evaluate, lambda r: r.grad)
+        ctx.in_dtype = input.dtype
+        out = res.totals[0].clone()
+        out.l2_term, out.out_of_range_term = (0.5 * l2) * res.totals[1], oor * res.totals[2]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        grad = _take_grad_buffer(ctx, "grad_buf")
+        if grad is None:
+            grad = ctx.again()                               # second backward over a retained graph: evaluate again
+        grad = native.rescale_(grad, g) if grad.is_cuda else torch.mul(grad, g)
+        return grad.to(ctx.in_dtype), None, None, None
+
+
+def output_regularizer(x, lengths, l2=0.0, out_of_range=0.0):
+    """The two element-wise regularisers of the chain objective over the network output x [B,T,D] (Kaldi: --chain.l2-regularize,
+    --chain.out-of-range-regularize), UN-averaged, as a 0-dim tensor differentiable in x:
+        0.5 * l2 * sum x^2  +  out_of_range * sum max(|x| - 30, 0)^2        over the live frames t < lengths[b]
+    (30 is the kernels' own clamp; frames beyond a length are never read and get a zero gradient).  `.l2_term` and
+    `.out_of_range_term` of the result: the two amounts, detached."""
+    l2, oor = float(l2), float(out_of_range)
+    if l2 < 0.0 or oor < 0.0:
+        raise ValueError("output_regularizer: l2 and out_of_range must not be negative (got %g, %g)" % (l2, oor))
+    return OutputRegFunction.apply(x, lengths, l2, oor)
+
+
 class ChainLossXentFunction(torch.autograd.Function):
     """ChainLossFunction with a second differentiable input, the xent branch's output z: the numerator posteriors of the step
     become its cross-entropy targets inside the same fused call (include/pychain_hip.h: pychain_hip_xent).
@@ -301,7 +385,7 @@ class ChainLossXentFunction(torch.autograd.Function):
     ChainLossFunction's, bit for bit: nothing flows back to it through the posteriors."""
 
     @staticmethod
-    def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize):
+    def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize, reg=None):
         x = input.detach()
         B, D = x.size(0), x.size(2)
         if B != num_graphs.batch_size:
@@ -324,10 +408,13 @@ class ChainLossXentFunction(torch.autograd.Function):
         z = xent_output.detach()
         spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closure must not hold ctx)
         z_grad, c = bool(ctx.needs_input_grad[1]), float(xent_regularize)
-        evaluate = lambda loss_scale: native.chain_loss_forward(
+        fused = lambda loss_scale: native.chain_loss_forward(
             plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
             with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw,
             xent=(z, z_grad, c))
+        # (the output regularisers: behind the call and behind its xent totals, on the same stream)
+        evaluate = fused if reg is None else (lambda loss_scale: _with_output_reg(fused(loss_scale), reg, spec, hscale, dnorm, loss_scale))
+        ctx.reg = reg
         den_objf, num_objf, bad, state, totals = evaluate(hscale)
         objf = native.totals_scalar(totals)                 # the full loss: LF-MMI - c * xent [/ frames]
         ctx.state = state
@@ -338,7 +425,7 @@ class ChainLossXentFunction(torch.autograd.Function):
         out = _attach(objf, totals, bad)
         out.xent_objf = state.xent.totals[0]                # sum_b xent_objf[b] [/ frames]: detached, for logging
         out.xent_objf_per_seq = state.xent.objf
-        return out
+        return _attach_reg(out, state.reg, reg, hscale, dnorm)
 
     @staticmethod
     def backward(ctx, objf_grad):
@@ -356,6 +443,7 @@ class ChainLossXentFunction(torch.autograd.Function):
             else:
                 g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
                 grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
+                _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
                 ctx.bad_count = ctx.bad_count + bad
                 ChainFunction.last_bad_count = ctx.bad_count
             grad = grad.to(ctx.in_dtype)
@@ -364,26 +452,68 @@ class ChainLossXentFunction(torch.autograd.Function):
             zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
         state.grad = state.xent = None
         state.den_ws = state.num_ws = None
-        return grad, zgrad, None, None, None, None, None, None
+        return grad, zgrad, None, None, None, None, None, None, None
 
 
 class ChainLoss(nn.Module):
     """`xent_regularize` = c > 0 and `forward(..., xent_output=z)`: the loss is LF-MMI - c * xent, xent the cross-entropy objective
     of z against the numerator posteriors of the same step (numerator_xent); `loss.xent_objf` is that objective [/ frames],
-    detached.  c = 0 or no xent_output: exactly the loss without it."""
+    detached.  c = 0 or no xent_output: exactly the loss without it.
+    `output_l2_regularize` = l2, `out_of_range_regularize` = r: the loss gains (0.5 * l2 * sum x^2 + r * sum max(|x| - 30, 0)^2)
+    [/ frames] over the live frames of the network output (output_regularizer); `loss.l2_term` and `loss.out_of_range_term` are
+    the two amounts, detached.  Both zero: exactly the loss without them, launch for launch."""
 
-    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, xent_regularize=0.0):
+    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, xent_regularize=0.0, output_l2_regularize=0.0,
+                 out_of_range_regularize=0.0):
         super(ChainLoss, self).__init__()
         self.den_graph = den_graph
         self.avg = avg
         self.leaky_coefficient = leaky_coefficient
         self.xent_regularize = float(xent_regularize)
+        self.output_l2_regularize = float(output_l2_regularize)
+        self.out_of_range_regularize = float(out_of_range_regularize)
+        if self.output_l2_regularize < 0.0 or self.out_of_range_regularize < 0.0:
+            raise ValueError("ChainLoss: output_l2_regularize and out_of_range_regularize must not be negative (got %g, %g)"
+                             % (self.output_l2_regularize, self.out_of_range_regularize))
         self.fused = True   # one-pass kernel path; False = two ChainFunction calls as in the reference
 
+    def _reg(self):
+        """(l2, oor), or None where both are zero: the code path is then exactly the one without them"""
+        if self.output_l2_regularize == 0.0 and self.out_of_range_regularize == 0.0:
+            return None
+        return (self.output_l2_regularize, self.out_of_range_regularize)
+
+    def _on_kernels(self, x, num_graphs):
+        return self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain
+
     def forward(self, x, x_lengths, num_graphs, xent_output=None):
+        reg = self._reg()
+        if reg is None or self._on_kernels(x, num_graphs):
+            return self._forward(x, x_lengths, num_graphs, xent_output, reg)
+        # the unfused route and CPU tensors: the loss without the terms as it is, and the terms through output_regularizer
+        # (the loss without the terms reads x through a view of its own: its calls' gradients are added up at that view, as
+        # ChainLoss without the terms adds them, and x receives exactly two gradients - that sum and the term.  A sum of two
+        # does not depend on which arrives first: x.grad is (the gradient without the terms) + the term, rounded once more)
+        base = self._forward(x.view_as(x), x_lengths, num_graphs, xent_output, None)
+        term = output_regularizer(x, x_lengths, reg[0], reg[1])
+        l2t, oort = term.l2_term, term.out_of_range_term
+        if self.avg:
+            n = x_lengths.sum()
+            term, l2t, oort = term / n, l2t / n, oort / n
+        objf = base + term
+        objf.totals = objf.totals_all = None
+        objf.bad_count = base.bad_count
+        if hasattr(base, "xent_objf"):
+            objf.xent_objf = base.xent_objf
+        objf.l2_term, objf.out_of_range_term = l2t, oort
+        return objf
+
+    def _forward(self, x, x_lengths, num_graphs, xent_output, reg):
         if self.xent_regularize != 0.0 and xent_output is not None:
-            return self._forward_xent(x, x_lengths, num_graphs, xent_output)
-        if (self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain):
+            return self._forward_xent(x, x_lengths, num_graphs, xent_output, reg)
+        if self._on_kernels(x, num_graphs):
+            if reg is not None:
+                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg, reg)
             return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs,
                                            self.leaky_coefficient, self.avg)
         batch_size = x.size(0)
@@ -400,12 +530,15 @@ class ChainLoss(nn.Module):
         ChainFunction.last_totals = ChainFunction.last_totals_all = None
         return objf
 
-    def _forward_xent(self, x, x_lengths, num_graphs, xent_output):
-        if (self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain):
+    def _forward_xent(self, x, x_lengths, num_graphs, xent_output, reg=None):
+        if self._on_kernels(x, num_graphs):
+            if reg is not None:
+                return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
+                                                   self.leaky_coefficient, self.avg, self.xent_regularize, reg)
             return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
                                                self.leaky_coefficient, self.avg, self.xent_regularize)
         # the unfused route: the loss without xent as it is, and the cross-entropy term through numerator_xent
-        lfmmi = self.forward(x, x_lengths, num_graphs)
+        lfmmi = self._forward(x, x_lengths, num_graphs, None, None)
         xent = numerator_xent(xent_output, x, x_lengths, num_graphs)
         if self.avg:
             xent = xent / x_lengths.sum()

@@ -312,6 +312,83 @@ def cpu_num_xent(graphs, x, lengths, z, with_grad=True, windows=None):
     return res
 
 
+_CLAMP_LIMIT = 30.0        # the kernels' own clamp: the `limit` of the out-of-range penalty (pychain_hip_output_reg)
+
+
+class RegResult(object):
+    """What pychain_hip_output_reg leaves (include/pychain_hip.h): per_seq [B,2] fp32 = {R2_b, RO_b}, totals fp32[3] = [scaled term,
+    sum R2, sum RO], grad [B,T,D] in x's dtype or None (the objective-only form, or the caller's own buffer in ACCUM)."""
+    __slots__ = ("per_seq", "totals", "grad")
+
+
+def output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, with_grad=True, grad_scale=1.0, grad_scale_dev=None,
+               norm_dev=None, loss_scale=1.0, totals=None):
+    """Output L2 and the out-of-range penalty on the GPU (include/pychain_hip.h: pychain_hip_output_reg), on the current stream.
+    `x` goes to the kernel in its own dtype (fp32 / bf16 / fp16).  GRAD_ACCUM: `grad` (x's dtype and shape) += s * term over the
+    live rows; GRAD_LINEAR: a fresh gradient buffer = s * term, zero rows beyond the lengths (`with_grad` False: the objective
+    only).  s = grad_scale [* grad_scale_dev] [/ norm_dev], the two 0-dim device tensors read on the device.  `totals`: the
+    device float[8] of a fused call on this stream - its [0] and [4] get the scaled term added.  Returns a RegResult."""
+    _require_device(x, "nnet_output")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    L = _lib.lib()
+    dev = x.device
+    res = RegResult()
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        if grad_mode == _lib.GRAD_ACCUM:
+            if grad is not None and (grad.dtype != x.dtype or tuple(grad.shape) != (B, T, D) or not grad.is_contiguous()
+                                     or grad.device != dev):
+                raise ValueError("GRAD_ACCUM needs a contiguous gradient of the network output's dtype, shape and device")
+        elif grad_mode == _lib.GRAD_LINEAR:
+            grad = torch.empty_like(x) if with_grad else None
+        else:
+            raise ValueError("output_reg: grad_mode must be GRAD_ACCUM or GRAD_LINEAR")
+        res.per_seq = torch.empty(B, 2, dtype=torch.float32, device=dev)
+        res.totals = torch.empty(3, dtype=torch.float32, device=dev)
+        res.grad = grad
+        if grad_scale_dev is not None:
+            grad_scale_dev = grad_scale_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        if norm_dev is not None:
+            norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        ws = _workspace(L.pychain_hip_output_reg_workspace_bytes(B, T), dev, "outreg")
+        _lib.check(L.pychain_hip_output_reg(
+            x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, float(l2), float(oor), _CLAMP_LIMIT, int(grad_mode),
+            0 if grad is None else grad.data_ptr(), float(grad_scale), 0 if grad_scale_dev is None else grad_scale_dev.data_ptr(),
+            0 if norm_dev is None else norm_dev.data_ptr(), res.per_seq.data_ptr(), float(loss_scale), res.totals.data_ptr(),
+            0 if totals is None else totals.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_output_reg")
+    return res
+
+
+def cpu_output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, with_grad=True, grad_scale=1.0, loss_scale=1.0):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_output_reg), fp32 rows, fp64 sums."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_output_reg is for CPU tensors; device tensors run on the HIP kernels")
+    xf = x.detach().to(torch.float32).contiguous()
+    B, T, D = xf.shape
+    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
+    _check_lengths(lc, B, T)
+    res = RegResult()
+    if grad_mode == _lib.GRAD_ACCUM:
+        if grad is not None and (grad.dtype != torch.float32 or tuple(grad.shape) != (B, T, D) or not grad.is_contiguous()):
+            raise ValueError("GRAD_ACCUM needs a contiguous float32 gradient of the network output's shape")
+    elif grad_mode == _lib.GRAD_LINEAR:
+        grad = torch.empty(B, T, D, dtype=torch.float32) if with_grad else None
+    else:
+        raise ValueError("cpu_output_reg: grad_mode must be GRAD_ACCUM or GRAD_LINEAR")
+    res.per_seq = torch.empty(B, 2, dtype=torch.float32)
+    res.totals = torch.empty(3, dtype=torch.float32)
+    res.grad = grad
+    _lib.check(_lib.lib().pychain_hip_cpu_output_reg(
+        xf.data_ptr(), lc.data_ptr(), B, T, D, float(l2), float(oor), _CLAMP_LIMIT, int(grad_mode),
+        None if grad is None else grad.data_ptr(), float(grad_scale), None, None, res.per_seq.data_ptr(), float(loss_scale),
+        res.totals.data_ptr(), None, int(CPU_THREADS)), "pychain_hip_cpu_output_reg")
+    return res
+
+
 def align(gt, graph_stride, num_states, x, lengths):
     """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
@@ -405,7 +482,7 @@ class ChainLossState(object):
     """What `chain_loss_forward` leaves behind for `chain_loss_backward`: the stored
     trajectories (workspaces) and the handles of everything the occupancy passes read."""
     __slots__ = ("plan", "gt", "graph_stride", "num_states_num", "x", "lengths_dev", "den_ws", "num_ws", "shape",
-                 "grad", "num_compat", "xent")
+                 "grad", "num_compat", "xent", "reg")
 
 
 def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient=1e-5,
@@ -446,7 +523,7 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
         if windows is not None:
             windows = _check_windows(windows, B, int(num_states_num), dev)
             fn, name, tail = L.pychain_hip_chain_loss_forward_tw, "pychain_hip_chain_loss_forward_tw", (windows.data_ptr(),)
-        st.xent = keep = None
+        st.xent = keep = st.reg = None
         if xent is not None:
             z, z_grad, c = xent
             st.xent = XentResult()

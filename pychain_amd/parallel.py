@@ -115,15 +115,20 @@ class ShardedChainLoss(torch.nn.Module):
     `force_collective` asks for the collective anyway (one rank under torch.distributed: the RCCL leg of the GPU tests)."""
 
     def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, group=None, loss_cls=None, force_collective=False,
-                 xent_regularize=0.0):
+                 xent_regularize=0.0, output_l2_regularize=0.0, out_of_range_regularize=0.0):
         super().__init__()
         self._native = loss_cls is None or bool(getattr(loss_cls, "reports_bad_count", False))
         if loss_cls is None:
             from .loss import ChainLoss as loss_cls
         # (the xent term - ChainLoss(xent_regularize=c), forward(..., xent_output=z) - rides in the local loss: the totals of the
         # native call hold the FULL local loss, so the collective below is the same one)
-        self.local = (loss_cls(den_graph, leaky_coefficient, avg=False, xent_regularize=xent_regularize) if xent_regularize
-                      else loss_cls(den_graph, leaky_coefficient, avg=False))
+        # (the output regularisers ride in the local loss the same way: un-averaged, divided by the GLOBAL frame count below)
+        extra = {}
+        if xent_regularize:
+            extra["xent_regularize"] = xent_regularize
+        if output_l2_regularize or out_of_range_regularize:
+            extra.update(output_l2_regularize=output_l2_regularize, out_of_range_regularize=out_of_range_regularize)
+        self.local = loss_cls(den_graph, leaky_coefficient, avg=False, **extra)
         self.avg = avg
         self.group = group
         self.force_collective = bool(force_collective)
