@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 21
+#define PYCHAIN_HIP_ABI_VERSION 22
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -565,6 +565,51 @@ int pychain_hip_cpu_output_reg(
     float l2, float oor, float limit, int grad_mode, float* grad,
     float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
     float* reg_per_seq, float loss_scale, float* reg_totals, float* totals, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Utterance weights and per-frame derivative weights (ABI 22): the two pieces of Kaldi's chain objective that come with a
+ * minibatch - Supervision::weight (u, float [B]) and NnetChainSupervision::deriv_weights (f, float [B,T], --apply-deriv-weights) -
+ * applied behind a call that has left a gradient and its per-sequence objectives on the device.  A missing factor (NULL) is 1;
+ * both NULL: PYCHAIN_HIP_EINVAL (there is nothing to do, and a caller without weights never comes here).
+ * ROWS (`grad` dev [B,T,D] of grad_dtype, or NULL: the sums only), in place, one streaming pass over the live rows; per
+ * (b, t < L_b), w = fl32(u_b * f_bt):
+ *   w == 1   the row is NEITHER READ NOR WRITTEN
+ *   w == 0   the row is stored as +0 WITHOUT A LOAD (a NaN or an infinity in it is gone)
+ *   else     every element is widened to fp32 (exact), multiplied ONCE by w and rounded ONCE, to nearest even, to grad_dtype:
+ *            grad(b,t,d) = round(fl32(w * grad(b,t,d))) - one IEEE multiply, one rounding, the same bits on every run
+ * Rows t >= L_b are NEVER TOUCHED.  The pass moves the bytes of the rows it changes: derivative weights that are 1 except at the
+ * edges of a chunk cost those edge rows.  Any D >= 1: 16-byte accesses where the rows allow (fp32 rows of a multiple of 4
+ * elements, 2-byte rows of a multiple of 8; 8-byte ones for 2-byte rows of a multiple of 4), else element by element.  Weights
+ * are not inspected: a negative or non-finite one is multiplied in as it is.  f scales derivative rows ONLY - neither the
+ * objective nor its normaliser, as in Kaldi - so with f the gradient is deliberately not the gradient of the scalar.
+ * SUMS (`totals` or `weighted` given; den_objf_per_seq and num_objf_per_seq are then required): over the per-sequence arrays
+ * a fused call leaves,
+ *   term_b = den_b - num_b [+ xent_coef * xent_b] [+ 0.5 * l2 * R2_b + oor * RO_b]     (reg_per_seq = {R2_b, RO_b} [B][2]; a
+ *                                                                                       trainer passes xent_coef = -c)
+ * in fp64, ascending b on one thread, no float atomics, each result rounded once.  AN UTTERANCE WITH u_b == 0 IS SKIPPED, not
+ * multiplied: its objective may be -inf or a NaN and contributes exactly 0 to every sum.
+ *   totals    dev float [PYCHAIN_HIP_TOTALS] or NULL, the totals of the fused call on the same stream (behind its xent totals and
+ *             behind pychain_hip_output_reg): totals[0] = totals[4] = loss_scale * sum_b u_b term_b [/ *loss_norm_dev],
+ *             totals[1] = sum_b u_b L_b (the normaliser of an averaged loss: what a sharded trainer all-reduces),
+ *             totals[3] = sum_b u_b (den_b - num_b); totals[2] and totals[5..7] keep their bits.
+ *   weighted  dev float [5] or NULL: {sum u (den - num), sum u xent, sum u R2, sum u RO, sum u L}
+ * The caller passes the loss_norm_dev (or folds 1 / sum_b u_b L_b into the scales) it gave the fused call: the gradient that
+ * call wrote is already divided by it.  Lengths outside [1,T] are clamped, as everywhere.  grad must be 16-byte aligned.  The
+ * entry point is a translation unit of its own (csrc/weights.hip): the objects of den_*.hip, num_*.hip, xent.hip, align.hip
+ * and outreg.hip do not change, and no existing entry point launches anything it did not launch before. */
+int pychain_hip_weight_rows(
+    void* grad, int grad_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const float* utt_weights, const float* deriv_weights,
+    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
+    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
+    float* totals, float* weighted, void* stream);
+/* the host twin: the same on host pointers, fp32 rows, the same single multiply and the same fp64 sums; no stream */
+int pychain_hip_cpu_weight_rows(
+    float* grad, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const float* utt_weights, const float* deriv_weights,
+    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
+    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
+    float* totals, float* weighted, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -1,1 +1,1 @@
-from pychain_amd.loss import ChainFunction, ChainLoss, ChainLossFunction, output_regularizer  # noqa: F401
+from pychain_amd.loss import ChainFunction, ChainLoss, ChainLossFunction, output_regularizer, weight_rows  # noqa: F401

@@ -27,5 +27,5 @@ def _more_hardware_queues():
 _more_hardware_queues()
 
 from .graph import ChainGraph, ChainGraphBatch  # noqa: F401
-from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent, output_regularizer  # noqa: F401
+from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent, output_regularizer, weight_rows  # noqa: F401
 from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401

@@ -19,6 +19,7 @@
 #include "num_kernels.h"
 #include "outreg.h"
 #include "plan_format.h"
+#include "weights.h"
 #include "xent.h"
 
 namespace pychain_hip {
@@ -1117,6 +1118,42 @@ extern "C" int pychain_hip_output_reg(
   hipStream_t st = (hipStream_t)stream;
   hipError_t e = launch_outreg_rows(a, st);
   if (e == hipSuccess && (reg_totals || totals)) e = launch_outreg_totals(a.seq_pairs, B, l2, oor, loss_scale, loss_norm_dev, reg_totals, totals, st);
+  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}
+
+// ---- utterance and derivative weights (include/pychain_hip.h: pychain_hip_weight_rows; weights.hip) ---------------------
+extern "C" int pychain_hip_weight_rows(
+    void* grad, int grad_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const float* utt_weights, const float* deriv_weights,
+    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
+    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
+    float* totals, float* weighted, void* stream) {
+  const char* who = "weight_rows";
+  if (!utt_weights && !deriv_weights) return fail(PYCHAIN_HIP_EINVAL, "%s: neither utt_weights nor deriv_weights", who);
+  if (!seq_lengths) return fail(PYCHAIN_HIP_EINVAL, "%s: null seq_lengths", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (grad && (grad_dtype < PYCHAIN_HIP_F32 || grad_dtype > PYCHAIN_HIP_F16)) return fail(PYCHAIN_HIP_EINVAL, "%s: unknown grad_dtype %d", who, grad_dtype);
+  if ((uintptr_t)grad & 15) return fail(PYCHAIN_HIP_EINVAL, "%s: grad must be 16-byte aligned", who);
+  const bool sums = totals || weighted;
+  if (!grad && !sums) return fail(PYCHAIN_HIP_EINVAL, "%s: nothing to do (no grad, no totals, no weighted)", who);
+  if (sums && (!den_objf_per_seq || !num_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: the sums need den_objf_per_seq and num_objf_per_seq", who);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  if (grad) {
+    WeightRowsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.grad = grad; a.dtype = grad_dtype; a.lengths = seq_lengths; a.u = utt_weights; a.f = deriv_weights; a.B = B; a.T = T; a.D = D;
+    e = launch_weight_rows(a, st);
+  }
+  if (e == hipSuccess && sums) {
+    WeightSumsArgs s;
+    memset(&s, 0, sizeof(s));
+    s.lengths = seq_lengths; s.u = utt_weights; s.den = den_objf_per_seq; s.num = num_objf_per_seq; s.xent = xent_objf_per_seq;
+    s.reg = reg_per_seq; s.xent_coef = xent_coef; s.l2 = l2; s.oor = oor; s.loss_scale = loss_scale; s.norm_dev = loss_norm_dev;
+    s.totals = totals; s.weighted = weighted; s.B = B; s.T = T;
+    e = launch_weight_sums(s, st);
+  }
   if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
 }

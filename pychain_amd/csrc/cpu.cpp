@@ -492,3 +492,55 @@ extern "C" int pychain_hip_cpu_output_reg(
   }
   return PYCHAIN_HIP_OK;
 }
+
+// ---- utterance and derivative weights (include/pychain_hip.h: pychain_hip_weight_rows; the device's weights.hip): the same
+// single fp32 multiply per element, the same fp64 sums in ascending b
+extern "C" int pychain_hip_cpu_weight_rows(
+    float* grad, const int64_t* seq_lengths, int B, int T, int D,
+    const float* utt_weights, const float* deriv_weights,
+    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
+    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
+    float* totals, float* weighted, int num_threads) {
+  const char* who = "cpu_weight_rows";
+  if (!utt_weights && !deriv_weights) return fail(PYCHAIN_HIP_EINVAL, "%s: neither utt_weights nor deriv_weights", who);
+  if (!seq_lengths) return fail(PYCHAIN_HIP_EINVAL, "%s: null seq_lengths", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  const bool sums = totals || weighted;
+  if (!grad && !sums) return fail(PYCHAIN_HIP_EINVAL, "%s: nothing to do (no grad, no totals, no weighted)", who);
+  if (sums && (!den_objf_per_seq || !num_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: the sums need den_objf_per_seq and num_objf_per_seq", who);
+  g_cpu_calls++;
+  auto len = [&](int b) { const int64_t l = seq_lengths[b]; return l < 1 ? 1 : (l > T ? T : (int)l); };
+  if (grad) {
+    for_each_sequence(B, num_threads, [&](int b) {
+      const int L = len(b);
+      const float ub = utt_weights ? utt_weights[b] : 1.f;
+      for (int t = 0; t < L; t++) {
+        const float w = deriv_weights ? ub * deriv_weights[(size_t)b * T + t] : ub;
+        if (w == 1.f) continue;
+        float* g = grad + ((size_t)b * T + t) * D;
+        if (w == 0.f) { for (int n = 0; n < D; n++) g[n] = 0.f; }
+        else { for (int n = 0; n < D; n++) g[n] = g[n] * w; }
+      }
+    });
+  }
+  if (sums) {
+    double lf = 0.0, sx = 0.0, s2 = 0.0, so = 0.0, sl = 0.0;
+    for (int b = 0; b < B; b++) {
+      const float u = utt_weights ? utt_weights[b] : 1.f;
+      if (u == 0.f) continue;                      // skipped, not multiplied: its objective may be -inf or a NaN
+      const double ud = (double)u;
+      lf += ud * ((double)den_objf_per_seq[b] - (double)num_objf_per_seq[b]);
+      if (xent_objf_per_seq) sx += ud * (double)xent_objf_per_seq[b];
+      if (reg_per_seq) { s2 += ud * (double)reg_per_seq[2 * b]; so += ud * (double)reg_per_seq[2 * b + 1]; }
+      sl += ud * (double)len(b);
+    }
+    double v = lf;
+    if (xent_objf_per_seq) v += (double)xent_coef * sx;
+    if (reg_per_seq) v += (l2 != 0.f ? 0.5 * (double)l2 * s2 : 0.0) + (oor != 0.f ? (double)oor * so : 0.0);
+    v *= (double)loss_scale;
+    if (loss_norm_dev) v /= (double)*loss_norm_dev;
+    if (totals) { const float full = (float)v; totals[0] = full; totals[4] = full; totals[1] = (float)sl; totals[3] = (float)lf; }
+    if (weighted) { weighted[0] = (float)lf; weighted[1] = (float)sx; weighted[2] = (float)s2; weighted[3] = (float)so; weighted[4] = (float)sl; }
+  }
+  return PYCHAIN_HIP_OK;
+}

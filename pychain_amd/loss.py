@@ -25,7 +25,7 @@ from . import _lib, _plan, native
 from .graph import ChainGraphBatch
 
 __all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent",
-           "output_regularizer", "ChainLoss"]
+           "output_regularizer", "weight_rows", "ChainLoss"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -40,7 +40,7 @@ class ChainFunction(torch.autograd.Function):
         report = {}
         objf, input_grad, bad = ChainFunction._occupancies(x, input_lengths, graphs, leaky_coefficient, totals=True, report=report)
         return ChainFunction._forward_tail(ctx, input, x, input_lengths, graphs, leaky_coefficient, objf, input_grad, bad,
-                                           report.get("totals"))
+                                           report.get("totals"), report.get("per_seq"))
 
     @staticmethod
     def _occupancies(x, input_lengths, graphs, leaky_coefficient, totals=False, report=None):
@@ -76,7 +76,7 @@ class ChainFunction(torch.autograd.Function):
                 objf, input_grad, bad, tot = native.den_forward_backward(
                     plan, x, input_lengths, leaky_coefficient, input_is_exp=False, totals=True)
                 if report is not None:
-                    report["totals"] = tot
+                    report["totals"], report["per_seq"] = tot, objf
                 objf = native.totals_scalar(tot)   # (no launch; not a view of the statistics)
             else:
                 objf, input_grad, bad = native.den_forward_backward(
@@ -90,7 +90,7 @@ class ChainFunction(torch.autograd.Function):
         return objf, input_grad, bad
 
     @staticmethod
-    def _forward_tail(ctx, input, x, input_lengths, graphs, leaky_coefficient, objf, input_grad, bad, tot=None):
+    def _forward_tail(ctx, input, x, input_lengths, graphs, leaky_coefficient, objf, input_grad, bad, tot=None, per_seq=None):
         # The occupancies are the gradient for an upstream gradient of 1.  backward() scales the
         # buffer in place on the device (a no-op launch when the upstream gradient is exactly 1,
         # i.e. `objf.backward()`) and hands it to autograd, instead of the reference's extra
@@ -107,6 +107,8 @@ class ChainFunction(torch.autograd.Function):
         ctx.in_dtype = input.dtype   # fp16 / bf16 inputs are evaluated in fp32; the gradient goes back in their dtype
         ctx.bad_count = bad          # device int32[1]; the reference's `ok`, never synced here
         out = objf.sum() if objf.dim() else objf               # (0-dim: the sum came with the call)
+        # (internal: the [B] objectives the sum was taken over - what ChainLoss weights an unfused call's value with)
+        out._objf_per_seq = objf if objf.dim() else per_seq
         return _attach(out, tot, bad)
 
     retain_grad_buffer = False
@@ -197,6 +199,131 @@ def _attach_reg(out, res, reg, host_scale, dev_norm):
     return out
 
 
+def _check_weights(utt_weights, deriv_weights, B, T, avg):
+    """(u float32 [B] or None, f float32 [B,T] or None), each where it was given.  Weights on the host are inspected - negative or
+    non-finite ones, and utterance weights that are all zero under `avg`, raise -; weights on the device are not (no sync)."""
+    out = []
+    for w, shape, what in ((utt_weights, (B,), "utt_weights"), (deriv_weights, (B, T), "deriv_weights")):
+        if w is not None:
+            w = torch.as_tensor(w).detach()
+            if w.dtype != torch.float32:
+                w = w.to(torch.float32)
+            if tuple(w.shape) != shape:
+                raise ValueError("%s must have shape %s, got %s" % (what, list(shape), list(w.shape)))
+            if not w.is_cuda:
+                if not bool(torch.isfinite(w).all()) or bool((w < 0).any()):
+                    raise ValueError("%s must be finite and not negative" % what)
+                if avg and what == "utt_weights" and not bool((w != 0).any()):
+                    raise ValueError("utt_weights are all zero: an averaged loss would divide by zero weighted frames")
+        out.append(w)
+    return tuple(out)
+
+
+def _normaliser(avg, lengths, u=None):
+    """(host scale, device normaliser) of a fused call: avg=True divides by N = the frame count (loss.py:103-104), or sum_b u_b
+    L_b under utterance weights - a host scalar when everything it is made of lives on the host, else a device scalar; never a
+    sync."""
+    if not avg:
+        return 1.0, None
+    if u is None:
+        if lengths.is_cuda:
+            return 1.0, lengths.sum().to(torch.float32)
+        return 1.0 / float(lengths.sum()), None
+    if lengths.is_cuda or u.is_cuda:
+        dev = u.device if u.is_cuda else lengths.device
+        return 1.0, (u.to(dev).double() * lengths.to(dev)).sum().to(torch.float32)
+    return 1.0 / float((u.double() * lengths).sum()), None
+
+
+def _with_weights(result, wts, reg, c, speculative, dev_norm, loss_scale):
+    """`result` of native.chain_loss_forward (with the regularisers' pass behind it, where there is one) under the weights `wts` =
+    (u, f, ...), both on the call's device: native.weight_rows on the current stream - over the gradient the call wrote (speculative mode), over the xent
+    branch's gradient, and, with utterance weights, the weighted sums into the call's totals.  state.weighted: the float[5]."""
+    den_objf, num_objf, _, state, totals = result
+    u, f = wts[:2]
+    xe, rg = state.xent, state.reg
+    if u is not None:
+        l2, oor = reg if reg is not None else (0.0, 0.0)
+        state.weighted = native.weight_rows(
+            state.grad if speculative else None, state.lengths_dev, u, f, shape=state.shape[:3], den_objf=den_objf, num_objf=num_objf,
+            xent_objf=None if xe is None else xe.objf, xent_coef=-c, reg_per_seq=None if rg is None else rg.per_seq, l2=l2, oor=oor,
+            loss_scale=loss_scale, norm_dev=dev_norm, totals=totals)
+    elif speculative:
+        native.weight_rows(state.grad, state.lengths_dev, None, f)
+    if xe is not None and xe.grad is not None:
+        native.weight_rows(xe.grad, state.lengths_dev, u, f)
+    return result
+
+
+def _attach_weighted(out, state, totals, reg, host_scale, dev_norm):
+    """`out.weighted_frames` = sum_b u_b L_b, and - under utterance weights - `out.xent_objf`, `out.l2_term`,
+    `out.out_of_range_term` as the weighted amounts (detached, for logging)."""
+    w = state.weighted
+    if w is None:                                        # derivative weights only: they change no sum
+        out.weighted_frames = totals[1]
+        return out
+    scaled = lambda t: t * host_scale if dev_norm is None else t * host_scale / dev_norm.to(t.device)
+    out.weighted_frames = w[4]
+    if state.xent is not None:
+        out.xent_objf = scaled(w[1])
+    if reg is not None:
+        out.l2_term, out.out_of_range_term = scaled((0.5 * reg[0]) * w[2]), scaled(reg[1] * w[3])
+    return out
+
+
+class WeightRowsFunction(torch.autograd.Function):
+    """Identity in forward; backward scales the rows of the incoming gradient by w(b,t) = u_b * f_bt over the live frames
+    (include/pychain_hip.h: pychain_hip_weight_rows): device tensors on the HIP kernel, CPU tensors on the host twin."""
+
+    @staticmethod
+    def forward(ctx, input, lengths, u, f):
+        ctx.lengths, ctx.u, ctx.f = lengths, u, f
+        return input.view_as(input)
+
+    @staticmethod
+    def backward(ctx, g):
+        if g.is_cuda:
+            g = g.clone(memory_format=torch.contiguous_format)     # (autograd's buffer is not ours to write into)
+            native.weight_rows(g, ctx.lengths, ctx.u, ctx.f)
+            return g, None, None, None
+        gf = g.to(torch.float32).clone(memory_format=torch.contiguous_format)
+        native.cpu_weight_rows(gf, ctx.lengths, ctx.u, ctx.f)
+        return gf.to(g.dtype), None, None, None
+
+
+def weight_rows(x, weights, lengths=None):
+    """x [B,T,D] unchanged in forward; in backward the rows of its gradient are scaled by `weights`: a [B] tensor (one weight per
+    utterance), a [B,T] tensor (one per frame), or a pair (utterance weights, frame weights) - the row weight is then their fp32
+    product, applied with ONE multiply.  Rows of weight 1 are not touched, rows of weight 0 are written as zeros without being
+    read, rows t >= lengths[b] are left alone (`lengths` None: every frame is live).  The building block of ChainLoss's
+    utt_weights / deriv_weights on the unfused route, and what a loss of one's own would call."""
+    B, T = x.size(0), x.size(1)
+    if isinstance(weights, (tuple, list)):
+        u, f = weights
+    else:
+        weights = torch.as_tensor(weights)
+        u, f = (weights, None) if weights.dim() == 1 else (None, weights)
+    u, f = _check_weights(u, f, B, T, False)
+    if u is None and f is None:
+        raise ValueError("weight_rows: no weights given")
+    if lengths is None:
+        lengths = torch.full((B,), T, dtype=torch.int64)
+    return WeightRowsFunction.apply(x, torch.as_tensor(lengths), u, f)
+
+
+class _ValueOf(torch.autograd.Function):
+    """value: `value` (detached); gradient: that of `local` (parallel.py's local - local.detach() + value, without the
+    subtraction: a local loss that is not finite - an utterance of weight zero may make it so - must not make the value a NaN)."""
+
+    @staticmethod
+    def forward(ctx, local, value):
+        return value.detach().to(local.dtype).clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
 class ChainLossFunction(torch.autograd.Function):
     """Denominator + numerator in one pass, split at the autograd
     boundary: forward runs the four recursions (numerator on a side stream) and returns the
@@ -206,7 +333,7 @@ class ChainLossFunction(torch.autograd.Function):
     (loss.py:85,100-104).  Same numbers as the two-call path."""
 
     @staticmethod
-    def forward(ctx, input, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, reg=None):
+    def forward(ctx, input, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, reg=None, wts=None):
         x = input.detach()
         B, D = x.size(0), x.size(2)
         if B != num_graphs.batch_size:
@@ -222,7 +349,9 @@ class ChainLossFunction(torch.autograd.Function):
         # avg=True divides by the frame count (loss.py:103-104): a host scalar when the lengths
         # live on the host, else a device scalar - never a sync
         ctx.host_scale, ctx.dev_norm = 1.0, None
-        if avg:
+        if wts is not None:
+            ctx.host_scale, ctx.dev_norm = _normaliser(avg, lengths, wts[2])
+        elif avg:
             if lengths.is_cuda:
                 ctx.dev_norm = lengths.sum().to(torch.float32)
             else:
@@ -234,7 +363,20 @@ class ChainLossFunction(torch.autograd.Function):
         # (2-byte network outputs go to the kernels as they are when the gradient is written here, or never)
         half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
         spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closures must not hold ctx)
-        if reg is None:
+        if wts is not None:
+            # utterance / derivative weights: one more pass on the same stream behind the fused call and behind the regularisers'
+            # pass, over the whole batch (after the last slice of a call in slices) - the rows of the gradient the call wrote
+            # (speculative), and the weighted sums into its totals
+            def evaluate(loss_scale):
+                r = native.chain_loss_forward(
+                    plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+                    with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw)
+                if reg is not None:
+                    r = _with_output_reg(r, reg, spec, hscale, dnorm, loss_scale)
+                return _with_weights(r, wts, reg, 0.0, spec, dnorm, loss_scale)
+            den_objf, num_objf, bad, state, totals = evaluate(hscale)
+            ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
+        elif reg is None:
             den_objf, num_objf, bad, state, totals = native.chain_loss_forward(
                 plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
                 with_grad=ctx.speculative, grad_scale=ctx.host_scale, loss_scale=ctx.host_scale, norm_dev=ctx.dev_norm,
@@ -252,14 +394,15 @@ class ChainLossFunction(torch.autograd.Function):
                 reg, spec, hscale, dnorm, loss_scale)
             den_objf, num_objf, bad, state, totals = evaluate(hscale)
             ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
-        ctx.reg = reg
+        ctx.reg, ctx.wts = reg, wts
         # -(num - den) [/ frames], loss.py:100-104, comes with the call (the last workgroup of its last kernel adds the
         # per-sequence objectives up): no reduction / subtraction / scaling launches behind it
         objf = native.totals_scalar(totals)    # (no launch; not a view of the statistics: `loss /= n` works)
         ctx.state = state
         ctx.in_dtype = input.dtype
         ctx.bad_count = bad                      # int32[2]: denominator, numerator; never synced here
-        return _attach_reg(_attach(objf, totals, bad), state.reg, reg, hscale, dnorm)
+        out = _attach_reg(_attach(objf, totals, bad), state.reg, reg, hscale, dnorm)
+        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
 
     overlap = True     # class-level switch: False = occupancy passes run in backward (no speculation)
 
@@ -277,11 +420,13 @@ class ChainLossFunction(torch.autograd.Function):
             g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
             grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
             _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
+            if ctx.wts is not None:
+                native.weight_rows(grad, state.lengths_dev, ctx.wts[0], ctx.wts[1])
             ctx.bad_count = ctx.bad_count + bad              # (the occupancy launches' own checks)
             ChainFunction.last_bad_count = ctx.bad_count
         state.grad = None         # the stored trajectories go with `state`
         state.den_ws = state.num_ws = None
-        return grad.to(ctx.in_dtype), None, None, None, None, None, None
+        return grad.to(ctx.in_dtype), None, None, None, None, None, None, None
 
 
 class NumeratorXentFunction(torch.autograd.Function):
@@ -352,6 +497,7 @@ class OutputRegFunction(torch.autograd.Function):
         ctx.in_dtype = input.dtype
         out = res.totals[0].clone()
         out.l2_term, out.out_of_range_term = (0.5 * l2) * res.totals[1], oor * res.totals[2]
+        out._reg_per_seq = res.per_seq                     # (internal: {R2_b, RO_b} [B,2], what ChainLoss weights the terms with)
         return out
 
     @staticmethod
@@ -385,7 +531,8 @@ class ChainLossXentFunction(torch.autograd.Function):
     ChainLossFunction's, bit for bit: nothing flows back to it through the posteriors."""
 
     @staticmethod
-    def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize, reg=None):
+    def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize, reg=None,
+                wts=None):
         x = input.detach()
         B, D = x.size(0), x.size(2)
         if B != num_graphs.batch_size:
@@ -398,7 +545,9 @@ class ChainLossXentFunction(torch.autograd.Function):
         gstride = 0 if num_graphs.shared_graph is not None else 1
         tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
         ctx.host_scale, ctx.dev_norm = 1.0, None
-        if avg:
+        if wts is not None:
+            ctx.host_scale, ctx.dev_norm = _normaliser(avg, lengths, wts[2])
+        elif avg:
             if lengths.is_cuda:
                 ctx.dev_norm = lengths.sum().to(torch.float32)
             else:
@@ -414,7 +563,11 @@ class ChainLossXentFunction(torch.autograd.Function):
             xent=(z, z_grad, c))
         # (the output regularisers: behind the call and behind its xent totals, on the same stream)
         evaluate = fused if reg is None else (lambda loss_scale: _with_output_reg(fused(loss_scale), reg, spec, hscale, dnorm, loss_scale))
-        ctx.reg = reg
+        if wts is not None:
+            # (the weights: behind all of that, over the chain output's gradient and over the xent branch's - native.weight_rows)
+            unweighted = evaluate
+            evaluate = lambda loss_scale: _with_weights(unweighted(loss_scale), wts, reg, c, spec, dnorm, loss_scale)
+        ctx.reg, ctx.wts = reg, wts
         den_objf, num_objf, bad, state, totals = evaluate(hscale)
         objf = native.totals_scalar(totals)                 # the full loss: LF-MMI - c * xent [/ frames]
         ctx.state = state
@@ -425,7 +578,8 @@ class ChainLossXentFunction(torch.autograd.Function):
         out = _attach(objf, totals, bad)
         out.xent_objf = state.xent.totals[0]                # sum_b xent_objf[b] [/ frames]: detached, for logging
         out.xent_objf_per_seq = state.xent.objf
-        return _attach_reg(out, state.reg, reg, hscale, dnorm)
+        out = _attach_reg(out, state.reg, reg, hscale, dnorm)
+        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
 
     @staticmethod
     def backward(ctx, objf_grad):
@@ -444,6 +598,8 @@ class ChainLossXentFunction(torch.autograd.Function):
                 g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
                 grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
                 _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
+                if ctx.wts is not None:
+                    native.weight_rows(grad, state.lengths_dev, ctx.wts[0], ctx.wts[1])
                 ctx.bad_count = ctx.bad_count + bad
                 ChainFunction.last_bad_count = ctx.bad_count
             grad = grad.to(ctx.in_dtype)
@@ -452,7 +608,7 @@ class ChainLossXentFunction(torch.autograd.Function):
             zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
         state.grad = state.xent = None
         state.den_ws = state.num_ws = None
-        return grad, zgrad, None, None, None, None, None, None, None
+        return grad, zgrad, None, None, None, None, None, None, None, None
 
 
 class ChainLoss(nn.Module):
@@ -486,18 +642,46 @@ class ChainLoss(nn.Module):
     def _on_kernels(self, x, num_graphs):
         return self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain
 
-    def forward(self, x, x_lengths, num_graphs, xent_output=None):
+    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None):
+        """`utt_weights` u (float [B]; Kaldi: Supervision::weight) scale each utterance's objective, its derivatives and the
+        normaliser: loss = sum_b u_b term_b / N with N = sum_b u_b L_b under avg=True (else 1), term_b the utterance's whole
+        objective (LF-MMI, the xent term and the regularisers that are switched on).  An utterance with u_b == 0 contributes
+        exactly 0 even where its own objective is -inf or a NaN (`utt_weights=viterbi_align(...).ok.float()` drops the
+        utterances that do not align).  `deriv_weights` f (float [B,T]; Kaldi: --apply-deriv-weights) scale the derivative rows
+        ONLY: they change neither the loss nor N, so WITH THEM THE GRADIENT IS DELIBERATELY NOT THE GRADIENT OF THE RETURNED
+        SCALAR.  x.grad(b,t,:) - and the xent output's - is w(b,t) = u_b * f_bt times what the same call with the same N writes
+        without weights: rows of weight 1 are not touched, rows of weight 0 are written as zeros without being read (a NaN in
+        them is gone), the others get one multiply and one rounding (native.weight_rows, one pass behind the fused call).
+        Where a bf16 / fp16 network output is up-cast for the call (rows that are no multiple of 8 pdfs, overlap = False, the
+        unfused route) the call's gradient is fp32 until it is handed back: the weights multiply THAT, and the product is
+        rounded to the output's dtype once - not the rounded 2-byte gradient a second time.
+        Other dtypes are converted to float32; weights on the host that are negative or not finite raise, as do utterance
+        weights that are all zero under avg=True; weights on the device are not inspected.  `loss.weighted_frames` is
+        sum_b u_b L_b; `loss.totals[1]` holds it too, `loss.totals[3]` sum_b u_b (den_b - num_b), and `loss.xent_objf`,
+        `loss.l2_term`, `loss.out_of_range_term` become the weighted amounts.  Both None: exactly the call without them."""
         reg = self._reg()
+        if utt_weights is not None or deriv_weights is not None:
+            wts = _check_weights(utt_weights, deriv_weights, x.size(0), x.size(1), self.avg)
+            if self._on_kernels(x, num_graphs):
+                # (uploaded once for every pass of the step; the utterance weights as they were given ride along: a host
+                # normaliser is made of them)
+                dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
+                return self._forward(x, x_lengths, num_graphs, xent_output, reg, wts=(dev(wts[0]), dev(wts[1]), wts[0]))
+            return self._forward_weighted(x, x_lengths, num_graphs, xent_output, reg, wts)
         if reg is None or self._on_kernels(x, num_graphs):
             return self._forward(x, x_lengths, num_graphs, xent_output, reg)
+        return self._forward_reg(x, x_lengths, num_graphs, xent_output, reg)
+
+    def _forward_reg(self, x, x_lengths, num_graphs, xent_output, reg, avg=None):
+        avg = self.avg if avg is None else avg
         # the unfused route and CPU tensors: the loss without the terms as it is, and the terms through output_regularizer
         # (the loss without the terms reads x through a view of its own: its calls' gradients are added up at that view, as
         # ChainLoss without the terms adds them, and x receives exactly two gradients - that sum and the term.  A sum of two
         # does not depend on which arrives first: x.grad is (the gradient without the terms) + the term, rounded once more)
-        base = self._forward(x.view_as(x), x_lengths, num_graphs, xent_output, None)
+        base = self._forward(x.view_as(x), x_lengths, num_graphs, xent_output, None, avg=avg)
         term = output_regularizer(x, x_lengths, reg[0], reg[1])
-        l2t, oort = term.l2_term, term.out_of_range_term
-        if self.avg:
+        l2t, oort, per_seq = term.l2_term, term.out_of_range_term, term._reg_per_seq
+        if avg:
             n = x_lengths.sum()
             term, l2t, oort = term / n, l2t / n, oort / n
         objf = base + term
@@ -506,44 +690,97 @@ class ChainLoss(nn.Module):
         if hasattr(base, "xent_objf"):
             objf.xent_objf = base.xent_objf
         objf.l2_term, objf.out_of_range_term = l2t, oort
+        objf._per_seq = dict(base._per_seq, reg=per_seq)
         return objf
 
-    def _forward(self, x, x_lengths, num_graphs, xent_output, reg):
+    def _forward_weighted(self, x, x_lengths, num_graphs, xent_output, reg, wts):
+        """The unfused route and CPU tensors under weights: the gradient comes from the loss as it is, un-averaged, evaluated on
+        weight_rows(x, w) - its backward scales the rows, once, after autograd has added the calls' gradients up -, divided by N;
+        the value is replaced by the weighted sum of the per-sequence objectives the calls leave (fp64, rounded once)."""
+        u, f = wts
+        lengths = torch.as_tensor(x_lengths)
+        xw = WeightRowsFunction.apply(x, lengths, u, f)
+        with_xent = self.xent_regularize != 0.0 and xent_output is not None
+        zw = WeightRowsFunction.apply(xent_output, lengths, u, f) if with_xent else None
+        if u is None:
+            # derivative weights only: neither the loss nor N changes - today's call, its gradient rows scaled
+            local = (self._forward(xw, x_lengths, num_graphs, zw, None) if reg is None
+                     else self._forward_reg(xw, x_lengths, num_graphs, zw, reg))
+            local.weighted_frames = lengths.sum()
+            return local
+        local = (self._forward(xw, x_lengths, num_graphs, zw, None, avg=False) if reg is None
+                 else self._forward_reg(xw, x_lengths, num_graphs, zw, reg, avg=False))
+        per, bad = local._per_seq, local.bad_count
+        dev = per["den"].device
+        ud, live = u.to(dev).double(), u.to(dev) != 0
+        total = lambda t: torch.where(live, ud * t.to(dev).double(), torch.zeros_like(ud)).sum()     # (weight 0: skipped, not multiplied)
+        frames = (ud * lengths.to(dev)).sum()
+        n = frames if self.avg else torch.ones_like(frames)
+        value = total(per["den"] - per["num"])
+        if with_xent:
+            sx = total(per["xent"])
+            value = value - self.xent_regularize * sx
+        if reg is not None:
+            s2, so = total(per["reg"][:, 0]), total(per["reg"][:, 1])
+            value = value + 0.5 * reg[0] * s2 + reg[1] * so
+        if self.avg:
+            local = local / frames.to(torch.float32)
+        objf = _ValueOf.apply(local, (value / n).to(torch.float32))
+        objf.totals = objf.totals_all = None
+        objf.bad_count = bad
+        objf.weighted_frames = frames.to(torch.float32)
+        if with_xent:
+            objf.xent_objf = (sx / n).to(torch.float32)
+        if reg is not None:
+            objf.l2_term, objf.out_of_range_term = (0.5 * reg[0] * s2 / n).to(torch.float32), (reg[1] * so / n).to(torch.float32)
+        return objf
+
+    def _forward(self, x, x_lengths, num_graphs, xent_output, reg, avg=None, wts=None):
+        avg = self.avg if avg is None else avg
         if self.xent_regularize != 0.0 and xent_output is not None:
-            return self._forward_xent(x, x_lengths, num_graphs, xent_output, reg)
+            return self._forward_xent(x, x_lengths, num_graphs, xent_output, reg, avg, wts)
         if self._on_kernels(x, num_graphs):
+            if wts is not None:
+                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, avg, reg, wts)
             if reg is not None:
-                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg, reg)
+                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, avg, reg)
             return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs,
-                                           self.leaky_coefficient, self.avg)
+                                           self.leaky_coefficient, avg)
         batch_size = x.size(0)
         den_graphs = ChainGraphBatch(self.den_graph, batch_size)
         den_objf = ChainFunction.apply(x, x_lengths, den_graphs, self.leaky_coefficient)
         num_objf = ChainFunction.apply(x, x_lengths, num_graphs)
         objf = -(num_objf - den_objf)
-        if self.avg:
+        if avg:
             objf = objf / x_lengths.sum()
         # (two native calls made this loss: neither's totals are the step's - ShardedChainLoss finds none and all-reduces its own
         # three scalars; the two bad counts ride along as they are: no launch here)
         objf.totals = objf.totals_all = None
         objf.bad_count = (den_objf.bad_count, num_objf.bad_count)
+        objf._per_seq = dict(den=den_objf._objf_per_seq, num=num_objf._objf_per_seq)    # (internal: _forward_weighted)
         ChainFunction.last_totals = ChainFunction.last_totals_all = None
         return objf
 
-    def _forward_xent(self, x, x_lengths, num_graphs, xent_output, reg=None):
+    def _forward_xent(self, x, x_lengths, num_graphs, xent_output, reg=None, avg=None, wts=None):
+        avg = self.avg if avg is None else avg
         if self._on_kernels(x, num_graphs):
+            if wts is not None:
+                return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
+                                                   self.leaky_coefficient, avg, self.xent_regularize, reg, wts)
             if reg is not None:
                 return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
-                                                   self.leaky_coefficient, self.avg, self.xent_regularize, reg)
+                                                   self.leaky_coefficient, avg, self.xent_regularize, reg)
             return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
-                                               self.leaky_coefficient, self.avg, self.xent_regularize)
+                                               self.leaky_coefficient, avg, self.xent_regularize)
         # the unfused route: the loss without xent as it is, and the cross-entropy term through numerator_xent
-        lfmmi = self._forward(x, x_lengths, num_graphs, None, None)
+        lfmmi = self._forward(x, x_lengths, num_graphs, None, None, avg=avg)
         xent = numerator_xent(xent_output, x, x_lengths, num_graphs)
-        if self.avg:
+        per_seq = xent.xent_objf_per_seq
+        if avg:
             xent = xent / x_lengths.sum()
         objf = lfmmi - self.xent_regularize * xent
         objf.totals = objf.totals_all = None
         objf.bad_count = lfmmi.bad_count
         objf.xent_objf = xent.detach()
+        objf._per_seq = dict(lfmmi._per_seq, xent=per_seq)
         return objf

@@ -389,6 +389,80 @@ def cpu_output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, w
     return res
 
 
+def _weight_args(u, f, B, T, device):
+    """The float32 [B] / [B,T] weights an entry point reads, on `device` (None stays None)."""
+    if u is None and f is None:
+        raise ValueError("weight_rows: neither utterance weights nor derivative weights (a caller without weights makes no call)")
+    if u is not None:
+        u = u.detach().to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+        if tuple(u.shape) != (B,):
+            raise ValueError("utterance weights must have shape [%d], got %s" % (B, tuple(u.shape)))
+    if f is not None:
+        f = f.detach().to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+        if tuple(f.shape) != (B, T):
+            raise ValueError("derivative weights must have shape [%d, %d], got %s" % (B, T, tuple(f.shape)))
+    return u, f
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=None, den_objf=None, num_objf=None, xent_objf=None,
+                xent_coef=0.0, reg_per_seq=None, l2=0.0, oor=0.0, loss_scale=1.0, norm_dev=None, totals=None):
+    """Utterance weights u [B] and derivative weights f [B,T] on the GPU (include/pychain_hip.h: pychain_hip_weight_rows), on the
+    current stream.  `grad` ([B,T,D], fp32 / bf16 / fp16, contiguous) is scaled IN PLACE: per live row, w = u_b * f_bt; w == 1
+    rows are not touched, w == 0 rows are stored as zeros without a load, the others get one multiply and one rounding.  `grad`
+    None (`shape` = (B, T, D) then): the sums only.  `den_objf` / `num_objf` given: the weighted sums over the per-sequence
+    arrays of a fused call - into `totals` (its device float[8]: [0] = [4] = the weighted loss, [1] = sum u L, [3] = sum u
+    (den - num)) - and the returned float[5] {sum u (den - num), sum u xent, sum u R2, sum u RO, sum u L}; else None."""
+    if grad is not None:
+        _require_device(grad, "grad")
+        if grad.dtype not in _DTYPE_CODE or grad.dim() != 3 or not grad.is_contiguous():
+            raise ValueError("weight_rows: grad must be a contiguous [B,T,D] float32, bfloat16 or float16 tensor")
+        shape = tuple(grad.shape)
+    B, T, D = shape
+    dev = grad.device if grad is not None else den_objf.device
+    _check_lengths(lengths, B, T)
+    weighted = None
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        u, f = _weight_args(utt_weights, deriv_weights, B, T, dev)
+        if den_objf is not None:
+            weighted = torch.empty(5, dtype=torch.float32, device=dev)
+        if norm_dev is not None:
+            norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        _lib.check(_lib.lib().pychain_hip_weight_rows(
+            _ptr(grad), _DTYPE_CODE[grad.dtype] if grad is not None else _lib.F32, ld.data_ptr(), B, T, D, _ptr(u), _ptr(f),
+            _ptr(den_objf), _ptr(num_objf), _ptr(xent_objf), float(xent_coef), _ptr(reg_per_seq), float(l2), float(oor),
+            float(loss_scale), _ptr(norm_dev), _ptr(totals), _ptr(weighted), _stream(dev)), "pychain_hip_weight_rows")
+    return weighted
+
+
+def cpu_weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=None, den_objf=None, num_objf=None, xent_objf=None,
+                    xent_coef=0.0, reg_per_seq=None, l2=0.0, oor=0.0, loss_scale=1.0, norm=None, totals=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_weight_rows), a contiguous float32 `grad` scaled in place, the
+    same single multiply and fp64 sums.  `norm`: None or a float32 tensor of one element the loss is divided by."""
+    if grad is not None:
+        if grad.is_cuda:
+            raise RuntimeError("pychain_amd: cpu_weight_rows is for CPU tensors; device tensors run on the HIP kernels")
+        if grad.dtype != torch.float32 or grad.dim() != 3 or not grad.is_contiguous():
+            raise ValueError("cpu_weight_rows: grad must be a contiguous [B,T,D] float32 tensor")
+        shape = tuple(grad.shape)
+    B, T, D = shape
+    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
+    _check_lengths(lc, B, T)
+    u, f = _weight_args(utt_weights, deriv_weights, B, T, torch.device("cpu"))
+    cf = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
+    den_objf, num_objf, xent_objf, reg_per_seq, norm = cf(den_objf), cf(num_objf), cf(xent_objf), cf(reg_per_seq), cf(norm)
+    weighted = torch.empty(5, dtype=torch.float32) if den_objf is not None else None
+    _lib.check(_lib.lib().pychain_hip_cpu_weight_rows(
+        _ptr(grad), lc.data_ptr(), B, T, D, _ptr(u), _ptr(f), _ptr(den_objf), _ptr(num_objf), _ptr(xent_objf), float(xent_coef),
+        _ptr(reg_per_seq), float(l2), float(oor), float(loss_scale), _ptr(norm), _ptr(totals), _ptr(weighted), int(CPU_THREADS)),
+        "pychain_hip_cpu_weight_rows")
+    return weighted
+
+
 def align(gt, graph_stride, num_states, x, lengths):
     """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
@@ -482,7 +556,7 @@ class ChainLossState(object):
     """What `chain_loss_forward` leaves behind for `chain_loss_backward`: the stored
     trajectories (workspaces) and the handles of everything the occupancy passes read."""
     __slots__ = ("plan", "gt", "graph_stride", "num_states_num", "x", "lengths_dev", "den_ws", "num_ws", "shape",
-                 "grad", "num_compat", "xent", "reg")
+                 "grad", "num_compat", "xent", "reg", "weighted")
 
 
 def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient=1e-5,
@@ -523,7 +597,7 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
         if windows is not None:
             windows = _check_windows(windows, B, int(num_states_num), dev)
             fn, name, tail = L.pychain_hip_chain_loss_forward_tw, "pychain_hip_chain_loss_forward_tw", (windows.data_ptr(),)
-        st.xent = keep = st.reg = None
+        st.xent = keep = st.reg = st.weighted = None
         if xent is not None:
             z, z_grad, c = xent
             st.xent = XentResult()

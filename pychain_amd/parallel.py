@@ -137,12 +137,24 @@ class ShardedChainLoss(torch.nn.Module):
     def _world(self):
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
-    def forward(self, x, x_lengths, num_graphs, xent_output=None):
+    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None):
+        """`utt_weights` [B_local] / `deriv_weights` [B_local, T]: this rank's rows of ChainLoss.forward's weights (shard_batch
+        returns the indices to take them by).  The global normaliser of an averaged loss is then the all-reduced sum_b u_b L_b.
+        Host utterance weights that are all zero under avg=True raise where this rank is the whole world; across ranks the sum
+        is only known after the collective, and a global sum of zero gives a NaN loss."""
+        collective = dist.is_available() and dist.is_initialized() and (self._world() > 1 or self.force_collective)
+        if self.avg and utt_weights is not None and not collective:
+            # (the local loss is un-averaged and does not look; with other ranks the global sum is what counts and is not known here)
+            uw = torch.as_tensor(utt_weights)
+            if not uw.is_cuda and not bool((uw != 0).any()):
+                raise ValueError("utt_weights are all zero: an averaged loss would divide by zero weighted frames")
         # sum over local utterances
-        local = self.local(x, x_lengths, num_graphs) if xent_output is None else self.local(x, x_lengths, num_graphs, xent_output)
+        if utt_weights is not None or deriv_weights is not None:
+            local = self.local(x, x_lengths, num_graphs, xent_output, utt_weights=utt_weights, deriv_weights=deriv_weights)
+        else:
+            local = self.local(x, x_lengths, num_graphs) if xent_output is None else self.local(x, x_lengths, num_graphs, xent_output)
         # [loss, frames, bad, ...] of THIS call, on the device: they came back with the tensor (pychain_amd/loss.py: _attach)
         totals = getattr(local, "totals", None) if self._native else None
-        collective = dist.is_available() and dist.is_initialized() and (self._world() > 1 or self.force_collective)
         if totals is not None:
             if not collective:
                 self.last_stats = totals[:3]
@@ -152,6 +164,8 @@ class ShardedChainLoss(torch.nn.Module):
             self.last_stats = stats
             return _GlobalLoss.apply(local, stats, self.avg)
         frames = torch.as_tensor(x_lengths).sum()
+        if utt_weights is not None and self._native:
+            frames = local.weighted_frames                            # sum_b u_b L_b of this shard
         bad = getattr(local, "bad_count", None) if self._native else None   # the reference's `ok` of every rank rides along
         if isinstance(bad, (tuple, list)):                            # (a two-call loss: denominator's and numerator's)
             bad = torch.cat([b.reshape(-1) for b in bad if b is not None]) if any(b is not None for b in bad) else None
