@@ -103,9 +103,8 @@ class ChainFunction(torch.autograd.Function):
         else:
             ctx.grad_buf = input_grad
             ctx.again = _recompute(x, lambda: ChainFunction._occupancies(x, input_lengths, graphs, leaky_coefficient),
-                                   lambda r: (r[1], r[2]))
+                                   ChainFunction._grad_again)
         ctx.in_dtype = input.dtype   # fp16 / bf16 inputs are evaluated in fp32; the gradient goes back in their dtype
-        ctx.bad_count = bad          # device int32[1]; the reference's `ok`, never synced here
         out = objf.sum() if objf.dim() else objf               # (0-dim: the sum came with the call)
         # (internal: the [B] objectives the sum was taken over - what ChainLoss weights an unfused call's value with)
         out._objf_per_seq = objf if objf.dim() else per_seq
@@ -119,18 +118,18 @@ class ChainFunction(torch.autograd.Function):
     last_bad_count = None
 
     @staticmethod
+    def _grad_again(result):
+        """(of a re-evaluation's (objf, occupancies, bad_count): the occupancies; the bad count goes to the deprecated mirror)"""
+        ChainFunction.last_bad_count = result[2]
+        return result[1]
+
+    @staticmethod
     def backward(ctx, objf_grad):
         # clamp is inside the Function and therefore not differentiated (loss.py:30,82-87)
         if ctx.saved_tensors:
             input_grad, = ctx.saved_tensors
             return torch.mul(input_grad, objf_grad).to(ctx.in_dtype), None, None, None
-        grad = _take_grad_buffer(ctx, "grad_buf")
-        if grad is None:
-            grad, ctx.bad_count = ctx.again()                  # second backward over a retained graph: evaluate again
-            ChainFunction.last_bad_count = ctx.bad_count
-        if not grad.is_cuda:
-            return torch.mul(grad, objf_grad).to(ctx.in_dtype), None, None, None          # (loss.py:85, as it is)
-        return native.rescale_(grad, objf_grad).to(ctx.in_dtype), None, None, None
+        return _grad_written_in_forward(ctx, objf_grad), None, None, None
 
 
 def _attach(out, totals, bad):
@@ -170,6 +169,20 @@ def _take_grad_buffer(ctx, attr):
     return buf
 
 
+def _grad_written_in_forward(ctx, upstream):
+    """backward() of a Function whose forward wrote the gradient of its first input for an upstream gradient of 1 (ctx.grad_buf,
+    ctx.again, ctx.in_dtype): the buffer, handed over once - a second backward over a retained graph evaluates again -,
+    rescaled in place on the device (skipped there when the upstream gradient is exactly 1) or multiplied on the host
+    (loss.py:85, as it is), in the input's dtype.  None where that input wants no gradient."""
+    if not ctx.needs_input_grad[0]:
+        return None
+    grad = _take_grad_buffer(ctx, "grad_buf")
+    if grad is None:
+        grad = ctx.again()
+    grad = native.rescale_(grad, upstream) if grad.is_cuda else torch.mul(grad, upstream)
+    return grad.to(ctx.in_dtype)
+
+
 def _with_output_reg(result, reg, speculative, host_scale, dev_norm, loss_scale):
     """`result` of native.chain_loss_forward with the output regularisers `reg` = (l2, oor) on top: native.output_reg on the
     current stream behind the fused call - ACCUM into the gradient the call wrote for an upstream gradient of 1 (speculative
@@ -179,13 +192,6 @@ def _with_output_reg(result, reg, speculative, host_scale, dev_norm, loss_scale)
                                   grad_mode=_lib.GRAD_ACCUM, grad_scale=host_scale, norm_dev=dev_norm, loss_scale=loss_scale,
                                   totals=totals)
     return result
-
-
-def _accumulate_output_reg(reg, state, grad, host_scale, upstream):
-    """overlap = False: the regularisers' gradient into the one chain_loss_backward just wrote (scale host_scale * upstream)."""
-    if reg is not None:
-        native.output_reg(state.x, state.lengths_dev, reg[0], reg[1], grad=grad, grad_mode=_lib.GRAD_ACCUM,
-                          grad_scale=host_scale, grad_scale_dev=upstream)
 
 
 def _attach_reg(out, res, reg, host_scale, dev_norm):
@@ -324,6 +330,101 @@ class _ValueOf(torch.autograd.Function):
         return g, None
 
 
+def _fused_forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize, reg, wts):
+    """forward() of ChainLossFunction (`xent_output` None) and of ChainLossXentFunction: the fused call, behind it on the same
+    stream the output regularisers' pass (`reg`) and the weights' pass (`wts`), each over the whole batch (after the last slice
+    of a call in slices)."""
+    x = input.detach()
+    z = None if xent_output is None else xent_output.detach()
+    B, D = x.size(0), x.size(2)
+    if B != num_graphs.batch_size:
+        raise ValueError(
+            "input batch size ({}) does not equal to graph batch size ({})"
+            .format(B, num_graphs.batch_size))
+    lengths = torch.as_tensor(input_lengths)
+    plan = _plan.graph_plan(den_graph, D, x.device)
+    gt = num_graphs.device_tensors(x.device)
+    gstride = 0 if num_graphs.shared_graph is not None else 1
+    # (alignment time windows of the numerator, or None)
+    tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
+    # avg=True divides by the frame count (loss.py:103-104): a host scalar when the lengths
+    # live on the host, else a device scalar - never a sync
+    ctx.host_scale, ctx.dev_norm = _normaliser(avg, lengths, None if wts is None else wts[2])
+    # When a gradient will be asked for, the occupancy passes run inside forward, overlapped
+    # with the recursions, for an upstream gradient of 1 (what `loss.backward()` sends);
+    # backward then only rescales if the upstream gradient turns out to differ.
+    ctx.speculative = bool(ctx.needs_input_grad[0]) and ChainLossFunction.overlap
+    # (2-byte network outputs go to the kernels as they are when the gradient is written here, or never)
+    half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
+    spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closures must not hold ctx)
+    c = 0.0 if z is None else float(xent_regularize)
+    xent = None if z is None else (z, bool(ctx.needs_input_grad[1]), c)
+
+    def evaluate(loss_scale):
+        r = native.chain_loss_forward(
+            plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
+            with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw, xent=xent)
+        if reg is not None:
+            # into the gradient the call wrote (speculative), else the objective only; behind the call's xent totals
+            r = _with_output_reg(r, reg, spec, hscale, dnorm, loss_scale)
+        if wts is not None:
+            # the rows of the gradient the call wrote (speculative) and of the xent branch's, and the weighted sums into its totals
+            r = _with_weights(r, wts, reg, c, spec, dnorm, loss_scale)
+        return r
+    den_objf, num_objf, bad, state, totals = evaluate(hscale)
+    # a second backward over a retained graph (loss.py:82-87 allows it) runs the recursions again
+    ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))   # (state, bad)
+    ctx.reg, ctx.wts, ctx.state = reg, wts, state
+    ctx.in_dtype = input.dtype
+    ctx.z = z
+    if z is not None:
+        ctx.z_version, ctx.z_dtype = z._version, xent_output.dtype
+    ctx.bad_count = bad                      # int32[2]: denominator, numerator; never synced here
+    # -(num - den) [- c * xent] [/ frames], loss.py:100-104, comes with the call (the last workgroup of its last kernel adds the
+    # per-sequence objectives up): no reduction / subtraction / scaling launches behind it
+    objf = native.totals_scalar(totals)    # (no launch; not a view of the statistics: `loss /= n` works)
+    out = _attach(objf, totals, bad)
+    if z is not None:
+        out.xent_objf = state.xent.totals[0]                # sum_b xent_objf[b] [/ frames]: detached, for logging
+        out.xent_objf_per_seq = state.xent.objf
+    out = _attach_reg(out, state.reg, reg, hscale, dnorm)
+    return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+
+
+def _fused_backward(ctx, objf_grad):
+    """backward() of the two: (gradient of the chain output, gradient of the xent output), None where it is not wanted."""
+    state = _take_grad_buffer(ctx, "state")
+    if state is None:
+        if ctx.z is not None and ctx.z._version != ctx.z_version:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "the xent output given to the LF-MMI loss (second backward over a retained graph)")
+        state, ctx.bad_count = ctx.again()
+        ChainFunction.last_bad_count = ctx.bad_count
+    grad = zgrad = None
+    if ctx.needs_input_grad[0]:
+        if ctx.speculative:
+            # (a device-side normaliser - avg=True with the lengths on the device - was divided into the gradient by the call
+            # that wrote it: include/pychain_hip.h, loss_norm_dev; an upstream gradient of exactly 1 then costs one tiny launch)
+            grad = native.rescale_(state.grad, objf_grad)
+        else:
+            g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
+            grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
+            if ctx.reg is not None:
+                # the regularisers' gradient into the one chain_loss_backward just wrote (scale host_scale * upstream)
+                native.output_reg(state.x, state.lengths_dev, ctx.reg[0], ctx.reg[1], grad=grad, grad_mode=_lib.GRAD_ACCUM,
+                                  grad_scale=ctx.host_scale, grad_scale_dev=g)
+            if ctx.wts is not None:
+                native.weight_rows(grad, state.lengths_dev, ctx.wts[0], ctx.wts[1])
+            ctx.bad_count = ctx.bad_count + bad              # (the occupancy launches' own checks)
+            ChainFunction.last_bad_count = ctx.bad_count
+        grad = grad.to(ctx.in_dtype)
+    if ctx.z is not None and ctx.needs_input_grad[1]:
+        zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
+    state.grad = state.xent = None         # the stored trajectories go with `state`
+    state.den_ws = state.num_ws = None
+    return grad, zgrad
+
+
 class ChainLossFunction(torch.autograd.Function):
     """Denominator + numerator in one pass, split at the autograd
     boundary: forward runs the four recursions (numerator on a side stream) and returns the
@@ -334,99 +435,13 @@ class ChainLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, reg=None, wts=None):
-        x = input.detach()
-        B, D = x.size(0), x.size(2)
-        if B != num_graphs.batch_size:
-            raise ValueError(
-                "input batch size ({}) does not equal to graph batch size ({})"
-                .format(B, num_graphs.batch_size))
-        lengths = torch.as_tensor(input_lengths)
-        plan = _plan.graph_plan(den_graph, D, x.device)
-        gt = num_graphs.device_tensors(x.device)
-        gstride = 0 if num_graphs.shared_graph is not None else 1
-        # (alignment time windows of the numerator, or None)
-        tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
-        # avg=True divides by the frame count (loss.py:103-104): a host scalar when the lengths
-        # live on the host, else a device scalar - never a sync
-        ctx.host_scale, ctx.dev_norm = 1.0, None
-        if wts is not None:
-            ctx.host_scale, ctx.dev_norm = _normaliser(avg, lengths, wts[2])
-        elif avg:
-            if lengths.is_cuda:
-                ctx.dev_norm = lengths.sum().to(torch.float32)
-            else:
-                ctx.host_scale = 1.0 / float(lengths.sum())
-        # When a gradient will be asked for, the occupancy passes run inside forward, overlapped
-        # with the recursions, for an upstream gradient of 1 (what `loss.backward()` sends);
-        # backward then only rescales if the upstream gradient turns out to differ.
-        ctx.speculative = bool(ctx.needs_input_grad[0]) and ChainLossFunction.overlap
-        # (2-byte network outputs go to the kernels as they are when the gradient is written here, or never)
-        half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
-        spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closures must not hold ctx)
-        if wts is not None:
-            # utterance / derivative weights: one more pass on the same stream behind the fused call and behind the regularisers'
-            # pass, over the whole batch (after the last slice of a call in slices) - the rows of the gradient the call wrote
-            # (speculative), and the weighted sums into its totals
-            def evaluate(loss_scale):
-                r = native.chain_loss_forward(
-                    plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-                    with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw)
-                if reg is not None:
-                    r = _with_output_reg(r, reg, spec, hscale, dnorm, loss_scale)
-                return _with_weights(r, wts, reg, 0.0, spec, dnorm, loss_scale)
-            den_objf, num_objf, bad, state, totals = evaluate(hscale)
-            ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
-        elif reg is None:
-            den_objf, num_objf, bad, state, totals = native.chain_loss_forward(
-                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-                with_grad=ctx.speculative, grad_scale=ctx.host_scale, loss_scale=ctx.host_scale, norm_dev=ctx.dev_norm,
-                half_ok=half_ok, windows=tw)
-            # a second backward over a retained graph (loss.py:82-87 allows it) runs the recursions again
-            ctx.again = _recompute(x, lambda: native.chain_loss_forward(
-                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-                with_grad=spec, grad_scale=hscale, norm_dev=dnorm, half_ok=half_ok, windows=tw), lambda r: (r[3], r[2]))   # (state, bad)
-        else:
-            # the output regularisers: one more pass on the same stream behind the fused call, over the whole batch (after the
-            # last slice of a call in slices) - into the gradient the call wrote (speculative), else the objective only
-            evaluate = lambda loss_scale: _with_output_reg(native.chain_loss_forward(
-                plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-                with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw),
-                reg, spec, hscale, dnorm, loss_scale)
-            den_objf, num_objf, bad, state, totals = evaluate(hscale)
-            ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
-        ctx.reg, ctx.wts = reg, wts
-        # -(num - den) [/ frames], loss.py:100-104, comes with the call (the last workgroup of its last kernel adds the
-        # per-sequence objectives up): no reduction / subtraction / scaling launches behind it
-        objf = native.totals_scalar(totals)    # (no launch; not a view of the statistics: `loss /= n` works)
-        ctx.state = state
-        ctx.in_dtype = input.dtype
-        ctx.bad_count = bad                      # int32[2]: denominator, numerator; never synced here
-        out = _attach_reg(_attach(objf, totals, bad), state.reg, reg, hscale, dnorm)
-        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+        return _fused_forward(ctx, input, None, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, 0.0, reg, wts)
 
     overlap = True     # class-level switch: False = occupancy passes run in backward (no speculation)
 
     @staticmethod
     def backward(ctx, objf_grad):
-        state = _take_grad_buffer(ctx, "state")
-        if state is None:
-            state, ctx.bad_count = ctx.again()
-            ChainFunction.last_bad_count = ctx.bad_count
-        if ctx.speculative:
-            # (a device-side normaliser - avg=True with the lengths on the device - was divided into the gradient by the call
-            # that wrote it: include/pychain_hip.h, loss_norm_dev; an upstream gradient of exactly 1 then costs one tiny launch)
-            grad = native.rescale_(state.grad, objf_grad)
-        else:
-            g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
-            grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
-            _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
-            if ctx.wts is not None:
-                native.weight_rows(grad, state.lengths_dev, ctx.wts[0], ctx.wts[1])
-            ctx.bad_count = ctx.bad_count + bad              # (the occupancy launches' own checks)
-            ChainFunction.last_bad_count = ctx.bad_count
-        state.grad = None         # the stored trajectories go with `state`
-        state.den_ws = state.num_ws = None
-        return grad.to(ctx.in_dtype), None, None, None, None, None, None, None
+        return (_fused_backward(ctx, objf_grad)[0],) + (None,) * 7
 
 
 class NumeratorXentFunction(torch.autograd.Function):
@@ -461,13 +476,7 @@ class NumeratorXentFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        grad = _take_grad_buffer(ctx, "grad_buf")
-        if grad is None:
-            grad = ctx.again()                               # second backward over a retained graph: evaluate again
-        grad = native.rescale_(grad, g) if grad.is_cuda else torch.mul(grad, g)
-        return grad.to(ctx.in_dtype), None, None, None
+        return _grad_written_in_forward(ctx, g), None, None, None
 
 
 def numerator_xent(xent_output, nnet_output, lengths, num_graphs):
@@ -502,13 +511,7 @@ class OutputRegFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        if not ctx.needs_input_grad[0]:
-            return None, None, None, None
-        grad = _take_grad_buffer(ctx, "grad_buf")
-        if grad is None:
-            grad = ctx.again()                               # second backward over a retained graph: evaluate again
-        grad = native.rescale_(grad, g) if grad.is_cuda else torch.mul(grad, g)
-        return grad.to(ctx.in_dtype), None, None, None
+        return _grad_written_in_forward(ctx, g), None, None, None
 
 
 def output_regularizer(x, lengths, l2=0.0, out_of_range=0.0):
@@ -533,82 +536,12 @@ class ChainLossXentFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg, xent_regularize, reg=None,
                 wts=None):
-        x = input.detach()
-        B, D = x.size(0), x.size(2)
-        if B != num_graphs.batch_size:
-            raise ValueError(
-                "input batch size ({}) does not equal to graph batch size ({})"
-                .format(B, num_graphs.batch_size))
-        lengths = torch.as_tensor(input_lengths)
-        plan = _plan.graph_plan(den_graph, D, x.device)
-        gt = num_graphs.device_tensors(x.device)
-        gstride = 0 if num_graphs.shared_graph is not None else 1
-        tw = num_graphs.device_time_windows(x.device) if getattr(num_graphs, "time_windows", None) is not None else None
-        ctx.host_scale, ctx.dev_norm = 1.0, None
-        if wts is not None:
-            ctx.host_scale, ctx.dev_norm = _normaliser(avg, lengths, wts[2])
-        elif avg:
-            if lengths.is_cuda:
-                ctx.dev_norm = lengths.sum().to(torch.float32)
-            else:
-                ctx.host_scale = 1.0 / float(lengths.sum())
-        ctx.speculative = bool(ctx.needs_input_grad[0]) and ChainLossFunction.overlap
-        half_ok = ctx.speculative or not bool(ctx.needs_input_grad[0])
-        z = xent_output.detach()
-        spec, hscale, dnorm = ctx.speculative, ctx.host_scale, ctx.dev_norm      # (locals: the closure must not hold ctx)
-        z_grad, c = bool(ctx.needs_input_grad[1]), float(xent_regularize)
-        fused = lambda loss_scale: native.chain_loss_forward(
-            plan, gt, gstride, num_graphs.num_states, x, lengths, leaky_coefficient,
-            with_grad=spec, grad_scale=hscale, loss_scale=loss_scale, norm_dev=dnorm, half_ok=half_ok, windows=tw,
-            xent=(z, z_grad, c))
-        # (the output regularisers: behind the call and behind its xent totals, on the same stream)
-        evaluate = fused if reg is None else (lambda loss_scale: _with_output_reg(fused(loss_scale), reg, spec, hscale, dnorm, loss_scale))
-        if wts is not None:
-            # (the weights: behind all of that, over the chain output's gradient and over the xent branch's - native.weight_rows)
-            unweighted = evaluate
-            evaluate = lambda loss_scale: _with_weights(unweighted(loss_scale), wts, reg, c, spec, dnorm, loss_scale)
-        ctx.reg, ctx.wts = reg, wts
-        den_objf, num_objf, bad, state, totals = evaluate(hscale)
-        objf = native.totals_scalar(totals)                 # the full loss: LF-MMI - c * xent [/ frames]
-        ctx.state = state
-        ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: (r[3], r[2]))
-        ctx.z_version, ctx.z = z._version, z
-        ctx.in_dtype, ctx.z_dtype = input.dtype, xent_output.dtype
-        ctx.bad_count = bad
-        out = _attach(objf, totals, bad)
-        out.xent_objf = state.xent.totals[0]                # sum_b xent_objf[b] [/ frames]: detached, for logging
-        out.xent_objf_per_seq = state.xent.objf
-        out = _attach_reg(out, state.reg, reg, hscale, dnorm)
-        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+        return _fused_forward(ctx, input, xent_output, input_lengths, den_graph, num_graphs, leaky_coefficient, avg,
+                              xent_regularize, reg, wts)
 
     @staticmethod
     def backward(ctx, objf_grad):
-        state = _take_grad_buffer(ctx, "state")
-        if state is None:
-            if ctx.z._version != ctx.z_version:
-                raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
-                                   "the xent output given to the LF-MMI loss (second backward over a retained graph)")
-            state, ctx.bad_count = ctx.again()
-            ChainFunction.last_bad_count = ctx.bad_count
-        grad = None
-        if ctx.needs_input_grad[0]:
-            if ctx.speculative:
-                grad = native.rescale_(state.grad, objf_grad)
-            else:
-                g = objf_grad if ctx.dev_norm is None else objf_grad / ctx.dev_norm.to(objf_grad.device)
-                grad, bad = native.chain_loss_backward(state, ctx.host_scale, g)
-                _accumulate_output_reg(ctx.reg, state, grad, ctx.host_scale, g)
-                if ctx.wts is not None:
-                    native.weight_rows(grad, state.lengths_dev, ctx.wts[0], ctx.wts[1])
-                ctx.bad_count = ctx.bad_count + bad
-                ChainFunction.last_bad_count = ctx.bad_count
-            grad = grad.to(ctx.in_dtype)
-        zgrad = None
-        if ctx.needs_input_grad[1]:
-            zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
-        state.grad = state.xent = None
-        state.den_ws = state.num_ws = None
-        return grad, zgrad, None, None, None, None, None, None, None, None
+        return _fused_backward(ctx, objf_grad) + (None,) * 8
 
 
 class ChainLoss(nn.Module):
@@ -660,127 +593,88 @@ class ChainLoss(nn.Module):
         sum_b u_b L_b; `loss.totals[1]` holds it too, `loss.totals[3]` sum_b u_b (den_b - num_b), and `loss.xent_objf`,
         `loss.l2_term`, `loss.out_of_range_term` become the weighted amounts.  Both None: exactly the call without them."""
         reg = self._reg()
+        z = xent_output if self.xent_regularize != 0.0 else None
+        wts = None
         if utt_weights is not None or deriv_weights is not None:
             wts = _check_weights(utt_weights, deriv_weights, x.size(0), x.size(1), self.avg)
-            if self._on_kernels(x, num_graphs):
-                # (uploaded once for every pass of the step; the utterance weights as they were given ride along: a host
-                # normaliser is made of them)
-                dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
-                return self._forward(x, x_lengths, num_graphs, xent_output, reg, wts=(dev(wts[0]), dev(wts[1]), wts[0]))
-            return self._forward_weighted(x, x_lengths, num_graphs, xent_output, reg, wts)
-        if reg is None or self._on_kernels(x, num_graphs):
-            return self._forward(x, x_lengths, num_graphs, xent_output, reg)
-        return self._forward_reg(x, x_lengths, num_graphs, xent_output, reg)
+        if not self._on_kernels(x, num_graphs):
+            return self._forward_separate(x, x_lengths, num_graphs, z, reg, wts)
+        if wts is not None:
+            # (uploaded once for every pass of the step; the utterance weights as they were given ride along: a host
+            # normaliser is made of them)
+            dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
+            wts = (dev(wts[0]), dev(wts[1]), wts[0])
+        if z is None:
+            return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg, reg, wts)
+        return ChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg,
+                                           self.xent_regularize, reg, wts)
 
-    def _forward_reg(self, x, x_lengths, num_graphs, xent_output, reg, avg=None):
-        avg = self.avg if avg is None else avg
-        # the unfused route and CPU tensors: the loss without the terms as it is, and the terms through output_regularizer
-        # (the loss without the terms reads x through a view of its own: its calls' gradients are added up at that view, as
-        # ChainLoss without the terms adds them, and x receives exactly two gradients - that sum and the term.  A sum of two
-        # does not depend on which arrives first: x.grad is (the gradient without the terms) + the term, rounded once more)
-        base = self._forward(x.view_as(x), x_lengths, num_graphs, xent_output, None, avg=avg)
-        term = output_regularizer(x, x_lengths, reg[0], reg[1])
-        l2t, oort, per_seq = term.l2_term, term.out_of_range_term, term._reg_per_seq
-        if avg:
-            n = x_lengths.sum()
-            term, l2t, oort = term / n, l2t / n, oort / n
-        objf = base + term
-        objf.totals = objf.totals_all = None
-        objf.bad_count = base.bad_count
-        if hasattr(base, "xent_objf"):
-            objf.xent_objf = base.xent_objf
-        objf.l2_term, objf.out_of_range_term = l2t, oort
-        objf._per_seq = dict(base._per_seq, reg=per_seq)
-        return objf
-
-    def _forward_weighted(self, x, x_lengths, num_graphs, xent_output, reg, wts):
-        """The unfused route and CPU tensors under weights: the gradient comes from the loss as it is, un-averaged, evaluated on
-        weight_rows(x, w) - its backward scales the rows, once, after autograd has added the calls' gradients up -, divided by N;
-        the value is replaced by the weighted sum of the per-sequence objectives the calls leave (fp64, rounded once)."""
-        u, f = wts
+    def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts):
+        """The unfused route and CPU tensors: two ChainFunction calls as in the reference, the cross-entropy term through
+        numerator_xent (`z`), the regularisers through output_regularizer (`reg`), each where it is switched on.
+        Under weights `wts` = (u, f) the gradient comes from the loss as it is, evaluated on weight_rows(x, w) - its backward
+        scales the rows, once, after autograd has added the calls' gradients up.  Derivative weights alone change neither the
+        loss nor N.  Under utterance weights the loss is evaluated un-averaged and divided by N = sum_b u_b L_b; its value is
+        replaced by the weighted sum of the per-sequence objectives the calls leave (fp64, rounded once)."""
+        u, f = wts if wts is not None else (None, None)
         lengths = torch.as_tensor(x_lengths)
-        xw = WeightRowsFunction.apply(x, lengths, u, f)
-        with_xent = self.xent_regularize != 0.0 and xent_output is not None
-        zw = WeightRowsFunction.apply(xent_output, lengths, u, f) if with_xent else None
-        if u is None:
-            # derivative weights only: neither the loss nor N changes - today's call, its gradient rows scaled
-            local = (self._forward(xw, x_lengths, num_graphs, zw, None) if reg is None
-                     else self._forward_reg(xw, x_lengths, num_graphs, zw, reg))
-            local.weighted_frames = lengths.sum()
-            return local
-        local = (self._forward(xw, x_lengths, num_graphs, zw, None, avg=False) if reg is None
-                 else self._forward_reg(xw, x_lengths, num_graphs, zw, reg, avg=False))
-        per, bad = local._per_seq, local.bad_count
-        dev = per["den"].device
-        ud, live = u.to(dev).double(), u.to(dev) != 0
-        total = lambda t: torch.where(live, ud * t.to(dev).double(), torch.zeros_like(ud)).sum()     # (weight 0: skipped, not multiplied)
-        frames = (ud * lengths.to(dev)).sum()
-        n = frames if self.avg else torch.ones_like(frames)
-        value = total(per["den"] - per["num"])
-        if with_xent:
-            sx = total(per["xent"])
-            value = value - self.xent_regularize * sx
-        if reg is not None:
-            s2, so = total(per["reg"][:, 0]), total(per["reg"][:, 1])
-            value = value + 0.5 * reg[0] * s2 + reg[1] * so
-        if self.avg:
-            local = local / frames.to(torch.float32)
-        objf = _ValueOf.apply(local, (value / n).to(torch.float32))
-        objf.totals = objf.totals_all = None
-        objf.bad_count = bad
-        objf.weighted_frames = frames.to(torch.float32)
-        if with_xent:
-            objf.xent_objf = (sx / n).to(torch.float32)
-        if reg is not None:
-            objf.l2_term, objf.out_of_range_term = (0.5 * reg[0] * s2 / n).to(torch.float32), (reg[1] * so / n).to(torch.float32)
-        return objf
-
-    def _forward(self, x, x_lengths, num_graphs, xent_output, reg, avg=None, wts=None):
-        avg = self.avg if avg is None else avg
-        if self.xent_regularize != 0.0 and xent_output is not None:
-            return self._forward_xent(x, x_lengths, num_graphs, xent_output, reg, avg, wts)
-        if self._on_kernels(x, num_graphs):
-            if wts is not None:
-                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, avg, reg, wts)
-            if reg is not None:
-                return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, avg, reg)
-            return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs,
-                                           self.leaky_coefficient, avg)
-        batch_size = x.size(0)
-        den_graphs = ChainGraphBatch(self.den_graph, batch_size)
-        den_objf = ChainFunction.apply(x, x_lengths, den_graphs, self.leaky_coefficient)
-        num_objf = ChainFunction.apply(x, x_lengths, num_graphs)
-        objf = -(num_objf - den_objf)
+        if wts is not None:
+            x = WeightRowsFunction.apply(x, lengths, u, f)
+            z = None if z is None else WeightRowsFunction.apply(z, lengths, u, f)
+        avg = self.avg and u is None
+        # (with the regularisers, the loss without them reads x through a view of its own: its calls' gradients are added up at
+        # that view, as ChainLoss without the terms adds them, and x receives exactly two gradients - that sum and the term.  A
+        # sum of two does not depend on which arrives first: x.grad is (the gradient without the terms) + the term, rounded once
+        # more)
+        xv = x if reg is None else x.view_as(x)
+        den = ChainFunction.apply(xv, x_lengths, ChainGraphBatch(self.den_graph, x.size(0)), self.leaky_coefficient)
+        num = ChainFunction.apply(xv, x_lengths, num_graphs)
+        objf = -(num - den)
         if avg:
             objf = objf / x_lengths.sum()
-        # (two native calls made this loss: neither's totals are the step's - ShardedChainLoss finds none and all-reduces its own
+        if z is not None:
+            xent = numerator_xent(z, xv, x_lengths, num_graphs)
+            xent_per_seq = xent.xent_objf_per_seq
+            if avg:
+                xent = xent / x_lengths.sum()
+            objf = objf - self.xent_regularize * xent
+            xent_objf = xent.detach()
+        if reg is not None:
+            term = output_regularizer(x, x_lengths, reg[0], reg[1])
+            l2t, oort, reg_per_seq = term.l2_term, term.out_of_range_term, term._reg_per_seq
+            if avg:
+                n = x_lengths.sum()
+                term, l2t, oort = term / n, l2t / n, oort / n
+            objf = objf + term
+        if u is not None:
+            den_per_seq, num_per_seq = den._objf_per_seq, num._objf_per_seq
+            dev = den_per_seq.device
+            ud, live = u.to(dev).double(), u.to(dev) != 0
+            total = lambda t: torch.where(live, ud * t.to(dev).double(), torch.zeros_like(ud)).sum()     # (weight 0: skipped, not multiplied)
+            frames = (ud * lengths.to(dev)).sum()
+            n = frames if self.avg else torch.ones_like(frames)
+            value = total(den_per_seq - num_per_seq)
+            if z is not None:
+                sx = total(xent_per_seq)
+                value = value - self.xent_regularize * sx
+                xent_objf = (sx / n).to(torch.float32)
+            if reg is not None:
+                s2, so = total(reg_per_seq[:, 0]), total(reg_per_seq[:, 1])
+                value = value + 0.5 * reg[0] * s2 + reg[1] * so
+                l2t, oort = (0.5 * reg[0] * s2 / n).to(torch.float32), (reg[1] * so / n).to(torch.float32)
+            if self.avg:
+                objf = objf / frames.to(torch.float32)
+            objf = _ValueOf.apply(objf, (value / n).to(torch.float32))
+            frames = frames.to(torch.float32)
+        # (several native calls made this loss: none's totals are the step's - ShardedChainLoss finds none and all-reduces its own
         # three scalars; the two bad counts ride along as they are: no launch here)
         objf.totals = objf.totals_all = None
-        objf.bad_count = (den_objf.bad_count, num_objf.bad_count)
-        objf._per_seq = dict(den=den_objf._objf_per_seq, num=num_objf._objf_per_seq)    # (internal: _forward_weighted)
         ChainFunction.last_totals = ChainFunction.last_totals_all = None
-        return objf
-
-    def _forward_xent(self, x, x_lengths, num_graphs, xent_output, reg=None, avg=None, wts=None):
-        avg = self.avg if avg is None else avg
-        if self._on_kernels(x, num_graphs):
-            if wts is not None:
-                return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
-                                                   self.leaky_coefficient, avg, self.xent_regularize, reg, wts)
-            if reg is not None:
-                return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
-                                                   self.leaky_coefficient, avg, self.xent_regularize, reg)
-            return ChainLossXentFunction.apply(x, xent_output, x_lengths, self.den_graph, num_graphs,
-                                               self.leaky_coefficient, avg, self.xent_regularize)
-        # the unfused route: the loss without xent as it is, and the cross-entropy term through numerator_xent
-        lfmmi = self._forward(x, x_lengths, num_graphs, None, None, avg=avg)
-        xent = numerator_xent(xent_output, x, x_lengths, num_graphs)
-        per_seq = xent.xent_objf_per_seq
-        if avg:
-            xent = xent / x_lengths.sum()
-        objf = lfmmi - self.xent_regularize * xent
-        objf.totals = objf.totals_all = None
-        objf.bad_count = lfmmi.bad_count
-        objf.xent_objf = xent.detach()
-        objf._per_seq = dict(lfmmi._per_seq, xent=per_seq)
+        objf.bad_count = (den.bad_count, num.bad_count)
+        if z is not None:
+            objf.xent_objf = xent_objf
+        if reg is not None:
+            objf.l2_term, objf.out_of_range_term = l2t, oort
+        if wts is not None:
+            objf.weighted_frames = frames if u is not None else lengths.sum()
         return objf

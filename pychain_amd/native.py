@@ -32,16 +32,37 @@ def _require_device(t, what):
 # ---------------------------------------------------------------------------
 CPU_THREADS = 0          # host threads the sequences of a minibatch are dealt to (0 = one per hardware thread)
 _GRAPH_INT = ("forward_transitions", "forward_transition_indices", "backward_transitions", "backward_transition_indices")
+_GRAPH6 = ["forward_transitions", "forward_transition_indices", "forward_transition_probs",
+           "backward_transitions", "backward_transition_indices", "backward_transition_probs"]
+_GRAPH8 = _GRAPH6 + ["initial_probs", "final_probs"]
+_GRAPH_FORWARD = _GRAPH6[:3]
+
+
+def _graph_ptrs(gt, names=_GRAPH8):
+    """The graph pointers of a device entry point in ABI order, `gt` a dict of device graph tensors: all eight, or those of
+    `names` (chain_loss_backward reads the forward transitions alone)."""
+    return [gt[n].data_ptr() for n in names]
 
 
 def _cpu_graph(graphs, with_leaky):
     """(tensors in ABI order, graph_batch_stride): one graph for every sequence (stride 0) or [B,...] tensors."""
     src, stride = (graphs.shared_graph, 0) if graphs.shared_graph is not None else (graphs, 1)
-    names = ["forward_transitions", "forward_transition_indices", "forward_transition_probs",
-             "backward_transitions", "backward_transition_indices", "backward_transition_probs"]
-    names += (["leaky_probs"] if with_leaky else []) + ["initial_probs", "final_probs"]
+    names = _GRAPH6 + (["leaky_probs"] if with_leaky else []) + ["initial_probs", "final_probs"]
     ts = [getattr(src, n).to(torch.int32 if n in _GRAPH_INT else torch.float32).contiguous() for n in names]
     return ts, stride
+
+
+def _host_lengths(lengths, B, T):
+    """The int64 lengths a host twin reads: on the host, contiguous, checked."""
+    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
+    _check_lengths(lc, B, T)
+    return lc
+
+
+def _host_inputs(x, lengths):
+    """(x as contiguous float32 [B,T,D], the int64 lengths on the host - checked): what every host twin reads."""
+    xf = x.detach().to(torch.float32).contiguous()
+    return xf, _host_lengths(lengths, xf.shape[0], xf.shape[1])
 
 
 def cpu_forward_backward(graphs, x, lengths, leaky_coefficient=1e-5, input_is_exp=False, grad_mode=_lib.GRAD_LINEAR, clamp=True,
@@ -52,10 +73,8 @@ def cpu_forward_backward(graphs, x, lengths, leaky_coefficient=1e-5, input_is_ex
     `windows` (numerator only): int [B, H, 2] alignment time windows (include/pychain_hip.h: pychain_hip_*_tw), None = none."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_forward_backward is for CPU tensors; device tensors run on the HIP kernels")
-    xf = x.detach().to(torch.float32).contiguous()
+    xf, lc = _host_inputs(x, lengths)
     B, T, D = xf.shape
-    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
-    _check_lengths(lc, B, T)
     ts, stride = _cpu_graph(graphs, not graphs.log_domain)
     H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
     objf = torch.empty(B, dtype=torch.float32)
@@ -117,6 +136,15 @@ def release_workspaces():
 
 def _stream(device):
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def _dev_scalar(t, device):
+    """An optional 0-dim scalar the kernels read on the device (a normaliser, an upstream gradient): None, or float32 on `device`."""
+    return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
 
 
 def _lengths_dev(lengths, device):
@@ -210,17 +238,14 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         nws = L.pychain_hip_num_workspace_bytes(B, T, int(num_states), K, D)
         ws = _workspace(nws, dev, "num")
-        fn, name, tail = L.pychain_hip_num_forward_backward, "pychain_hip_num_forward_backward", ()
         if windows is not None:
             windows = _check_windows(windows, B, int(num_states), dev)
-            fn, name, tail = L.pychain_hip_num_forward_backward_tw, "pychain_hip_num_forward_backward_tw", (windows.data_ptr(),)
-        _lib.check(fn(
-            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
-            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
-            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
-            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
+        # (the widest entry point of the family; the narrower ones pass NULL on to it)
+        _lib.check(L.pychain_hip_num_forward_backward_xent(
+            *_graph_ptrs(gt), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(grad_mode), float(grad_scale),
-            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), *tail), name)
+            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), _ptr(windows), None),
+            "pychain_hip_num_forward_backward_xent")
     return objf, grad, bad
 
 
@@ -271,13 +296,10 @@ def num_xent(gt, graph_stride, num_states, x, lengths, z, with_grad=True, window
             windows = _check_windows(windows, B, int(num_states), dev)
         arg, keep = _xent_arg(z, (B, T, D), num_states, K, with_grad, 1.0, 0.0, res)
         _lib.check(L.pychain_hip_num_forward_backward_xent(
-            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
-            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
-            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
-            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
+            *_graph_ptrs(gt), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(_lib.GRAD_LINEAR), 1.0,
             objf.data_ptr(), 0, bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev),
-            0 if windows is None else windows.data_ptr(), ctypes.addressof(arg)), "pychain_hip_num_forward_backward_xent")
+            _ptr(windows), ctypes.addressof(arg)), "pychain_hip_num_forward_backward_xent")
         del keep
     return res
 
@@ -286,13 +308,11 @@ def cpu_num_xent(graphs, x, lengths, z, with_grad=True, windows=None):
     """The same on CPU tensors: the host twin (pychain_hip_cpu_num_forward_backward_xent), fp64 accumulation."""
     if x.is_cuda or z.is_cuda:
         raise RuntimeError("pychain_amd: cpu_num_xent is for CPU tensors; device tensors run on the HIP kernels")
-    xf = x.detach().to(torch.float32).contiguous()
     zf = z.detach().to(torch.float32).contiguous()
+    if tuple(zf.shape) != tuple(x.shape):
+        raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(zf.shape), tuple(x.shape)))
+    xf, lc = _host_inputs(x, lengths)
     B, T, D = xf.shape
-    if tuple(zf.shape) != (B, T, D):
-        raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(zf.shape), (B, T, D)))
-    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
-    _check_lengths(lc, B, T)
     ts, stride = _cpu_graph(graphs, False)
     H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
     objf = torch.empty(B, dtype=torch.float32)
@@ -350,16 +370,12 @@ def output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, with_
         res.per_seq = torch.empty(B, 2, dtype=torch.float32, device=dev)
         res.totals = torch.empty(3, dtype=torch.float32, device=dev)
         res.grad = grad
-        if grad_scale_dev is not None:
-            grad_scale_dev = grad_scale_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
-        if norm_dev is not None:
-            norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        grad_scale_dev, norm_dev = _dev_scalar(grad_scale_dev, dev), _dev_scalar(norm_dev, dev)
         ws = _workspace(L.pychain_hip_output_reg_workspace_bytes(B, T), dev, "outreg")
         _lib.check(L.pychain_hip_output_reg(
             x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, float(l2), float(oor), _CLAMP_LIMIT, int(grad_mode),
-            0 if grad is None else grad.data_ptr(), float(grad_scale), 0 if grad_scale_dev is None else grad_scale_dev.data_ptr(),
-            0 if norm_dev is None else norm_dev.data_ptr(), res.per_seq.data_ptr(), float(loss_scale), res.totals.data_ptr(),
-            0 if totals is None else totals.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_output_reg")
+            _ptr(grad), float(grad_scale), _ptr(grad_scale_dev), _ptr(norm_dev), res.per_seq.data_ptr(), float(loss_scale),
+            res.totals.data_ptr(), _ptr(totals), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_output_reg")
     return res
 
 
@@ -367,10 +383,8 @@ def cpu_output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, w
     """The same on CPU tensors: the host twin (pychain_hip_cpu_output_reg), fp32 rows, fp64 sums."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_output_reg is for CPU tensors; device tensors run on the HIP kernels")
-    xf = x.detach().to(torch.float32).contiguous()
+    xf, lc = _host_inputs(x, lengths)
     B, T, D = xf.shape
-    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
-    _check_lengths(lc, B, T)
     res = RegResult()
     if grad_mode == _lib.GRAD_ACCUM:
         if grad is not None and (grad.dtype != torch.float32 or tuple(grad.shape) != (B, T, D) or not grad.is_contiguous()):
@@ -404,10 +418,6 @@ def _weight_args(u, f, B, T, device):
     return u, f
 
 
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
 def weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=None, den_objf=None, num_objf=None, xent_objf=None,
                 xent_coef=0.0, reg_per_seq=None, l2=0.0, oor=0.0, loss_scale=1.0, norm_dev=None, totals=None):
     """Utterance weights u [B] and derivative weights f [B,T] on the GPU (include/pychain_hip.h: pychain_hip_weight_rows), on the
@@ -430,8 +440,7 @@ def weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=None,
         u, f = _weight_args(utt_weights, deriv_weights, B, T, dev)
         if den_objf is not None:
             weighted = torch.empty(5, dtype=torch.float32, device=dev)
-        if norm_dev is not None:
-            norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        norm_dev = _dev_scalar(norm_dev, dev)
         _lib.check(_lib.lib().pychain_hip_weight_rows(
             _ptr(grad), _DTYPE_CODE[grad.dtype] if grad is not None else _lib.F32, ld.data_ptr(), B, T, D, _ptr(u), _ptr(f),
             _ptr(den_objf), _ptr(num_objf), _ptr(xent_objf), float(xent_coef), _ptr(reg_per_seq), float(l2), float(oor),
@@ -450,8 +459,7 @@ def cpu_weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=N
             raise ValueError("cpu_weight_rows: grad must be a contiguous [B,T,D] float32 tensor")
         shape = tuple(grad.shape)
     B, T, D = shape
-    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
-    _check_lengths(lc, B, T)
+    lc = _host_lengths(lengths, B, T)
     u, f = _weight_args(utt_weights, deriv_weights, B, T, torch.device("cpu"))
     cf = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
     den_objf, num_objf, xent_objf, reg_per_seq, norm = cf(den_objf), cf(num_objf), cf(xent_objf), cf(reg_per_seq), cf(norm)
@@ -482,10 +490,7 @@ def align(gt, graph_stride, num_states, x, lengths):
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         ws = _workspace(L.pychain_hip_align_workspace_bytes(B, T, int(num_states), K, D), dev, "align")
         _lib.check(L.pychain_hip_align(
-            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
-            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
-            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
-            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
+            *_graph_ptrs(gt), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K,
             score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
             "pychain_hip_align")
@@ -497,10 +502,8 @@ def cpu_align(graphs, x, lengths):
     fp32 value of the same input.  Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32)."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_align is for CPU tensors; device tensors run on the HIP kernels")
-    xf = x.detach().to(torch.float32).contiguous()
+    xf, lc = _host_inputs(x, lengths)
     B, T, D = xf.shape
-    lc = torch.as_tensor(lengths).to(torch.int64).cpu().contiguous()
-    _check_lengths(lc, B, T)
     ts, stride = _cpu_graph(graphs, False)
     H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
     score = torch.empty(B, dtype=torch.float64)
@@ -513,11 +516,10 @@ def cpu_align(graphs, x, lengths):
     return score, states, pdfs, bad
 
 
-def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengths,
-                                leaky_coefficient=1e-5, grad_scale=1.0, windows=None):
-    """Fused ChainLoss: returns (den_objf[B], num_objf[B], grad[B,T,D] = grad_scale*(gamma_den - gamma_num),
-    bad_count[2]).  The numerator recursion overlaps the denominator on a side stream.  `windows`: the numerator's device time
-    windows (int32 [B, H, 2]) or None."""
+def _chain_loss_args(plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient, half_ok, windows):
+    """What the two forms of the fused call share: the inputs as the kernels read them - checked -, the outputs both write and
+    the arguments both begin with.  Returns (x, lengths on the device, den_objf [B], num_objf [B], bad_count [2], windows, K,
+    the leading arguments: plan, leaky coefficient, numerator graphs, x, lengths, B, T, D)."""
     _require_device(x, "nnet_output")
     x = x.contiguous()
     B, T, D = x.shape
@@ -526,29 +528,37 @@ def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengt
     L = _lib.lib()
     dev = x.device
     with torch.cuda.device(dev):
-        x, xcode = _rows_as_given(x, lambda: L.pychain_hip_chain_loss_half_native(
+        x, xcode = _rows_as_given(x, lambda: half_ok and L.pychain_hip_chain_loss_half_native(
             plan.stride, plan.slot_rows, plan.num_states, D, B, T, int(num_states_num), K))
         ld = _lengths_dev(lengths, dev)
         den_objf = torch.empty(B, dtype=torch.float32, device=dev)
         num_objf = torch.empty(B, dtype=torch.float32, device=dev)
-        grad = torch.empty_like(x)
         bad = torch.empty(2, dtype=torch.int32, device=dev)
+    if windows is not None:
+        windows = _check_windows(windows, B, int(num_states_num), dev)
+    head = [plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient)] + _graph_ptrs(gt) + [
+        int(graph_stride), int(num_states_num), K, x.data_ptr(), xcode, ld.data_ptr(), B, T, D]
+    return x, ld, den_objf, num_objf, bad, windows, K, head
+
+
+def chain_loss_forward_backward(plan, gt, graph_stride, num_states_num, x, lengths,
+                                leaky_coefficient=1e-5, grad_scale=1.0, windows=None):
+    """Fused ChainLoss: returns (den_objf[B], num_objf[B], grad[B,T,D] = grad_scale*(gamma_den - gamma_num),
+    bad_count[2]).  The numerator recursion overlaps the denominator on a side stream.  `windows`: the numerator's device time
+    windows (int32 [B, H, 2]) or None."""
+    x, ld, den_objf, num_objf, bad, windows, K, head = _chain_loss_args(
+        plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient, True, windows)
+    B, T, D = x.shape
+    L = _lib.lib()
+    dev = x.device
+    with torch.cuda.device(dev):
+        grad = torch.empty_like(x)
         dws = _workspace(L.pychain_hip_den_workspace_min_bytes(B, T, plan.num_states, D), dev, "den")   # (the fused loss never exp's rows ahead)
         nws = _workspace(L.pychain_hip_num_workspace_bytes(B, T, int(num_states_num), K, D), dev, "num")
-        fn, name, tail = L.pychain_hip_chain_loss_forward_backward, "pychain_hip_chain_loss_forward_backward", ()
-        if windows is not None:
-            windows = _check_windows(windows, B, int(num_states_num), dev)
-            fn, name, tail = L.pychain_hip_chain_loss_forward_backward_tw, "pychain_hip_chain_loss_forward_backward_tw", (windows.data_ptr(),)
-        _lib.check(fn(
-            plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient),
-            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
-            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
-            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
-            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
-            int(num_states_num), K,
-            x.data_ptr(), xcode, ld.data_ptr(), B, T, D, float(grad_scale),
-            den_objf.data_ptr(), num_objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), 1.0, 0, 0,
-            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), *tail), name)
+        _lib.check(L.pychain_hip_chain_loss_forward_backward_xent(
+            *head, float(grad_scale), den_objf.data_ptr(), num_objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), 1.0, 0, 0,
+            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), _ptr(windows), None),
+            "pychain_hip_chain_loss_forward_backward_xent")
     return den_objf, num_objf, grad, bad
 
 
@@ -569,51 +579,32 @@ def chain_loss_forward(plan, gt, graph_stride, num_states_num, x, lengths, leaky
     `xent`: None, or (z, with_grad, c) - the numerator posteriors of the call as cross-entropy targets of z (include/pychain_hip.h:
     pychain_hip_xent): state.xent is then an XentResult (grad = -c * grad_scale [/ norm_dev] * d xent / dz, written by the same
     call), and totals[0] = totals[4] = the full loss, LF-MMI - c * xent, scaled alike."""
-    _require_device(x, "nnet_output")
-    x = x.contiguous()
+    # (`half_ok` False: a later chain_loss_backward on this state - it accumulates the numerator into an fp32 gradient)
+    x, ld, den_objf, num_objf, bad, windows, K, head = _chain_loss_args(
+        plan, gt, graph_stride, num_states_num, x, lengths, leaky_coefficient, half_ok, windows)
     B, T, D = x.shape
-    _check_lengths(lengths, B, T)
-    K = gt["forward_transitions"].shape[1]
     L = _lib.lib()
     dev = x.device
     st = ChainLossState()
     with torch.cuda.device(dev):
-        # (`half_ok` False: a later chain_loss_backward on this state - it accumulates the numerator into an fp32 gradient)
-        x, xcode = _rows_as_given(x, lambda: half_ok and L.pychain_hip_chain_loss_half_native(
-            plan.stride, plan.slot_rows, plan.num_states, D, B, T, int(num_states_num), K))
-        ld = _lengths_dev(lengths, dev)
-        den_objf = torch.empty(B, dtype=torch.float32, device=dev)
-        num_objf = torch.empty(B, dtype=torch.float32, device=dev)
-        bad = torch.empty(2, dtype=torch.int32, device=dev)
         totals = torch.empty(_lib.TOTALS, dtype=torch.float32, device=dev)
-        if norm_dev is not None:
-            norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+        norm_dev = _dev_scalar(norm_dev, dev)
         # per-call workspaces (they must survive until backward); the caching allocator makes this cheap
         dws = torch.empty(L.pychain_hip_den_workspace_min_bytes(B, T, plan.num_states, D), dtype=torch.uint8, device=dev)
         nws = torch.empty(L.pychain_hip_num_workspace_bytes(B, T, int(num_states_num), K, D), dtype=torch.uint8,
                           device=dev)
         grad = torch.empty_like(x) if with_grad else None
-        fn, name, tail = L.pychain_hip_chain_loss_forward, "pychain_hip_chain_loss_forward", ()
-        if windows is not None:
-            windows = _check_windows(windows, B, int(num_states_num), dev)
-            fn, name, tail = L.pychain_hip_chain_loss_forward_tw, "pychain_hip_chain_loss_forward_tw", (windows.data_ptr(),)
-        st.xent = keep = st.reg = st.weighted = None
+        st.xent = arg = keep = st.reg = st.weighted = None
         if xent is not None:
             z, z_grad, c = xent
             st.xent = XentResult()
             arg, keep = _xent_arg(z, (B, T, D), num_states_num, K, z_grad, -float(c) * float(grad_scale), -float(c), st.xent)
-            fn, name = L.pychain_hip_chain_loss_forward_xent, "pychain_hip_chain_loss_forward_xent"
-            tail = (0 if windows is None else windows.data_ptr(), ctypes.addressof(arg))
-        _lib.check(fn(
-            plan.blob.data_ptr(), plan.stride, plan.slot_rows, plan.num_states, float(leaky_coefficient),
-            gt["forward_transitions"].data_ptr(), gt["forward_transition_indices"].data_ptr(),
-            gt["forward_transition_probs"].data_ptr(), gt["backward_transitions"].data_ptr(),
-            gt["backward_transition_indices"].data_ptr(), gt["backward_transition_probs"].data_ptr(),
-            gt["initial_probs"].data_ptr(), gt["final_probs"].data_ptr(), int(graph_stride),
-            int(num_states_num), K, x.data_ptr(), xcode, ld.data_ptr(), B, T, D,
-            den_objf.data_ptr(), num_objf.data_ptr(), grad.data_ptr() if with_grad else 0, float(grad_scale),
-            bad.data_ptr(), float(loss_scale), 0 if norm_dev is None else norm_dev.data_ptr(), totals.data_ptr(),
-            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), *tail), name)
+        # (the widest entry point of the family; the narrower ones pass NULL on to it)
+        _lib.check(L.pychain_hip_chain_loss_forward_xent(
+            *head, den_objf.data_ptr(), num_objf.data_ptr(), _ptr(grad), float(grad_scale),
+            bad.data_ptr(), float(loss_scale), _ptr(norm_dev), totals.data_ptr(),
+            dws.data_ptr(), dws.numel(), nws.data_ptr(), nws.numel(), _stream(dev), _ptr(windows),
+            None if arg is None else ctypes.addressof(arg)), "pychain_hip_chain_loss_forward_xent")
     st.grad = grad
     # (which numerator wrote the stored rows: backward runs on autograd's thread, where the caller's thread options do not reach)
     st.num_compat = _lib.get_option("num_compat") or "0"
@@ -631,17 +622,12 @@ def chain_loss_backward(st, grad_scale=1.0, grad_scale_dev=None):
     with torch.cuda.device(dev):
         grad = torch.empty_like(st.x)
         bad = torch.empty(2, dtype=torch.int32, device=dev)
-        sptr = 0
-        if grad_scale_dev is not None:
-            grad_scale_dev = grad_scale_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
-            sptr = grad_scale_dev.data_ptr()
+        grad_scale_dev = _dev_scalar(grad_scale_dev, dev)
         with _lib.option("num_compat", st.num_compat):
             _lib.check(L.pychain_hip_chain_loss_backward(
-                st.plan.blob.data_ptr(), st.plan.stride, st.plan.slot_rows, st.plan.num_states,
-                st.gt["forward_transitions"].data_ptr(), st.gt["forward_transition_indices"].data_ptr(),
-                st.gt["forward_transition_probs"].data_ptr(),
+                st.plan.blob.data_ptr(), st.plan.stride, st.plan.slot_rows, st.plan.num_states, *_graph_ptrs(st.gt, _GRAPH_FORWARD),
                 st.graph_stride, st.num_states_num, K, st.x.data_ptr(), _DTYPE_CODE[st.x.dtype], st.lengths_dev.data_ptr(), B, T, D,
-                float(grad_scale), sptr, grad.data_ptr(), bad.data_ptr(),
+                float(grad_scale), _ptr(grad_scale_dev), grad.data_ptr(), bad.data_ptr(),
                 st.den_ws.data_ptr(), st.den_ws.numel(), st.num_ws.data_ptr(), st.num_ws.numel(), _stream(dev)),
                 "pychain_hip_chain_loss_backward")
     return grad, bad
@@ -652,12 +638,11 @@ def loss_total(den_objf, num_objf, scale=1.0, norm_dev=None):
     (the scalar of ChainLoss.forward, loss.py:100-104)."""
     dev = den_objf.device
     out = torch.empty((), dtype=torch.float32, device=dev)
-    if norm_dev is not None:
-        norm_dev = norm_dev.detach().to(device=dev, dtype=torch.float32).contiguous()
+    norm_dev = _dev_scalar(norm_dev, dev)
     with torch.cuda.device(dev):
         _lib.check(_lib.lib().pychain_hip_loss_total(
-            den_objf.data_ptr(), 0 if num_objf is None else num_objf.data_ptr(), den_objf.numel(), float(scale),
-            0 if norm_dev is None else norm_dev.data_ptr(), out.data_ptr(), _stream(dev)), "pychain_hip_loss_total")
+            den_objf.data_ptr(), _ptr(num_objf), den_objf.numel(), float(scale), _ptr(norm_dev), out.data_ptr(), _stream(dev)),
+            "pychain_hip_loss_total")
     return out
 
 
@@ -670,7 +655,7 @@ def totals_scalar(totals):
 
 def rescale_(t, scale_dev):
     """t *= scale_dev (0-dim device tensor), skipped on the device when the scalar is exactly 1."""
-    scale_dev = scale_dev.detach().to(device=t.device, dtype=torch.float32).contiguous()
+    scale_dev = _dev_scalar(scale_dev, t.device)
     with torch.cuda.device(t.device):
         _lib.check(_lib.lib().pychain_hip_rescale(t.data_ptr(), _DTYPE_CODE[t.dtype], t.numel(), scale_dev.data_ptr(), _stream(t.device)),
                    "pychain_hip_rescale")
@@ -680,10 +665,6 @@ def rescale_(t, scale_dev):
 # ---------------------------------------------------------------------------
 # pychain_C-compatible surface (positional signatures of pychain.cc:26-41, :81-94)
 # ---------------------------------------------------------------------------
-_GRAPH6 = ["forward_transitions", "forward_transition_indices", "forward_transition_probs",
-           "backward_transitions", "backward_transition_indices", "backward_transition_probs"]
-
-
 def _check_contiguous(**named):
     """CHECK_CONTIGUOUS of pychain.cc:24,42-54,95-107: every tensor argument, RuntimeError with the
     reference's message.  One extension: the stride-0 batch views of `ChainGraphBatch(one_graph, B)`
@@ -774,11 +755,11 @@ def forward_backward_log_domain(forward_transitions, forward_transition_indices,
             backward_transitions, backward_transition_indices, backward_transition_probs,
             initial_probs, final_probs]
     if not nnet_output.is_cuda:                   # chain-log-domain-computation.cc:123-159,231-271: the host twin
-        gb = _RawGraphs(dict(zip(_GRAPH6 + ["initial_probs", "final_probs"], vals)), log_domain=True)
+        gb = _RawGraphs(dict(zip(_GRAPH8, vals)), log_domain=True)
         objf, lgrad, bad = cpu_forward_backward(gb, nnet_output, sequence_lengths, grad_mode=_lib.GRAD_LOG, clamp=False)
         return [objf.sum(), lgrad, bad == 0]
     gt = _compat_cached("num", vals, (str(dev),), lambda: {
-        n: t.contiguous().to(dev) for n, t in zip(_GRAPH6 + ["initial_probs", "final_probs"], vals)})
+        n: t.contiguous().to(dev) for n, t in zip(_GRAPH8, vals)})
     objf, lgrad, bad = num_forward_backward(gt, 1, num_states, nnet_output, sequence_lengths,
                                             grad_mode=_lib.GRAD_LOG)
     return [objf.sum(), lgrad, bad == 0]
