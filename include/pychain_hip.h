@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 22
+#define PYCHAIN_HIP_ABI_VERSION 23
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -610,6 +610,66 @@ int pychain_hip_cpu_weight_rows(
     const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
     const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
     float* totals, float* weighted, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Posterior-target supervision (ABI 23): the numerator of the chain objective as sparse per-frame posterior targets instead of a
+ * graph - q(b,t,k) on the pdfs pdf(b,t,k), K entries per frame, from a teacher model or from lattice posteriors of unlabelled
+ * audio (Kaldi: the "KL" objective of teacher-student and semi-supervised chain training).  The objective is
+ * sum q x - log Z_den, its derivative q - gamma_den.  C callers: call pychain_hip_den_forward_backward, then
+ * pychain_hip_post_targets on the same stream, with the gradient, the per-sequence objectives and the totals the first left.
+ * ENTRIES.  (b,t,k) is live when t < L_b and 0 <= pdf < D.  pdf < 0 is padding and is skipped; pdf >= D in a live frame is
+ * skipped and counted in bad_count (dev int32[1], written by the call).  Rows and entries with t >= L_b are NEVER READ (a NaN in
+ * them is harmless).  Lengths outside [1,T] are clamped, as everywhere.  Targets need not sum to 1 per frame: they are
+ * multiplied in as given.
+ * OBJECTIVE.  num_objf_per_seq[b] = sum_{t < L_b} sum_k q_k * clamp(x(b,t,pdf_k), -30, 30).  x and q are widened to fp64 first,
+ * so every product is exact; the sum is fp64 in a fixed order - k within a frame, one value per frame into the workspace, then
+ * the frames of a sequence -, without float atomics, rounded once: the same call gives the same bits.  A NaN in a referenced live
+ * element makes that sequence's objective a NaN and leaves the other sequences' objectives alone.
+ * GRADIENT (`grad` dev [B,T,D] of nnet_output's dtype, or NULL: the objective only).  For every live frame and every distinct
+ * pdf d in it, qd = the fp32 sum of the frame's q_k with pdf_k == d, in ascending k, and
+ *   grad(b,t,d) = round(fmaf(s, qd, (float)grad(b,t,d)))         ONE fma, one rounding to the gradient's dtype
+ * with s = grad_scale [* *grad_scale_dev] [/ *loss_norm_dev], both scalars read on the device, formed in fp32 as
+ * pychain_hip_output_reg forms it.  ONLY THE ADDRESSED ELEMENTS ARE TOUCHED.  The clamp is not differentiated, as in the rest of
+ * the library.  A trainer passes s < 0 behind a denominator call that wrote grad_scale * gamma_den (the convention of
+ * PYCHAIN_HIP_GRAD_ACCUM).  A 2-BYTE GRADIENT IS THEREBY ROUNDED TWICE: the call that stored it rounded it to bf16 / fp16, and
+ * this pass rounds the sum again.  One thread owns a frame: a pdf that occurs several times in it does not race.
+ * TOTALS (`totals` dev float [PYCHAIN_HIP_TOTALS] or NULL: the totals of the denominator call on the same stream;
+ * den_objf_per_seq, dev [B], is then required).  One thread, in stream order behind that call, in ascending b and in fp64 over
+ * the float denominator objectives and the unrounded numerator sums:
+ *   totals[3] = S = sum_b den_b - sum_b num_b,   totals[0] = totals[4] = loss_scale * S [/ *loss_norm_dev],
+ *   totals[2] += the bad entries;   totals[1] and totals[5..7] keep their bits
+ * - the layout a fused call leaves, so pychain_hip_output_reg and pychain_hip_weight_rows work behind this call unchanged.
+ *   workspace   dev, pychain_hip_post_targets_workspace_bytes(B, T) bytes, 16-byte aligned
+ * Any K >= 1 and any D >= 1.  K < 1, a NULL required pointer, or a grad or workspace that is not 16-byte aligned:
+ * PYCHAIN_HIP_EINVAL.  The entry point is a translation unit of its own (csrc/post.hip): the objects of den_*.hip, num_*.hip,
+ * xent.hip, align.hip, outreg.hip and weights.hip do not change, and no existing entry point launches anything it did not
+ * launch before. */
+size_t pychain_hip_post_targets_workspace_bytes(int B, int T);
+int pychain_hip_post_targets(
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, void* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    const float* den_objf_per_seq, float* num_objf_per_seq, int32_t* bad_count,
+    float loss_scale, float* totals, void* workspace, size_t workspace_bytes, void* stream);
+/* the host twin: the same on host pointers (the two scalars too), fp32 rows, the same fma - its fp32 gradient has the device's
+ * bits - and the same fp64 sums; no workspace, no stream */
+int pychain_hip_cpu_post_targets(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, float* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    const float* den_objf_per_seq, float* num_objf_per_seq, int32_t* bad_count,
+    float loss_scale, float* totals, int num_threads);
+/* Sparse targets out of dense posterior rows (the teacher side).  Per live frame the elements of rows(b,t,:) are ordered by
+ * value descending, index ascending; a NaN never wins a comparison and is never selected.  The first K elements with
+ * value >= floor fill the slots in that order; unfilled slots get pdf = -1, prob = 0.  Values are the inputs widened to fp32
+ * (exact); with `normalize` each is divided by the fp32 sum of the selected values taken in slot order (IEEE division).  A frame
+ * with nothing selected stays all -1 / 0.  Frames t >= L_b are WRITTEN -1 / 0 and their rows never read.  out_pdfs int32
+ * [B,T,K], out_probs float [B,T,K].  1 <= K <= min(num_pdfs, 64), else PYCHAIN_HIP_EINVAL.  Rows of up to 9216 elements are
+ * read from memory once and held on chip; longer rows are re-read. */
+int pychain_hip_topk_rows(const void* rows, int rows_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+                          int K, float floor, int normalize, int32_t* out_pdfs, float* out_probs, void* stream);
+int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+                              int K, float floor, int normalize, int32_t* out_pdfs, float* out_probs, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -544,3 +544,126 @@ extern "C" int pychain_hip_cpu_weight_rows(
   }
   return PYCHAIN_HIP_OK;
 }
+
+// ---- posterior-target supervision (include/pychain_hip.h: pychain_hip_post_targets, pychain_hip_topk_rows; the device's
+// post.hip): the same fp64 sums in the same order of k and frames, the same single fma per addressed gradient element
+namespace pychain_hip {
+namespace {
+inline float post_add(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_post_targets(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, float* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    const float* den_objf_per_seq, float* num_objf_per_seq, int32_t* bad_count,
+    float loss_scale, float* totals, int num_threads) {
+  const char* who = "cpu_post_targets";
+  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !num_objf_per_seq || !bad_count)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if (totals && !den_objf_per_seq) return fail(PYCHAIN_HIP_EINVAL, "%s: totals need den_objf_per_seq", who);
+  g_cpu_calls++;
+  float s = grad_scale_dev ? grad_scale * *grad_scale_dev : grad_scale;
+  if (loss_norm_dev) s = s / *loss_norm_dev;
+  std::vector<double> sums((size_t)B);
+  std::vector<int> bads((size_t)B);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int64_t l = seq_lengths[b];
+    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    double seq = 0.0;
+    int bad = 0;
+    for (int t = 0; t < L; t++) {
+      const size_t f = (size_t)b * T + t;
+      const int32_t* pd = target_pdfs + f * K;
+      const float* pr = target_probs + f * K;
+      const float* x = nnet_output + f * D;
+      double acc = 0.0;
+      for (int k = 0; k < K; k++) {
+        const int d = pd[k];
+        if (d < 0) continue;
+        if (d >= D) { bad++; continue; }
+        const double xd = (double)x[d];
+        const double c = xd < -30.0 ? -30.0 : (xd > 30.0 ? 30.0 : xd);
+        acc = std::fma((double)pr[k], c, acc);
+        if (grad) {
+          bool first = true;
+          for (int j = 0; j < k; j++) first = first && pd[j] != d;
+          if (first) {
+            float qd = pr[k];
+            for (int j = k + 1; j < K; j++)
+              if (pd[j] == d) qd = post_add(qd, pr[j]);
+            float* g = grad + f * D + d;
+            *g = std::fma(s, qd, *g);
+          }
+        }
+      }
+      seq += acc;
+    }
+    sums[b] = seq; bads[b] = bad;
+    num_objf_per_seq[b] = (float)seq;
+  });
+  int bad = 0;
+  for (int b = 0; b < B; b++) bad += bads[b];
+  *bad_count = bad;
+  if (totals) {
+    double sd = 0.0, sn = 0.0;
+    for (int b = 0; b < B; b++) { sd += (double)den_objf_per_seq[b]; sn += sums[b]; }
+    const double S = sd - sn;
+    double v = (double)loss_scale * S;
+    if (loss_norm_dev) v /= (double)*loss_norm_dev;
+    const float full = (float)v;
+    totals[0] = full; totals[4] = full;
+    totals[3] = (float)S;
+    totals[2] = totals[2] + (float)bad;
+  }
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int D, int K, float floor,
+                                         int normalize, int32_t* out_pdfs, float* out_probs, int num_threads) {
+  const char* who = "cpu_topk_rows";
+  if (!rows || !seq_lengths || !out_pdfs || !out_probs) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1 || K > D || K > 64) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be in [1, min(D, 64)], got %d (D = %d)", who, K, D);
+  g_cpu_calls++;
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int64_t l = seq_lengths[b];
+    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    for (int t = 0; t < T; t++) {
+      const size_t f = (size_t)b * T + t;
+      int32_t* op = out_pdfs + f * K;
+      float* ov = out_probs + f * K;
+      int n = 0;
+      if (t < L) {
+        const float* r = rows + f * D;
+        float lastv = 0.f;
+        int lasti = -1;
+        for (; n < K; n++) {                       // the next element behind the previous pick: value descending, index ascending
+          int bi = -1;
+          float bv = 0.f;
+          for (int i = 0; i < D; i++) {
+            const float v = r[i];
+            const bool ok = v >= floor && (lasti < 0 || v < lastv || (v == lastv && i > lasti));
+            if (ok && (bi < 0 || v > bv)) { bv = v; bi = i; }
+          }
+          if (bi < 0) break;
+          op[n] = bi; ov[n] = bv;
+          lastv = bv; lasti = bi;
+        }
+        if (normalize && n > 0) {
+          float sum = 0.f;
+          for (int j = 0; j < n; j++) sum = post_add(sum, ov[j]);
+          for (int j = 0; j < n; j++) ov[j] = ov[j] / sum;
+        }
+      }
+      for (int j = n; j < K; j++) { op[j] = -1; ov[j] = 0.f; }
+    }
+  });
+  return PYCHAIN_HIP_OK;
+}

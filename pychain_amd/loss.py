@@ -25,7 +25,8 @@ from . import _lib, _plan, native
 from .graph import ChainGraphBatch
 
 __all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent",
-           "output_regularizer", "weight_rows", "ChainLoss"]
+           "output_regularizer", "weight_rows", "ChainLoss", "PosteriorTargets", "posterior_targets", "occupancies",
+           "posterior_numerator", "PosteriorNumeratorFunction", "PosteriorChainLossFunction"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -526,6 +527,214 @@ def output_regularizer(x, lengths, l2=0.0, out_of_range=0.0):
     return OutputRegFunction.apply(x, lengths, l2, oor)
 
 
+class PosteriorTargets(object):
+    """Sparse per-frame posterior targets q(b,t,k) on the pdfs pdf(b,t,k) (include/pychain_hip.h: pychain_hip_post_targets): what
+    ChainLoss.forward takes where the numerator graphs go when the supervision is a teacher's posteriors, or lattice posteriors
+    of unlabelled audio.  `pdfs`: integer [B,T,K], -1 for padding; `probs`: float [B,T,K]; stored as int32 and float32.  Host
+    tensors are validated (shapes, probs of the entries that are not padding finite and not negative; pdf < D where a call knows
+    D); device tensors are not inspected (no sync)."""
+
+    def __init__(self, pdfs, probs):
+        pdfs, probs = torch.as_tensor(pdfs), torch.as_tensor(probs)
+        if pdfs.dim() != 3 or tuple(pdfs.shape) != tuple(probs.shape) or pdfs.size(2) < 1:
+            raise ValueError("PosteriorTargets: pdfs and probs must both be [B, T, K >= 1], got %s and %s"
+                             % (list(pdfs.shape), list(probs.shape)))
+        if pdfs.is_floating_point() or pdfs.dtype == torch.bool or not probs.is_floating_point():
+            raise ValueError("PosteriorTargets: pdfs must be an integer tensor and probs a float tensor")
+        self.pdfs = pdfs.detach().to(torch.int32).contiguous()
+        self.probs = probs.detach().to(torch.float32).contiguous()
+        if not self.probs.is_cuda:
+            used = self.probs[self.pdfs.to(self.probs.device) >= 0] if not self.pdfs.is_cuda else self.probs
+            if not bool(torch.isfinite(used).all()) or bool((used < 0).any()):
+                raise ValueError("PosteriorTargets: probs must be finite and not negative")
+        self._device_cache = {}
+
+    @property
+    def batch_size(self):
+        return int(self.pdfs.size(0))
+
+    @property
+    def device(self):
+        return self.pdfs.device
+
+    @classmethod
+    def _of(cls, pdfs, probs):
+        t = cls.__new__(cls)                                   # (tensors this package made: not inspected again)
+        t.pdfs, t.probs, t._device_cache = pdfs, probs, {}
+        return t
+
+    def to(self, device):
+        """The targets on `device`: uploaded once and cached until a tensor is replaced or edited in place (as
+        ChainGraphBatch.device_tensors caches the numerator graphs)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if self.pdfs.device == device and self.probs.device == device:
+            return self
+        key = (str(device), self.pdfs.data_ptr(), self.pdfs._version, self.probs.data_ptr(), self.probs._version)
+        hit = self._device_cache.get(key)
+        if hit is None:
+            hit = PosteriorTargets._of(self.pdfs.to(device, non_blocking=True), self.probs.to(device, non_blocking=True))
+            self._device_cache = {key: hit}
+        return hit
+
+    def index_select(self, idx):
+        """The targets of the utterances `idx` (parallel.shard_batch)."""
+        idx = torch.as_tensor(idx, dtype=torch.int64)
+        return PosteriorTargets._of(self.pdfs.index_select(0, idx.to(self.pdfs.device)).contiguous(),
+                                    self.probs.index_select(0, idx.to(self.probs.device)).contiguous())
+
+    def check(self, B, T, D):
+        """Against the network output [B,T,D] of a call: the shape, and - host tensors only - every pdf below D."""
+        if tuple(self.pdfs.shape[:2]) != (B, T):
+            raise ValueError("posterior targets are [%d, %d, K], the network output is [%d, %d, D]"
+                             % (self.pdfs.size(0), self.pdfs.size(1), B, T))
+        if not self.pdfs.is_cuda and bool((self.pdfs >= D).any()):
+            raise ValueError("posterior targets name pdf %d, the network output has %d" % (int(self.pdfs.max()), D))
+        return self
+
+    @classmethod
+    def from_dense(cls, post, lengths, k, floor=0.0, normalize=True):
+        """The `k` largest posteriors of every live frame of `post` [B,T,D] that are >= `floor` (ties: the lower pdf), divided by
+        their sum when `normalize` (include/pychain_hip.h: pychain_hip_topk_rows): device tensors - fp32, bf16 or fp16 as they
+        are - on the HIP kernel, CPU tensors on the host twin."""
+        post = post.detach()
+        if post.dim() != 3:
+            raise ValueError("from_dense: posteriors must be [B, T, D], got %s" % list(post.shape))
+        k = int(k)
+        if k < 1 or k > min(post.size(2), 64):
+            raise ValueError("from_dense: k must be in [1, min(D, 64)], got %d (D = %d)" % (k, post.size(2)))
+        if post.is_cuda:
+            if post.dtype not in native._DTYPE_CODE:
+                post = post.float()
+            return cls._of(*native.topk_rows(post, lengths, k, floor, normalize))
+        return cls._of(*native.cpu_topk_rows(post, lengths, k, floor, normalize))
+
+
+def occupancies(x, lengths, graphs, leaky_coefficient=1e-5):
+    """The dense occupancies gamma(b,t,d) of (x, graphs) - what ChainFunction's backward hands out for an upstream gradient of 1 -
+    as a [B,T,D] tensor, not differentiable: of a probability-domain graph (a ChainGraph or a ChainGraphBatch: the denominator
+    posteriors) or of log-domain numerator graphs.  Rows beyond a length are zero."""
+    from .graph import ChainGraph
+    x = x.detach()
+    if isinstance(graphs, ChainGraph):
+        graphs = ChainGraphBatch(graphs, x.size(0))
+    if x.size(0) != graphs.batch_size:
+        raise ValueError("input batch size ({}) does not equal to graph batch size ({})".format(x.size(0), graphs.batch_size))
+    with torch.no_grad():
+        return ChainFunction._occupancies(x, lengths, graphs, leaky_coefficient)[1]
+
+
+def posterior_targets(teacher_output, lengths, graphs, k, leaky_coefficient=1e-5, floor=0.0, normalize=True):
+    """The teacher side of teacher-student LF-MMI: the occupancies of (teacher_output, graphs) - `occupancies` - cut down to
+    their `k` largest per frame - PosteriorTargets.from_dense.  Not differentiable."""
+    return PosteriorTargets.from_dense(occupancies(teacher_output, lengths, graphs, leaky_coefficient), lengths, k, floor, normalize)
+
+
+class PosteriorNumeratorFunction(torch.autograd.Function):
+    """sum_b num_b of include/pychain_hip.h (pychain_hip_post_targets), differentiable in the network output: the gradient -
+    zeros plus the pass with s = 1 - is written by the forward call for an upstream gradient of 1; backward rescales."""
+
+    @staticmethod
+    def forward(ctx, input, lengths, targets):
+        x = input.detach()
+        targets.check(*x.shape)
+        want = bool(ctx.needs_input_grad[0])
+        evaluate = lambda: PosteriorNumeratorFunction._evaluate(x, lengths, targets, want)
+        num, grad, bad = evaluate()
+        ctx.grad_buf = grad
+        ctx.again = _recompute(x, evaluate, lambda r: r[1])
+        ctx.in_dtype = input.dtype
+        out = num.sum(dtype=torch.float64).to(torch.float32)
+        out.objf_per_seq = out._objf_per_seq = num
+        out.bad_count = bad
+        return out
+
+    @staticmethod
+    def _evaluate(x, lengths, targets, want):
+        tg = targets.to(x.device)
+        if x.is_cuda:
+            xk = x if x.dtype in native._DTYPE_CODE else x.float()
+            grad = torch.zeros_like(xk, memory_format=torch.contiguous_format) if want else None
+            num, bad = native.post_targets(xk, lengths, tg.pdfs, tg.probs, grad=grad)
+        else:
+            grad = torch.zeros(x.shape, dtype=torch.float32) if want else None
+            num, bad = native.cpu_post_targets(x, lengths, tg.pdfs, tg.probs, grad=grad)
+        return num, grad, bad
+
+    @staticmethod
+    def backward(ctx, g):
+        return _grad_written_in_forward(ctx, g), None, None
+
+
+def posterior_numerator(x, lengths, targets):
+    """The numerator of posterior-target supervision, sum_b sum_{t < L_b} sum_k q_k clamp(x(b,t,pdf_k), -30, 30), as a 0-dim tensor
+    differentiable in x (the clamp is not differentiated, as in the rest of the library).  Device tensors run on the HIP kernel,
+    CPU tensors on the host twin.  `.objf_per_seq` of the result: the [B] per-sequence values; `.bad_count`: the entries that
+    name a pdf the network output does not have."""
+    return PosteriorNumeratorFunction.apply(x, lengths, targets)
+
+
+class PosteriorChainLossFunction(torch.autograd.Function):
+    """ChainLoss on device tensors with PosteriorTargets where the numerator graphs go: loss = (sum_b den_b - sum_b num_b) / N, its
+    gradient (gamma_den - q) / N written ONCE by the forward call for an upstream gradient of 1 - the denominator call
+    (native.den_forward_backward, scale 1 / N), behind it on the same stream native.post_targets into that gradient (scale
+    -1 / N) and into that call's totals, then the regularisers' and the weights' passes exactly as the fused step applies them.
+    ChainLossFunction.overlap has no effect here: the denominator call always writes its gradient.
+    LENGTHS ON THE DEVICE: N is then a device scalar the denominator entry point does not take, so its gradient is written
+    un-normalised and ONE native.rescale_ by 1 / N - one extra pass over [B,T,D] - puts it on the scale of the passes behind
+    it, which all read N on the device."""
+
+    @staticmethod
+    def forward(ctx, input, input_lengths, den_graph, targets, leaky_coefficient, avg, reg=None, wts=None):
+        x = input.detach().contiguous()
+        B, T, D = x.shape
+        targets.check(B, T, D)
+        tg = targets.to(x.device)
+        lengths = torch.as_tensor(input_lengths)
+        plan = _plan.graph_plan(den_graph, D, x.device)
+        hscale, dnorm = _normaliser(avg, lengths, None if wts is None else wts[2])
+        L = _lib.lib()
+        # (2-byte network outputs go to the kernels as they are wherever the denominator's kernel family takes them; else up-cast once)
+        xk, _ = native._rows_as_given(x, lambda: L.pychain_hip_den_half_native(plan.stride, plan.slot_rows, int(plan.num_states), D, B, T))
+        K = int(tg.pdfs.size(2))
+
+        def evaluate(loss_scale):
+            den_objf, grad, dbad, totals = native.den_forward_backward(plan, xk, lengths, leaky_coefficient, grad_scale=hscale, totals=True)
+            if dnorm is not None:
+                native.rescale_(grad, torch.reciprocal(dnorm.to(grad.device)))
+            num_objf, tbad = native.post_targets(xk, lengths, tg.pdfs, tg.probs, grad=grad, grad_scale=-hscale, norm_dev=dnorm,
+                                                 den_objf=den_objf, loss_scale=loss_scale, totals=totals)
+            st = native.ChainLossState()
+            st.x, st.lengths_dev, st.grad, st.shape = xk, native._lengths_dev(lengths, x.device), grad, (B, T, D, K)
+            st.xent = st.reg = st.weighted = None
+            r = (den_objf, num_objf, torch.cat([dbad, tbad]), st, totals)
+            if reg is not None:
+                r = _with_output_reg(r, reg, True, hscale, dnorm, loss_scale)
+            if wts is not None:
+                r = _with_weights(r, wts, reg, 0.0, True, dnorm, loss_scale)
+            return r
+        _, _, bad, state, totals = evaluate(hscale)
+        # a second backward over a retained graph runs the passes again
+        ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: r[3])
+        ctx.state = state
+        ctx.in_dtype = input.dtype
+        out = _attach(native.totals_scalar(totals), totals, bad)     # bad_count int32[2]: denominator, targets
+        out = _attach_reg(out, state.reg, reg, hscale, dnorm)
+        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+
+    @staticmethod
+    def backward(ctx, objf_grad):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        state = _take_grad_buffer(ctx, "state")
+        if state is None:
+            state = ctx.again()
+        grad = native.rescale_(state.grad, objf_grad).to(ctx.in_dtype)
+        state.grad = None
+        return (grad,) + (None,) * 7
+
+
 class ChainLossXentFunction(torch.autograd.Function):
     """ChainLossFunction with a second differentiable input, the xent branch's output z: the numerator posteriors of the step
     become its cross-entropy targets inside the same fused call (include/pychain_hip.h: pychain_hip_xent).
@@ -550,7 +759,9 @@ class ChainLoss(nn.Module):
     detached.  c = 0 or no xent_output: exactly the loss without it.
     `output_l2_regularize` = l2, `out_of_range_regularize` = r: the loss gains (0.5 * l2 * sum x^2 + r * sum max(|x| - 30, 0)^2)
     [/ frames] over the live frames of the network output (output_regularizer); `loss.l2_term` and `loss.out_of_range_term` are
-    the two amounts, detached.  Both zero: exactly the loss without them, launch for launch."""
+    the two amounts, detached.  Both zero: exactly the loss without them, launch for launch.
+    `forward(x, lengths, targets)` with a PosteriorTargets where the numerator graphs go: posterior-target supervision
+    (teacher-student and semi-supervised LF-MMI), loss = (sum_b den_b - sum_b sum q clamp(x)) / N - _forward_targets."""
 
     def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, xent_regularize=0.0, output_l2_regularize=0.0,
                  out_of_range_regularize=0.0):
@@ -597,6 +808,8 @@ class ChainLoss(nn.Module):
         wts = None
         if utt_weights is not None or deriv_weights is not None:
             wts = _check_weights(utt_weights, deriv_weights, x.size(0), x.size(1), self.avg)
+        if isinstance(num_graphs, PosteriorTargets):
+            return self._forward_targets(x, x_lengths, num_graphs, xent_output, reg, wts)
         if not self._on_kernels(x, num_graphs):
             return self._forward_separate(x, x_lengths, num_graphs, z, reg, wts)
         if wts is not None:
@@ -608,6 +821,23 @@ class ChainLoss(nn.Module):
             return ChainLossFunction.apply(x, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg, reg, wts)
         return ChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg,
                                            self.xent_regularize, reg, wts)
+
+    def _forward_targets(self, x, x_lengths, targets, xent_output, reg, wts):
+        """`targets`: PosteriorTargets where the numerator graphs go (teacher-student and semi-supervised LF-MMI; Kaldi's "KL"
+        objective): loss = (sum_b den_b - sum_b num_b) / N with num_b = sum_{t < L_b} sum_k q_k clamp(x(b,t,pdf_k), -30, 30), plus
+        the regularisers, under the weights, N as for graphs.  The gradient is (gamma_den - q) / N.  Device tensors with
+        fused = True and a probability-domain denominator: PosteriorChainLossFunction; else the unfused route with
+        posterior_numerator in the numerator's place.  xent regularisation against posterior targets is not provided."""
+        if xent_output is not None:
+            raise ValueError("ChainLoss: xent_output together with PosteriorTargets is not supported (the xent term takes its "
+                             "targets from numerator graphs)")
+        targets.check(x.size(0), x.size(1), x.size(2))
+        if not (self.fused and x.is_cuda and not self.den_graph.log_domain):
+            return self._forward_separate(x, x_lengths, targets, None, reg, wts)
+        if wts is not None:
+            dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
+            wts = (dev(wts[0]), dev(wts[1]), wts[0])
+        return PosteriorChainLossFunction.apply(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, self.avg, reg, wts)
 
     def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts):
         """The unfused route and CPU tensors: two ChainFunction calls as in the reference, the cross-entropy term through
@@ -628,7 +858,10 @@ class ChainLoss(nn.Module):
         # more)
         xv = x if reg is None else x.view_as(x)
         den = ChainFunction.apply(xv, x_lengths, ChainGraphBatch(self.den_graph, x.size(0)), self.leaky_coefficient)
-        num = ChainFunction.apply(xv, x_lengths, num_graphs)
+        if isinstance(num_graphs, PosteriorTargets):
+            num = posterior_numerator(xv, x_lengths, num_graphs)
+        else:
+            num = ChainFunction.apply(xv, x_lengths, num_graphs)
         objf = -(num - den)
         if avg:
             objf = objf / x_lengths.sum()

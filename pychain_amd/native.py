@@ -471,6 +471,106 @@ def cpu_weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=N
     return weighted
 
 
+def _target_args(pdfs, probs, B, T, device):
+    """The int32 / float32 [B,T,K] targets an entry point reads, on `device`."""
+    if pdfs.dim() != 3 or tuple(pdfs.shape[:2]) != (B, T) or tuple(probs.shape) != tuple(pdfs.shape) or pdfs.shape[2] < 1:
+        raise ValueError("posterior targets must be [%d, %d, K >= 1] pdfs and probs of one shape, got %s and %s"
+                         % (B, T, tuple(pdfs.shape), tuple(probs.shape)))
+    return (pdfs.detach().to(device=device, dtype=torch.int32).contiguous(),
+            probs.detach().to(device=device, dtype=torch.float32).contiguous())
+
+
+def post_targets(x, lengths, pdfs, probs, grad=None, grad_scale=1.0, grad_scale_dev=None, norm_dev=None, den_objf=None,
+                 loss_scale=1.0, totals=None):
+    """Sparse posterior targets as the numerator on the GPU (include/pychain_hip.h: pychain_hip_post_targets), on the current
+    stream.  `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernel as it is; `pdfs` / `probs`: [B,T,K].  `grad` (x's dtype and
+    shape, or None: the objective only) gets s * q added at the addressed elements, s = grad_scale [* grad_scale_dev]
+    [/ norm_dev].  `totals` (with `den_objf` [B]): the device float[8] of the denominator call on this stream - [3] = sum den -
+    sum num, [0] = [4] = loss_scale * that [/ norm_dev], [2] += the bad entries.  Returns (num_objf [B], bad_count int32 [1])."""
+    _require_device(x, "nnet_output")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    L = _lib.lib()
+    dev = x.device
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        pd, pr = _target_args(pdfs, probs, B, T, dev)
+        if grad is not None and (grad.dtype != x.dtype or tuple(grad.shape) != (B, T, D) or not grad.is_contiguous() or grad.device != dev):
+            raise ValueError("post_targets needs a contiguous gradient of the network output's dtype, shape and device")
+        if totals is not None and den_objf is None:
+            raise ValueError("post_targets: totals need den_objf")
+        num_objf = torch.empty(B, dtype=torch.float32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        grad_scale_dev, norm_dev = _dev_scalar(grad_scale_dev, dev), _dev_scalar(norm_dev, dev)
+        ws = _workspace(L.pychain_hip_post_targets_workspace_bytes(B, T), dev, "post")
+        _lib.check(L.pychain_hip_post_targets(
+            x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), _ptr(grad),
+            float(grad_scale), _ptr(grad_scale_dev), _ptr(norm_dev), _ptr(den_objf), num_objf.data_ptr(), bad.data_ptr(),
+            float(loss_scale), _ptr(totals), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_post_targets")
+    return num_objf, bad
+
+
+def cpu_post_targets(x, lengths, pdfs, probs, grad=None, grad_scale=1.0, grad_scale_dev=None, norm=None, den_objf=None,
+                     loss_scale=1.0, totals=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_post_targets), fp32 rows, a contiguous float32 `grad` updated in
+    place.  `grad_scale_dev` / `norm`: None or float32 tensors of one element."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_post_targets is for CPU tensors; device tensors run on the HIP kernels")
+    xf, lc = _host_inputs(x, lengths)
+    B, T, D = xf.shape
+    pd, pr = _target_args(pdfs, probs, B, T, torch.device("cpu"))
+    if grad is not None and (grad.dtype != torch.float32 or tuple(grad.shape) != (B, T, D) or not grad.is_contiguous()):
+        raise ValueError("cpu_post_targets needs a contiguous float32 gradient of the network output's shape")
+    if totals is not None and den_objf is None:
+        raise ValueError("cpu_post_targets: totals need den_objf")
+    cf = lambda t: None if t is None else torch.as_tensor(t).detach().to(torch.float32).contiguous()
+    grad_scale_dev, norm, den_objf = cf(grad_scale_dev), cf(norm), cf(den_objf)
+    num_objf = torch.empty(B, dtype=torch.float32)
+    bad = torch.zeros(1, dtype=torch.int32)
+    _lib.check(_lib.lib().pychain_hip_cpu_post_targets(
+        xf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), _ptr(grad), float(grad_scale),
+        _ptr(grad_scale_dev), _ptr(norm), _ptr(den_objf), num_objf.data_ptr(), bad.data_ptr(), float(loss_scale), _ptr(totals),
+        int(CPU_THREADS)), "pychain_hip_cpu_post_targets")
+    return num_objf, bad
+
+
+def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
+    """Sparse targets out of dense posterior rows on the GPU (include/pychain_hip.h: pychain_hip_topk_rows), on the current
+    stream: `rows` [B,T,D] in fp32 / bf16 / fp16 as it is.  Returns (pdfs int32 [B,T,k], probs float32 [B,T,k])."""
+    _require_device(rows, "rows")
+    if rows.dtype not in _DTYPE_CODE:
+        raise ValueError("rows must be float32, bfloat16 or float16, got %s" % rows.dtype)
+    rows = rows.detach().contiguous()
+    B, T, D = rows.shape
+    _check_lengths(lengths, B, T)
+    dev = rows.device
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        pdfs = torch.empty(B, T, max(int(k), 0), dtype=torch.int32, device=dev)
+        probs = torch.empty(B, T, max(int(k), 0), dtype=torch.float32, device=dev)
+        _lib.check(_lib.lib().pychain_hip_topk_rows(
+            rows.data_ptr(), _DTYPE_CODE[rows.dtype], ld.data_ptr(), B, T, D, int(k), float(floor), int(bool(normalize)),
+            pdfs.data_ptr(), probs.data_ptr(), _stream(dev)), "pychain_hip_topk_rows")
+    return pdfs, probs
+
+
+def cpu_topk_rows(rows, lengths, k, floor=0.0, normalize=True):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_topk_rows), fp32 rows."""
+    if rows.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_topk_rows is for CPU tensors; device tensors run on the HIP kernels")
+    rf, lc = _host_inputs(rows, lengths)
+    B, T, D = rf.shape
+    pdfs = torch.empty(B, T, max(int(k), 0), dtype=torch.int32)
+    probs = torch.empty(B, T, max(int(k), 0), dtype=torch.float32)
+    _lib.check(_lib.lib().pychain_hip_cpu_topk_rows(
+        rf.data_ptr(), lc.data_ptr(), B, T, D, int(k), float(floor), int(bool(normalize)), pdfs.data_ptr(), probs.data_ptr(),
+        int(CPU_THREADS)), "pychain_hip_cpu_topk_rows")
+    return pdfs, probs
+
+
 def align(gt, graph_stride, num_states, x, lengths):
     """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""

@@ -42,7 +42,9 @@ def shard_batch(x, lengths, num_graphs, world_size, rank):
     xs = x.index_select(0, idx.to(x.device)) if x is not None else None
     ls = lengths.index_select(0, idx.to(lengths.device))
     gs = None
-    if num_graphs is not None:
+    if hasattr(num_graphs, "index_select"):              # loss.PosteriorTargets: the targets of this rank's utterances
+        gs = num_graphs.index_select(idx)
+    elif num_graphs is not None:
         gs = ChainGraphBatch.__new__(ChainGraphBatch)
         gs.__dict__.update(num_graphs.__dict__)
         gs._device_cache = {}
