@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 23
+#define PYCHAIN_HIP_ABI_VERSION 24
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -670,6 +670,52 @@ int pychain_hip_topk_rows(const void* rows, int rows_dtype, const int64_t* seq_l
                           int K, float floor, int normalize, int32_t* out_pdfs, float* out_probs, void* stream);
 int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int num_pdfs,
                               int K, float floor, int normalize, int32_t* out_pdfs, float* out_probs, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Cross-entropy against sparse targets (ABI 24): the xent term of chain training where the supervision is posterior targets (the
+ * teacher-student and semi-supervised recipes train their xent output against the same posteriors), and frame cross-entropy
+ * against an alignment (hard targets, K = 1).  z is a network output [B,T,D], RAW (not clamped), fp32 / bf16 / fp16; the
+ * targets are pdf(b,t,k) int32 and q(b,t,k) float, both [B,T,K], any K >= 1; lengths outside [1,T] are clamped, as everywhere.
+ * ENTRIES.  (b,t,k) is live when t < L_b and 0 <= pdf < D.  pdf < 0 is padding and is skipped; pdf >= D in a live frame is
+ * skipped and counted in bad_count (dev int32[1], written by the call).  Nothing with t >= L_b is ever read - neither entries
+ * nor rows of z: a NaN there is harmless.
+ * PER FRAME.  For every distinct pdf d of a frame, qd = the fp32 sum of the frame's q_k with pdf_k == d, in ascending k (the
+ * rule of pychain_hip_post_targets: a repeated pdf is handled where it occurs first, nothing races, nothing is atomic);
+ * s(t) = sum_d qd (targets need not sum to 1), and
+ *   objective(b,t) = sum_d qd z(t,d) - s(t) logsumexp_d z(t,.)          d / dz(b,t,d) = qd - s(t) softmax(z(t,.))_d
+ * Maximum, exp and log in fp32; the frame value is (double)dot - (double)s * (double)lse; the frames of a sequence are added in
+ * fp64 in a fixed order and rounded once into xent_objf_per_seq[b] (dev float [B]).  A LIVE FRAME WITHOUT A LIVE ENTRY has
+ * objective 0, its gradient row is stored as zeros and ITS ROW OF z IS NOT READ: sparse supervision costs the frames it
+ * supervises.  A NaN or an infinity in a row that is read does what log_softmax does: that sequence's objective is a NaN, the
+ * others are untouched.
+ * GRADIENT (`xent_grad` dev [B,T,D] in z's dtype, or NULL: the form without the store).  Every element is written ONCE:
+ *   grad_scale [* *grad_scale_dev] [/ *loss_norm_dev] * (qd - s softmax),   rounded at the store;   rows t >= L_b: zeros
+ * 2-byte rows are read as they are; the values, and the gradient before its rounding, are the bits of the same call on the
+ * up-cast fp32 z.  No float atomics: the same call gives the same bits.  Rows of more than 24 576 pdfs do not fit LDS and are
+ * re-read from memory by every pass (slow but complete).
+ *   workspace   dev, pychain_hip_xent_targets_workspace_bytes(B, T) bytes, 16-byte aligned
+ * K < 1, a NULL required pointer, or a z, xent_grad or workspace that is not 16-byte aligned: PYCHAIN_HIP_EINVAL.  The call runs
+ * the rows, the per-sequence sums and the bad count on `stream`; it depends on nothing else of a training step. */
+size_t pychain_hip_xent_targets_workspace_bytes(int B, int T);
+int pychain_hip_xent_targets(
+    const void* z, int z_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, void* xent_grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* xent_objf_per_seq, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream);
+/* The totals step behind it (what the *_xent entry points do for their own term): with S = sum_b xent_objf_per_seq[b] in fp64,
+ *   xent_totals[0] = loss_scale * S [/ *loss_norm_dev],   xent_totals[1] = S             (dev float[2], or NULL)
+ *   totals[0] = totals[4] = totals[0] + loss_coef * xent_totals[0],   totals[2] += *bad_count      (dev float[8], or NULL)
+ * - the other words of `totals` keep their bits; `bad_count` (dev int32[1]) may be NULL.  One small launch, in stream order
+ * behind whatever wrote `totals`. */
+int pychain_hip_xent_add_totals(const float* xent_objf_per_seq, int B, float loss_scale, const float* loss_norm_dev, float loss_coef,
+                                float* xent_totals, float* totals, const int32_t* bad_count, void* stream);
+/* the host twin: the same on host pointers (the two scalars too), fp32 z, qd by the same fp32 rule, fp64 log-sum-exp and sums,
+ * host threads over the sequences; zeros beyond a length; no workspace, no stream */
+int pychain_hip_cpu_xent_targets(
+    const float* z, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, float* xent_grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* xent_objf_per_seq, int32_t* bad_count, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 23
+ABI_VERSION = 24
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -98,6 +98,11 @@ _SIGNATURES = {
     "pychain_hip_cpu_post_targets": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _f, _vp, _i]),
     "pychain_hip_topk_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp]),
     "pychain_hip_cpu_topk_rows": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _i]),
+    # (ABI 24: cross-entropy of a network output against sparse targets - posterior targets, alignments - and its totals step)
+    "pychain_hip_xent_targets_workspace_bytes": (_sz, [_i, _i]),
+    "pychain_hip_xent_targets": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pychain_hip_xent_add_totals": (_i, [_vp, _i, _f, _vp, _f, _vp, _vp, _vp, _vp]),
+    "pychain_hip_cpu_xent_targets": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),

@@ -625,6 +625,73 @@ extern "C" int pychain_hip_cpu_post_targets(
   return PYCHAIN_HIP_OK;
 }
 
+// ---- sparse entries as cross-entropy targets of z (include/pychain_hip.h: pychain_hip_xent_targets; the device's xent.hip, sparse
+// source): qd by the same first-occurrence rule in fp32, everything else - maximum, log-sum-exp, the frame value, the sums - fp64
+extern "C" int pychain_hip_cpu_xent_targets(
+    const float* z, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, float* xent_grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* xent_objf_per_seq, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_xent_targets";
+  if (!z || !seq_lengths || !target_pdfs || !target_probs || !xent_objf_per_seq || !bad_count)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  g_cpu_calls++;
+  float sc = grad_scale_dev ? grad_scale * *grad_scale_dev : grad_scale;
+  if (loss_norm_dev) sc = sc / *loss_norm_dev;
+  std::vector<int> bads((size_t)B);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int64_t l = seq_lengths[b];
+    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    if (xent_grad) std::fill(xent_grad + (size_t)b * T * D, xent_grad + (size_t)(b + 1) * T * D, 0.f);
+    std::vector<int> pdf_of((size_t)K);               // the frame's distinct live pdfs, where each occurs first, and their qd
+    std::vector<float> qd_of((size_t)K);
+    double seq = 0.0;
+    int bad = 0;
+    for (int t = 0; t < L; t++) {
+      const size_t f = (size_t)b * T + t;
+      const int32_t* pd = target_pdfs + f * K;
+      const float* pr = target_probs + f * K;
+      int n = 0, nlive = 0;
+      for (int k = 0; k < K; k++) {
+        const int d = pd[k];
+        if (d < 0) continue;
+        if (d >= D) { bad++; continue; }
+        nlive++;
+        bool first = true;
+        for (int j = 0; j < k; j++) first = first && pd[j] != d;
+        if (!first) continue;
+        float qd = pr[k];
+        for (int j = k + 1; j < K; j++)
+          if (pd[j] == d) qd = post_add(qd, pr[j]);
+        pdf_of[n] = d; qd_of[n] = qd; n++;
+      }
+      if (nlive == 0) continue;                       // no objective, a zero row, and the row of z is not read
+      const float* zr = z + f * D;
+      double m = -std::numeric_limits<double>::infinity(), se = 0.0, s = 0.0, dot = 0.0;
+      for (int d = 0; d < D; d++) if ((double)zr[d] > m) m = (double)zr[d];          // (a NaN is passed by here and met by the sum)
+      for (int d = 0; d < D; d++) se += std::exp((double)zr[d] - m);
+      for (int i = 0; i < n; i++) { s += (double)qd_of[i]; dot += (double)qd_of[i] * (double)zr[pdf_of[i]]; }
+      const double lse = m + std::log(se);
+      seq += dot - s * lse;
+      if (xent_grad) {
+        float* o = xent_grad + f * D;
+        std::vector<double> row((size_t)D);
+        for (int d = 0; d < D; d++) row[d] = -(s * std::exp((double)zr[d] - lse));
+        for (int i = 0; i < n; i++) row[pdf_of[i]] += (double)qd_of[i];
+        for (int d = 0; d < D; d++) o[d] = (float)((double)sc * row[d]);
+      }
+    }
+    bads[b] = bad;
+    xent_objf_per_seq[b] = (float)seq;
+  });
+  int bad = 0;
+  for (int b = 0; b < B; b++) bad += bads[b];
+  *bad_count = bad;
+  return PYCHAIN_HIP_OK;
+}
+
 extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int D, int K, float floor,
                                          int normalize, int32_t* out_pdfs, float* out_probs, int num_threads) {
   const char* who = "cpu_topk_rows";

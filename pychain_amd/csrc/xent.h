@@ -20,6 +20,9 @@ struct XentArgs {
   // gamma, one of: the compact rows of the tile path (NumArgs::rows_ws / upd_ws / ucount_ws, rows of K words) ...
   const float* rows; const int32_t* upd; const int32_t* ucount; int K;
   const float* dense;        // ... or dense fp32 rows [B,T,D] (numerator graphs on the general kernels)
+  // ... or sparse entries [B,T,K] (pychain_hip_xent_targets: posterior targets; K above is then the entries per frame, logp is
+  // nullptr - every sequence has targets -, and frame_bad [B,T] receives the entries with pdf >= D of every live frame)
+  const int32_t* tpdfs; const float* tprobs; int32_t* frame_bad; int32_t* seq_bad;
   double* frame_objf;        // [B,T] scratch: the objective of every frame
   float* objf;               // [B] out
   int B, T, D;
@@ -29,9 +32,10 @@ size_t xent_frame_bytes(int B, int T);
 // one workgroup per frame (live frames: the row of z once, the gradient row once; frames beyond a length: zeros), then the
 // per-sequence sums of the frame objectives in fp64, fixed order
 hipError_t launch_xent_rows(const XentArgs& a, hipStream_t st, const char** why);
-// xent_totals[0] = loss_scale * S [/ *norm_dev], [1] = S = sum_b objf[b]; totals (or nullptr): [0] = [4] = totals[0] + coef * xent_totals[0]
+// xent_totals[0] = loss_scale * S [/ *norm_dev], [1] = S = sum_b objf[b]; totals (or nullptr): [0] = [4] = totals[0] + coef * xent_totals[0],
+// [2] += *bad_count (or nullptr)
 hipError_t launch_xent_totals(const float* objf, int B, float loss_scale, const float* norm_dev, float coef, float* xent_totals,
-                              float* totals, hipStream_t st);
+                              float* totals, hipStream_t st, const int32_t* bad_count = nullptr);
 // the event that joins the row kernel on a side stream back to the caller's stream (one per device and caller stream)
 hipEvent_t xent_join_event(hipStream_t caller);
 

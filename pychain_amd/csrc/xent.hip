@@ -6,12 +6,19 @@
 // words, scattered to the pdf-ids of upd_ws through that LDS row) or, for numerator graphs on the general kernels, from a
 // dense fp32 row; the gradient row is written ONCE, in z's type, scale multiplied in, rounded at the store.  Memory-bound:
 // (sizeof z + sizeof dz) D bytes per live frame against ~6 D flops and 2 D transcendentals.
+// A third source of targets (pychain_hip_xent_targets): sparse entries q(b,t,k) on pdf(b,t,k), K per frame -
+// posterior targets from a teacher or a lattice, or an alignment (K = 1).  The same row kernel; a pdf that occurs several times
+// in a frame is handled where it occurs first (the later q added to the first in ascending k: the rule of post.hip), so the
+// scatter into the LDS row neither races nor needs an atomic; a live frame without a live entry stores zeros and does not read z.
 #include <hip/hip_runtime.h>
 
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <utility>
 
+#include "../../include/pychain_hip.h"
+#include "common.h"
 #include "device_utils.h"
 #include "xent.h"
 
@@ -19,7 +26,8 @@ namespace pychain_hip {
 namespace {
 
 constexpr int kXnNT = 256;
-constexpr size_t kXnMaxLdsRow = 96 * 1024;      // rows beyond: re-read from global memory (dense gamma only)
+constexpr size_t kXnMaxLdsRow = 96 * 1024;      // rows beyond: re-read from global memory (dense gamma and sparse entries)
+constexpr int kXnCompact = 0, kXnDense = 1, kXnSparse = 2;      // where the targets of a frame come from
 
 template <int ZH>
 __device__ __forceinline__ void z_load4(const void* z, size_t e, float (&v)[4]) {
@@ -73,19 +81,65 @@ __device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float (
   __syncthreads();
 }
 
+// sparse entries: the two integer counts of a frame over the workgroup
+__device__ __forceinline__ void block_sum2i(int& a, int& b, int (*red)[4]) {
+  for (int o = 32; o > 0; o >>= 1) { a += __shfl_xor(a, o); b += __shfl_xor(b, o); }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; }
+  __syncthreads();
+  a = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
+  b = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+  __syncthreads();
+}
+// entry k of a frame's K sparse entries: true where it is live (0 <= pdf < D) and the FIRST of its pdf in the frame; then d = the
+// pdf and qd = the fp32 sum of the frame's q with that pdf, in ascending k (nothing to contract: adds only)
+__device__ __forceinline__ bool sparse_first(const int32_t* pd, const float* pr, int K, int k, int D, int& d, float& qd) {
+  d = pd[k];
+  if ((unsigned)d >= (unsigned)D) return false;
+  for (int j = 0; j < k; j++)
+    if (pd[j] == d) return false;
+  qd = pr[k];
+  for (int j = k + 1; j < K; j++)
+    if (pd[j] == d) qd += pr[j];
+  return true;
+}
+
 // ZH: z's element type; VEC: rows of a multiple of four elements (vector loads and stores); GRAD: the gradient row is stored;
-// DENSE: gamma from a dense fp32 row instead of the compact one; INLDS: the row fits LDS (else DENSE && !VEC: every pass reads z
-// again - rows of more than 24 576 pdfs, which only the general numerator kernels take)
-template <int ZH, bool VEC, bool GRAD, bool DENSE, bool INLDS>
+// SRC: gamma from the compact occupancy row (kXnCompact), from a dense fp32 row (kXnDense) or from sparse entries (kXnSparse);
+// INLDS: the row fits LDS (else !VEC and not compact: every pass reads z again - rows of more than 24 576 pdfs, which only the
+// general numerator kernels and sparse entries take)
+template <int ZH, bool VEC, bool GRAD, int SRC, bool INLDS>
 __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
+  constexpr bool DENSE = SRC == kXnDense, SPARSE = SRC == kXnSparse;
   extern __shared__ __attribute__((aligned(16))) float srow[];
   __shared__ float red[3][4];
   const int tid = threadIdx.x, t = blockIdx.x, b = blockIdx.y, D = a.D, T = a.T;
   const int L = seq_len(a.lengths, b, T);
   const size_t fr = (size_t)b * T + t, row = fr * D;
-  const double logp = a.logp[b];
-  // a sequence without an admissible path (logP = -inf, or NaN) has gamma = 0: no objective, zero rows
-  if (!(t < L && logp - logp == 0.0)) {
+  bool live = t < L;
+  if constexpr (!SPARSE) {
+    // a sequence without an admissible path (logP = -inf, or NaN) has gamma = 0: no objective, zero rows
+    const double logp = a.logp[b];
+    live = live && logp - logp == 0.0;
+  }
+  const int32_t* tpd = SPARSE ? a.tpdfs + fr * a.K : nullptr;      // (only formed here: entries of frames t >= L are never read)
+  const float* tpr = SPARSE ? a.tprobs + fr * a.K : nullptr;
+  if constexpr (SPARSE) {
+    if (live) {
+      // the frame's live entries and the ones that name a pdf the row does not have; a frame without a live entry stays zero
+      // and its row of z is not read
+      __shared__ int redi[2][4];
+      int nlive = 0, nbad = 0;
+      for (int u = tid; u < a.K; u += kXnNT) {
+        const int d = tpd[u];
+        if (d >= D) nbad++;
+        else if (d >= 0) nlive++;
+      }
+      block_sum2i(nlive, nbad, redi);
+      if (tid == 0) a.frame_bad[fr] = nbad;
+      live = nlive != 0;
+    }
+  }
+  if (!live) {
     if constexpr (GRAD) {
       if constexpr (VEC) { for (int e = tid * 4; e < D; e += 4 * kXnNT) z_store4<ZH>(a.grad, row + e, 0.f, 0.f, 0.f, 0.f); }
       else { for (int e = tid; e < D; e += kXnNT) z_store1<ZH>(a.grad, row + e, 0.f); }
@@ -125,10 +179,17 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
       }
     }
   }
-  const int U = DENSE ? 0 : min(a.ucount[b], a.K);
-  const float* crow = DENSE ? nullptr : a.rows + fr * a.K;
-  const int32_t* upd = DENSE ? nullptr : a.upd + (size_t)b * a.K;
-  if constexpr (!DENSE) {
+  const int U = SRC != kXnCompact ? 0 : min(a.ucount[b], a.K);
+  const float* crow = SRC != kXnCompact ? nullptr : a.rows + fr * a.K;
+  const int32_t* upd = SRC != kXnCompact ? nullptr : a.upd + (size_t)b * a.K;
+  if constexpr (SPARSE) {
+    for (int u = tid; u < a.K; u += kXnNT) {         // (O(K) per entry: K is 1 to 64 in real targets; any K is covered)
+      int n;
+      float g;
+      if (sparse_first(tpd, tpr, a.K, u, D, n, g)) { s += g; dot = fmaf(g, zv(n), dot); }
+    }
+  }
+  if constexpr (SRC == kXnCompact) {
     for (int u = tid; u < U; u += kXnNT) {
       const float g = crow[u];
       const int n = upd[u];
@@ -142,16 +203,25 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
   // 3. the gradient row, once: scale * (gamma - s softmax(z)), rounded to z's type at the store
   float sc = a.scale_dev ? a.scale * *a.scale_dev : a.scale;
   if (a.norm_dev) sc = sc / *a.norm_dev;
-  if constexpr (!DENSE) {
+  constexpr bool SCATTER = !DENSE && INLDS;          // the targets are added into the LDS row ahead of the one store
+  if constexpr (SCATTER) {
     for (int e = e0; e < D; e += estep) {
 #pragma unroll
       for (int i = 0; i < ew; i++) srow[e + i] = -(s * expf(srow[e + i] - lse));
     }
     __syncthreads();
-    for (int u = tid; u < U; u += kXnNT) {           // (the distinct pdfs of the sequence: one thread per word)
-      const float g = crow[u];
-      const int n = upd[u];
-      if (g != 0.f && (unsigned)n < (unsigned)D) srow[n] += g;
+    if constexpr (SPARSE) {
+      for (int u = tid; u < a.K; u += kXnNT) {       // (the distinct pdfs of the frame: one thread per pdf, where it occurs first)
+        int n;
+        float g;
+        if (sparse_first(tpd, tpr, a.K, u, D, n, g)) srow[n] += g;
+      }
+    } else {
+      for (int u = tid; u < U; u += kXnNT) {         // (the distinct pdfs of the sequence: one thread per word)
+        const float g = crow[u];
+        const int n = upd[u];
+        if (g != 0.f && (unsigned)n < (unsigned)D) srow[n] += g;
+      }
     }
     __syncthreads();
   }
@@ -160,10 +230,21 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
 #pragma unroll
     for (int i = 0; i < ew; i++) {
       if constexpr (DENSE) o[i] = sc * fmaf(-s, expf(zv(e + i) - lse), a.dense[row + e + i]);
-      else o[i] = sc * srow[e + i];
+      else if constexpr (SCATTER) o[i] = sc * srow[e + i];
+      else o[i] = sc * -(s * expf(zv(e + i) - lse));
     }
     if constexpr (VEC) z_store4<ZH>(a.grad, row + e, o[0], o[1], o[2], o[3]);
     else z_store1<ZH>(a.grad, row + e, o[0]);
+  }
+  if constexpr (SPARSE && !INLDS) {
+    // the re-reading form: the addressed elements are patched behind the row store (the barrier orders this workgroup's two
+    // stores to one address), from z again and not from the rounded gradient - the same operations as the form above
+    __syncthreads();
+    for (int u = tid; u < a.K; u += kXnNT) {
+      int n;
+      float g;
+      if (sparse_first(tpd, tpr, a.K, u, D, n, g)) z_store1<ZH>(a.grad, row + n, sc * (-(s * expf(zv(n) - lse)) + g));
+    }
   }
 }
 
@@ -179,8 +260,29 @@ __global__ __launch_bounds__(kXnNT) void xent_seq_sum_kernel(const double* frame
   if (threadIdx.x == 0) objf[b] = (float)((part[0] + part[1]) + (part[2] + part[3]));
 }
 
+// sparse entries: seq_bad[b] = the live frames' entries that name a pdf the row does not have, then their sum over the batch
+__global__ __launch_bounds__(kXnNT) void xent_seq_bad_kernel(const int32_t* frame_bad, const int64_t* lengths, int T, int32_t* seq_bad) {
+  __shared__ int part[4];
+  const int b = blockIdx.x, L = seq_len(lengths, b, T);
+  int acc = 0;
+  for (int t = threadIdx.x; t < L; t += kXnNT) acc += frame_bad[(size_t)b * T + t];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) seq_bad[b] = (part[0] + part[1]) + (part[2] + part[3]);
+}
+__global__ __launch_bounds__(kXnNT) void xent_bad_total_kernel(const int32_t* seq_bad, int B, int32_t* bad_count) {
+  __shared__ int part[4];
+  int acc = 0;
+  for (int i = threadIdx.x; i < B; i += kXnNT) acc += seq_bad[i];
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) *bad_count = (part[0] + part[1]) + (part[2] + part[3]);
+}
+
 __global__ __launch_bounds__(kXnNT) void xent_totals_kernel(const float* objf, int B, float loss_scale, const float* norm_dev, float coef,
-                                                           float* xent_totals, float* totals) {
+                                                           float* xent_totals, float* totals, const int32_t* bad_count) {
   __shared__ double part[4];
   double acc = 0.0;
   for (int i = threadIdx.x; i < B; i += kXnNT) acc += (double)objf[i];
@@ -195,13 +297,14 @@ __global__ __launch_bounds__(kXnNT) void xent_totals_kernel(const float* objf, i
     if (totals) {                                    // the full loss: LF-MMI + coef * xent
       const float full = (float)((double)totals[0] + (double)coef * sc);
       totals[0] = full; totals[4] = full;
+      if (bad_count) totals[2] = totals[2] + (float)*bad_count;
     }
   }
 }
 
-template <int ZH, bool VEC, bool GRAD, bool DENSE, bool INLDS>
+template <int ZH, bool VEC, bool GRAD, int SRC, bool INLDS>
 hipError_t launch_rows_as(const XentArgs& a, size_t lds, hipStream_t st) {
-  auto k = xent_row_kernel<ZH, VEC, GRAD, DENSE, INLDS>;
+  auto k = xent_row_kernel<ZH, VEC, GRAD, SRC, INLDS>;
   if (lds > 48 * 1024) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -212,10 +315,12 @@ hipError_t launch_rows_as(const XentArgs& a, size_t lds, hipStream_t st) {
 template <int ZH, bool VEC, bool GRAD>
 hipError_t launch_rows_g(const XentArgs& a, size_t lds, bool inlds, hipStream_t st) {
   if (!inlds) {
-    if constexpr (!VEC) return launch_rows_as<ZH, false, GRAD, true, false>(a, 0, st);
+    if constexpr (!VEC) return a.tpdfs ? launch_rows_as<ZH, false, GRAD, kXnSparse, false>(a, 0, st)
+                                       : launch_rows_as<ZH, false, GRAD, kXnDense, false>(a, 0, st);
     else return hipErrorInvalidValue;
   }
-  return a.dense ? launch_rows_as<ZH, VEC, GRAD, true, true>(a, lds, st) : launch_rows_as<ZH, VEC, GRAD, false, true>(a, lds, st);
+  if (a.tpdfs) return launch_rows_as<ZH, VEC, GRAD, kXnSparse, true>(a, lds, st);
+  return a.dense ? launch_rows_as<ZH, VEC, GRAD, kXnDense, true>(a, lds, st) : launch_rows_as<ZH, VEC, GRAD, kXnCompact, true>(a, lds, st);
 }
 template <int ZH>
 hipError_t launch_rows_z(const XentArgs& a, size_t lds, bool vec, bool inlds, hipStream_t st) {
@@ -231,19 +336,25 @@ hipError_t launch_xent_rows(const XentArgs& a, hipStream_t st, const char** why)
   if (a.B > 65535) { *why = "the cross-entropy row kernel takes at most 65535 sequences per call"; return hipErrorInvalidValue; }
   const size_t row_bytes = 4 * (((size_t)a.D + 3) & ~(size_t)3);
   bool inlds = row_bytes <= kXnMaxLdsRow;
-  if (!inlds && !a.dense) { *why = "a row of the cross-entropy output does not fit LDS beside compact occupancy rows"; return hipErrorInvalidValue; }
+  if (!inlds && !a.dense && !a.tpdfs) { *why = "a row of the cross-entropy output does not fit LDS beside compact occupancy rows"; return hipErrorInvalidValue; }
   const bool vec = inlds && a.D % 4 == 0;
   const size_t lds = inlds ? row_bytes : 0;
   hipError_t e = a.z_half == kXF32 ? launch_rows_z<kXF32>(a, lds, vec, inlds, st)
                : a.z_half == kXBf16 ? launch_rows_z<kXBf16>(a, lds, vec, inlds, st) : launch_rows_z<kXF16>(a, lds, vec, inlds, st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(xent_seq_sum_kernel, dim3(a.B), dim3(kXnNT), 0, st, a.frame_objf, a.lengths, a.T, a.objf);
+  if (a.tpdfs) hipLaunchKernelGGL(xent_seq_bad_kernel, dim3(a.B), dim3(kXnNT), 0, st, a.frame_bad, a.lengths, a.T, a.seq_bad);
+  return hipGetLastError();
+}
+
+hipError_t launch_xent_bad_total(const int32_t* seq_bad, int B, int32_t* bad_count, hipStream_t st) {
+  hipLaunchKernelGGL(xent_bad_total_kernel, dim3(1), dim3(kXnNT), 0, st, seq_bad, B, bad_count);
   return hipGetLastError();
 }
 
 hipError_t launch_xent_totals(const float* objf, int B, float loss_scale, const float* norm_dev, float coef, float* xent_totals,
-                              float* totals, hipStream_t st) {
-  hipLaunchKernelGGL(xent_totals_kernel, dim3(1), dim3(kXnNT), 0, st, objf, B, loss_scale, norm_dev, coef, xent_totals, totals);
+                              float* totals, hipStream_t st, const int32_t* bad_count) {
+  hipLaunchKernelGGL(xent_totals_kernel, dim3(1), dim3(kXnNT), 0, st, objf, B, loss_scale, norm_dev, coef, xent_totals, totals, bad_count);
   return hipGetLastError();
 }
 
@@ -259,3 +370,59 @@ hipEvent_t xent_join_event(hipStream_t caller) {
 }
 
 }  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+// ---- sparse entries as the targets: the entry points (include/pychain_hip.h: pychain_hip_xent_targets) -----------------------
+namespace {
+inline size_t xt_align(size_t n) { return (n + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" size_t pychain_hip_xent_targets_workspace_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  // frame objectives (fp64), the frames' bad entries, the sequences' - and the slack of the alignment to 256 bytes
+  return xt_align(xent_frame_bytes(B, T)) + xt_align(4 * (size_t)B * T) + xt_align(4 * (size_t)B) + 256;
+}
+
+extern "C" int pychain_hip_xent_targets(
+    const void* z, int z_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, void* xent_grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* xent_objf_per_seq, int32_t* bad_count, void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "xent_targets";
+  if (z_dtype < PYCHAIN_HIP_F32 || z_dtype > PYCHAIN_HIP_F16) return fail(PYCHAIN_HIP_EINVAL, "%s: unknown z_dtype %d", who, z_dtype);
+  if (!z || !seq_lengths || !target_pdfs || !target_probs || !xent_objf_per_seq || !bad_count || !workspace)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if (((uintptr_t)z | (uintptr_t)xent_grad | (uintptr_t)workspace) & 15)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: z, xent_grad and workspace must be 16-byte aligned", who);
+  const size_t need = pychain_hip_xent_targets_workspace_bytes(B, T);
+  if (workspace_bytes < need) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  XentArgs a;
+  memset(&a, 0, sizeof(a));
+  a.z = z; a.z_half = z_dtype; a.grad = xent_grad; a.scale = grad_scale; a.scale_dev = grad_scale_dev; a.norm_dev = loss_norm_dev;
+  a.lengths = seq_lengths; a.tpdfs = target_pdfs; a.tprobs = target_probs; a.K = K;
+  a.frame_objf = (double*)ws;
+  a.frame_bad = (int32_t*)(ws + xt_align(xent_frame_bytes(B, T)));
+  a.seq_bad = (int32_t*)(ws + xt_align(xent_frame_bytes(B, T)) + xt_align(4 * (size_t)B * T));
+  a.objf = xent_objf_per_seq; a.B = B; a.T = T; a.D = D;
+  const char* why = "";
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_xent_rows(a, st, &why);
+  if (e == hipSuccess) e = launch_xent_bad_total(a.seq_bad, B, bad_count, st);
+  if (e != hipSuccess) return fail(*why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, *why ? why : hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_xent_add_totals(const float* xent_objf_per_seq, int B, float loss_scale, const float* loss_norm_dev, float loss_coef,
+                                           float* xent_totals, float* totals, const int32_t* bad_count, void* stream) {
+  const char* who = "xent_add_totals";
+  if (!xent_objf_per_seq || (!xent_totals && !totals)) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad size B=%d", who, B);
+  const hipError_t e = launch_xent_totals(xent_objf_per_seq, B, loss_scale, loss_norm_dev, loss_coef, xent_totals, totals, (hipStream_t)stream,
+                                          bad_count);
+  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}

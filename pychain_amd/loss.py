@@ -26,7 +26,8 @@ from .graph import ChainGraphBatch
 
 __all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent",
            "output_regularizer", "weight_rows", "ChainLoss", "PosteriorTargets", "posterior_targets", "occupancies",
-           "posterior_numerator", "PosteriorNumeratorFunction", "PosteriorChainLossFunction"]
+           "posterior_numerator", "PosteriorNumeratorFunction", "PosteriorChainLossFunction", "PosteriorChainLossXentFunction",
+           "PosteriorXentFunction", "posterior_xent"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -611,6 +612,19 @@ class PosteriorTargets(object):
         return cls._of(*native.cpu_topk_rows(post, lengths, k, floor, normalize))
 
 
+    @classmethod
+    def from_alignment(cls, ali):
+        """Hard targets out of an alignment (align.viterbi_align): K = 1, pdfs = ali.pdfs[..., None] with -1 beyond a length and
+        for the utterances that did not align (ali.ok False), probs = 1.  posterior_xent(z, lengths, these) is then frame
+        cross-entropy against the alignment."""
+        pdfs = ali.pdfs.detach()                                   # (-1 beyond a length already: align.viterbi_align)
+        B, T = pdfs.shape
+        dev = pdfs.device
+        live = (pdfs >= 0) & ali.ok.to(dev).to(torch.bool)[:, None]
+        pd = torch.where(live, pdfs.to(torch.int32), torch.full((), -1, dtype=torch.int32, device=dev))
+        return cls._of(pd[..., None].contiguous(), torch.ones(B, T, 1, dtype=torch.float32, device=dev))
+
+
 def occupancies(x, lengths, graphs, leaky_coefficient=1e-5):
     """The dense occupancies gamma(b,t,d) of (x, graphs) - what ChainFunction's backward hands out for an upstream gradient of 1 -
     as a [B,T,D] tensor, not differentiable: of a probability-domain graph (a ChainGraph or a ChainGraphBatch: the denominator
@@ -675,6 +689,138 @@ def posterior_numerator(x, lengths, targets):
     return PosteriorNumeratorFunction.apply(x, lengths, targets)
 
 
+class PosteriorXentFunction(torch.autograd.Function):
+    """sum_b xent_objf[b] of include/pychain_hip.h (pychain_hip_xent_targets): sparse targets as cross-entropy targets of
+    xent_output.  Differentiable in xent_output only.  The gradient is written by the forward call for an upstream gradient of
+    1; backward rescales, a second backward over a retained graph evaluates again."""
+
+    @staticmethod
+    def forward(ctx, xent_output, lengths, targets):
+        z = xent_output.detach()
+        targets.check(*z.shape)
+        want = bool(ctx.needs_input_grad[0])
+        evaluate = lambda: PosteriorXentFunction._evaluate(z, lengths, targets, want)
+        res, bad = evaluate()
+        ctx.grad_buf = res.grad
+        ctx.again = _recompute(z, evaluate, lambda r: r[0].grad)
+        ctx.in_dtype = xent_output.dtype
+        out = res.totals[1].clone()
+        out.xent_objf_per_seq = res.objf
+        out.bad_count = bad
+        return out
+
+    @staticmethod
+    def _evaluate(z, lengths, targets, want):
+        tg = targets.to(z.device)
+        if not z.is_cuda:
+            return native.cpu_xent_targets(z, lengths, tg.pdfs, tg.probs, with_grad=want)
+        zk = z if z.dtype in native._DTYPE_CODE else z.float()
+        res, bad = native.xent_targets(zk, lengths, tg.pdfs, tg.probs, with_grad=want)
+        return native.xent_add_totals(res), bad
+
+    @staticmethod
+    def backward(ctx, g):
+        return _grad_written_in_forward(ctx, g), None, None
+
+
+def posterior_xent(xent_output, lengths, targets):
+    """The cross-entropy objective of a network output against sparse targets - PosteriorTargets: a teacher's or a lattice's
+    posteriors (the xent term of teacher-student and semi-supervised chain training), or PosteriorTargets.from_alignment:
+    frame cross-entropy against an alignment -
+        sum_b sum_{t < L_b} sum_k q(b,t,k) log_softmax(xent_output)(b,t,pdf(b,t,k))
+    as a 0-dim tensor, differentiable in xent_output only.  xent_output is read raw (no clamp), in its own dtype.  A live frame
+    without an entry costs nothing: its row is not read.  Device tensors run on the HIP kernel (one pass over xent_output),
+    CPU tensors on the host twin.  `.xent_objf_per_seq` of the result: the [B] per-sequence objectives; `.bad_count`: the
+    entries that name a pdf xent_output does not have."""
+    if not isinstance(targets, PosteriorTargets):
+        raise ValueError("posterior_xent takes PosteriorTargets, got %s" % type(targets).__name__)
+    return PosteriorXentFunction.apply(xent_output, lengths, targets)
+
+
+def _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg,
+                       xent_regularize, reg, wts):
+    """forward() of PosteriorChainLossFunction (`xent_output` None) and of PosteriorChainLossXentFunction."""
+    x = input.detach().contiguous()
+    z = None if xent_output is None else xent_output.detach()
+    B, T, D = x.shape
+    targets.check(B, T, D)
+    tg = targets.to(x.device)
+    lengths = torch.as_tensor(input_lengths)
+    plan = _plan.graph_plan(den_graph, D, x.device)
+    hscale, dnorm = _normaliser(avg, lengths, None if wts is None else wts[2])
+    L = _lib.lib()
+    # (2-byte network outputs go to the kernels as they are wherever the denominator's kernel family takes them; else up-cast once)
+    xk, _ = native._rows_as_given(x, lambda: L.pychain_hip_den_half_native(plan.stride, plan.slot_rows, int(plan.num_states), D, B, T))
+    K = int(tg.pdfs.size(2))
+    c = 0.0 if z is None else float(xent_regularize)
+    if z is not None:
+        if tuple(z.shape) != (B, T, D):
+            raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(z.shape), (B, T, D)))
+        native._require_device(z, "xent_output")
+        xent_targets.check(B, T, D)
+        ztg = xent_targets.to(x.device)
+        zk = z if z.dtype in native._DTYPE_CODE else z.float()
+        z_grad = bool(ctx.needs_input_grad[1])
+
+    def evaluate(loss_scale):
+        den_objf, grad, dbad, totals = native.den_forward_backward(plan, xk, lengths, leaky_coefficient, grad_scale=hscale, totals=True)
+        if dnorm is not None:
+            native.rescale_(grad, torch.reciprocal(dnorm.to(grad.device)))
+        num_objf, tbad = native.post_targets(xk, lengths, tg.pdfs, tg.probs, grad=grad, grad_scale=-hscale, norm_dev=dnorm,
+                                             den_objf=den_objf, loss_scale=loss_scale, totals=totals)
+        st = native.ChainLossState()
+        st.x, st.lengths_dev, st.grad, st.shape = xk, native._lengths_dev(lengths, x.device), grad, (B, T, D, K)
+        st.xent = st.reg = st.weighted = None
+        bads = [dbad, tbad]
+        if z is not None:
+            # the xent output's pass (its gradient for the scale -c [/ N]) and its term into the totals post_targets just wrote
+            # (on the caller's stream: the same pass on a side stream beside the denominator call was measured and gained
+            # nothing - DESIGN.md §3.23)
+            xe, xbad = native.xent_targets(zk, lengths, ztg.pdfs, ztg.probs, with_grad=z_grad, grad_scale=-c * hscale, norm_dev=dnorm)
+            st.xent = native.xent_add_totals(xe, xbad, loss_scale, dnorm, -c, totals)
+            bads.append(xbad)
+        r = (den_objf, num_objf, torch.cat(bads), st, totals)
+        if reg is not None:
+            r = _with_output_reg(r, reg, True, hscale, dnorm, loss_scale)
+        if wts is not None:
+            r = _with_weights(r, wts, reg, c, True, dnorm, loss_scale)
+        return r
+    _, _, bad, state, totals = evaluate(hscale)
+    # a second backward over a retained graph runs the passes again
+    ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: r[3])
+    ctx.state = state
+    ctx.in_dtype = input.dtype
+    ctx.z = z
+    if z is not None:
+        ctx.z_version, ctx.z_dtype = z._version, xent_output.dtype
+    out = _attach(native.totals_scalar(totals), totals, bad)     # bad_count int32[2]: denominator, targets [, xent targets]
+    if z is not None:
+        out.xent_objf = state.xent.totals[0]                     # sum_b xent_objf[b] [/ N]: detached, for logging
+        out.xent_objf_per_seq = state.xent.objf
+    out = _attach_reg(out, state.reg, reg, hscale, dnorm)
+    return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+
+
+def _posterior_backward(ctx, objf_grad):
+    """backward() of the two: (gradient of the chain output, gradient of the xent output), None where it is not wanted."""
+    want_z = ctx.z is not None and ctx.needs_input_grad[1]
+    if not (ctx.needs_input_grad[0] or want_z):
+        return None, None
+    state = _take_grad_buffer(ctx, "state")
+    if state is None:
+        if ctx.z is not None and ctx.z._version != ctx.z_version:
+            raise RuntimeError("one of the variables needed for gradient computation has been modified by an inplace operation: "
+                               "the xent output given to the LF-MMI loss (second backward over a retained graph)")
+        state = ctx.again()
+    grad = zgrad = None
+    if ctx.needs_input_grad[0]:
+        grad = native.rescale_(state.grad, objf_grad).to(ctx.in_dtype)
+    if want_z:
+        zgrad = native.rescale_(state.xent.grad, objf_grad).to(ctx.z_dtype)
+    state.grad = state.xent = None
+    return grad, zgrad
+
+
 class PosteriorChainLossFunction(torch.autograd.Function):
     """ChainLoss on device tensors with PosteriorTargets where the numerator graphs go: loss = (sum_b den_b - sum_b num_b) / N, its
     gradient (gamma_den - q) / N written ONCE by the forward call for an upstream gradient of 1 - the denominator call
@@ -687,52 +833,29 @@ class PosteriorChainLossFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, input_lengths, den_graph, targets, leaky_coefficient, avg, reg=None, wts=None):
-        x = input.detach().contiguous()
-        B, T, D = x.shape
-        targets.check(B, T, D)
-        tg = targets.to(x.device)
-        lengths = torch.as_tensor(input_lengths)
-        plan = _plan.graph_plan(den_graph, D, x.device)
-        hscale, dnorm = _normaliser(avg, lengths, None if wts is None else wts[2])
-        L = _lib.lib()
-        # (2-byte network outputs go to the kernels as they are wherever the denominator's kernel family takes them; else up-cast once)
-        xk, _ = native._rows_as_given(x, lambda: L.pychain_hip_den_half_native(plan.stride, plan.slot_rows, int(plan.num_states), D, B, T))
-        K = int(tg.pdfs.size(2))
-
-        def evaluate(loss_scale):
-            den_objf, grad, dbad, totals = native.den_forward_backward(plan, xk, lengths, leaky_coefficient, grad_scale=hscale, totals=True)
-            if dnorm is not None:
-                native.rescale_(grad, torch.reciprocal(dnorm.to(grad.device)))
-            num_objf, tbad = native.post_targets(xk, lengths, tg.pdfs, tg.probs, grad=grad, grad_scale=-hscale, norm_dev=dnorm,
-                                                 den_objf=den_objf, loss_scale=loss_scale, totals=totals)
-            st = native.ChainLossState()
-            st.x, st.lengths_dev, st.grad, st.shape = xk, native._lengths_dev(lengths, x.device), grad, (B, T, D, K)
-            st.xent = st.reg = st.weighted = None
-            r = (den_objf, num_objf, torch.cat([dbad, tbad]), st, totals)
-            if reg is not None:
-                r = _with_output_reg(r, reg, True, hscale, dnorm, loss_scale)
-            if wts is not None:
-                r = _with_weights(r, wts, reg, 0.0, True, dnorm, loss_scale)
-            return r
-        _, _, bad, state, totals = evaluate(hscale)
-        # a second backward over a retained graph runs the passes again
-        ctx.again = _recompute(x, lambda: evaluate(1.0), lambda r: r[3])
-        ctx.state = state
-        ctx.in_dtype = input.dtype
-        out = _attach(native.totals_scalar(totals), totals, bad)     # bad_count int32[2]: denominator, targets
-        out = _attach_reg(out, state.reg, reg, hscale, dnorm)
-        return out if wts is None else _attach_weighted(out, state, totals, reg, hscale, dnorm)
+        return _posterior_forward(ctx, input, None, input_lengths, den_graph, targets, None, leaky_coefficient, avg, 0.0, reg, wts)
 
     @staticmethod
     def backward(ctx, objf_grad):
-        if not ctx.needs_input_grad[0]:
-            return (None,) * 8
-        state = _take_grad_buffer(ctx, "state")
-        if state is None:
-            state = ctx.again()
-        grad = native.rescale_(state.grad, objf_grad).to(ctx.in_dtype)
-        state.grad = None
-        return (grad,) + (None,) * 7
+        return (_posterior_backward(ctx, objf_grad)[0],) + (None,) * 7
+
+
+class PosteriorChainLossXentFunction(torch.autograd.Function):
+    """PosteriorChainLossFunction with a second differentiable input, the xent branch's output z, trained by cross-entropy against
+    `xent_targets` (usually the very targets of the numerator; include/pychain_hip.h: pychain_hip_xent_targets; DESIGN.md
+    §3.23): loss = LF-MMI_KL - c * xent, both divided by N when `avg`.  Behind post_targets on the same stream:
+    native.xent_targets writes z's gradient (scale -c [/ N], an upstream gradient of 1), native.xent_add_totals adds the term to
+    the step's totals; backward rescales.  The gradient of the chain output is PosteriorChainLossFunction's, bit for bit."""
+
+    @staticmethod
+    def forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg, xent_regularize,
+                reg=None, wts=None):
+        return _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg,
+                                  xent_regularize, reg, wts)
+
+    @staticmethod
+    def backward(ctx, objf_grad):
+        return _posterior_backward(ctx, objf_grad) + (None,) * 9
 
 
 class ChainLossXentFunction(torch.autograd.Function):
@@ -786,8 +909,12 @@ class ChainLoss(nn.Module):
     def _on_kernels(self, x, num_graphs):
         return self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain
 
-    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None):
-        """`utt_weights` u (float [B]; Kaldi: Supervision::weight) scale each utterance's objective, its derivatives and the
+    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None, xent_targets=None):
+        """`xent_targets` (with PosteriorTargets where the numerator graphs go, and `xent_output`): the PosteriorTargets the xent
+        output is trained against - usually the same object, `criterion(y, lengths, targets, xent_output=z, xent_targets=targets)`;
+        the loss is LF-MMI_KL - c * xent (posterior_xent), `loss.bad_count` gains a third word, the xent entries that name a pdf
+        z does not have.  Graph numerators bring their own posteriors: `xent_targets` with them raises.
+        `utt_weights` u (float [B]; Kaldi: Supervision::weight) scale each utterance's objective, its derivatives and the
         normaliser: loss = sum_b u_b term_b / N with N = sum_b u_b L_b under avg=True (else 1), term_b the utterance's whole
         objective (LF-MMI, the xent term and the regularisers that are switched on).  An utterance with u_b == 0 contributes
         exactly 0 even where its own objective is -inf or a NaN (`utt_weights=viterbi_align(...).ok.float()` drops the
@@ -809,7 +936,10 @@ class ChainLoss(nn.Module):
         if utt_weights is not None or deriv_weights is not None:
             wts = _check_weights(utt_weights, deriv_weights, x.size(0), x.size(1), self.avg)
         if isinstance(num_graphs, PosteriorTargets):
-            return self._forward_targets(x, x_lengths, num_graphs, xent_output, reg, wts)
+            return self._forward_targets(x, x_lengths, num_graphs, xent_output, reg, wts, xent_targets)
+        if xent_targets is not None:
+            raise ValueError("ChainLoss: xent_targets go with PosteriorTargets as the numerator (numerator graphs bring their own "
+                             "posteriors: the xent term takes its targets from them)")
         if not self._on_kernels(x, num_graphs):
             return self._forward_separate(x, x_lengths, num_graphs, z, reg, wts)
         if wts is not None:
@@ -822,26 +952,38 @@ class ChainLoss(nn.Module):
         return ChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg,
                                            self.xent_regularize, reg, wts)
 
-    def _forward_targets(self, x, x_lengths, targets, xent_output, reg, wts):
+    def _forward_targets(self, x, x_lengths, targets, xent_output, reg, wts, xent_targets=None):
         """`targets`: PosteriorTargets where the numerator graphs go (teacher-student and semi-supervised LF-MMI; Kaldi's "KL"
         objective): loss = (sum_b den_b - sum_b num_b) / N with num_b = sum_{t < L_b} sum_k q_k clamp(x(b,t,pdf_k), -30, 30), plus
         the regularisers, under the weights, N as for graphs.  The gradient is (gamma_den - q) / N.  Device tensors with
         fused = True and a probability-domain denominator: PosteriorChainLossFunction; else the unfused route with
-        posterior_numerator in the numerator's place.  xent regularisation against posterior targets is not provided."""
-        if xent_output is not None:
-            raise ValueError("ChainLoss: xent_output together with PosteriorTargets is not supported (the xent term takes its "
-                             "targets from numerator graphs)")
+        posterior_numerator in the numerator's place.  The xent term needs targets of its own, `xent_targets` (posterior_xent):
+        xent_output without them raises; with them, and xent_regularize != 0, the loss is LF-MMI_KL - c * xent."""
+        if xent_targets is None:
+            if xent_output is not None:
+                raise ValueError("ChainLoss: xent_output together with PosteriorTargets is not supported (the xent term takes its "
+                                 "targets from numerator graphs)")
+        elif not isinstance(xent_targets, PosteriorTargets):
+            raise ValueError("ChainLoss: xent_targets must be PosteriorTargets, got %s" % type(xent_targets).__name__)
+        z = xent_output if self.xent_regularize != 0.0 and xent_targets is not None else None
         targets.check(x.size(0), x.size(1), x.size(2))
+        if z is not None:
+            if tuple(z.shape) != tuple(x.shape):
+                raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(z.shape), tuple(x.shape)))
+            xent_targets.check(x.size(0), x.size(1), x.size(2))
         if not (self.fused and x.is_cuda and not self.den_graph.log_domain):
-            return self._forward_separate(x, x_lengths, targets, None, reg, wts)
+            return self._forward_separate(x, x_lengths, targets, z, reg, wts, xent_targets)
         if wts is not None:
             dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
             wts = (dev(wts[0]), dev(wts[1]), wts[0])
-        return PosteriorChainLossFunction.apply(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, self.avg, reg, wts)
+        if z is None:
+            return PosteriorChainLossFunction.apply(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, self.avg, reg, wts)
+        return PosteriorChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, targets, xent_targets, self.leaky_coefficient,
+                                                    self.avg, self.xent_regularize, reg, wts)
 
-    def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts):
+    def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts, xent_targets=None):
         """The unfused route and CPU tensors: two ChainFunction calls as in the reference, the cross-entropy term through
-        numerator_xent (`z`), the regularisers through output_regularizer (`reg`), each where it is switched on.
+        numerator_xent (`z`; with PosteriorTargets as the numerator: posterior_xent against `xent_targets`), the regularisers through output_regularizer (`reg`), each where it is switched on.
         Under weights `wts` = (u, f) the gradient comes from the loss as it is, evaluated on weight_rows(x, w) - its backward
         scales the rows, once, after autograd has added the calls' gradients up.  Derivative weights alone change neither the
         loss nor N.  Under utterance weights the loss is evaluated un-averaged and divided by N = sum_b u_b L_b; its value is
@@ -866,7 +1008,11 @@ class ChainLoss(nn.Module):
         if avg:
             objf = objf / x_lengths.sum()
         if z is not None:
-            xent = numerator_xent(z, xv, x_lengths, num_graphs)
+            if isinstance(num_graphs, PosteriorTargets):
+                xent = posterior_xent(z, x_lengths, xent_targets)
+                xent_bad = xent.bad_count
+            else:
+                xent = numerator_xent(z, xv, x_lengths, num_graphs)
             xent_per_seq = xent.xent_objf_per_seq
             if avg:
                 xent = xent / x_lengths.sum()
@@ -904,6 +1050,8 @@ class ChainLoss(nn.Module):
         objf.totals = objf.totals_all = None
         ChainFunction.last_totals = ChainFunction.last_totals_all = None
         objf.bad_count = (den.bad_count, num.bad_count)
+        if z is not None and isinstance(num_graphs, PosteriorTargets):
+            objf.bad_count = objf.bad_count + (xent_bad,)
         if z is not None:
             objf.xent_objf = xent_objf
         if reg is not None:

@@ -332,6 +332,72 @@ def cpu_num_xent(graphs, x, lengths, z, with_grad=True, windows=None):
     return res
 
 
+def xent_targets(z, lengths, pdfs, probs, with_grad=True, grad_scale=1.0, grad_scale_dev=None, norm_dev=None):
+    """Sparse targets as cross-entropy targets of z on the GPU (include/pychain_hip.h: pychain_hip_xent_targets), on the current
+    stream: `z` ([B,T,D], fp32 / bf16 / fp16) goes to the kernel as it is; `pdfs` / `probs`: [B,T,K].  Returns (XentResult -
+    objf [B], grad in z's dtype for the scale grad_scale [* grad_scale_dev] [/ norm_dev] or None, totals None until
+    xent_add_totals fills them -, bad_count int32 [1])."""
+    _require_device(z, "xent_output")
+    if z.dtype not in _DTYPE_CODE:
+        raise ValueError("xent_output must be float32, bfloat16 or float16, got %s" % z.dtype)
+    zc = z.detach().contiguous()
+    B, T, D = zc.shape
+    _check_lengths(lengths, B, T)
+    L = _lib.lib()
+    dev = zc.device
+    res = XentResult()
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        pd, pr = _target_args(pdfs, probs, B, T, dev)
+        res.objf = torch.empty(B, dtype=torch.float32, device=dev)
+        res.totals = None
+        res.grad = torch.empty_like(zc) if with_grad else None
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        grad_scale_dev, norm_dev = _dev_scalar(grad_scale_dev, dev), _dev_scalar(norm_dev, dev)
+        ws = _workspace(L.pychain_hip_xent_targets_workspace_bytes(B, T), dev, "xent_targets")
+        _lib.check(L.pychain_hip_xent_targets(
+            zc.data_ptr(), _DTYPE_CODE[zc.dtype], ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), _ptr(res.grad),
+            float(grad_scale), _ptr(grad_scale_dev), _ptr(norm_dev), res.objf.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(),
+            _stream(dev)), "pychain_hip_xent_targets")
+    return res, bad
+
+
+def xent_add_totals(res, bad=None, loss_scale=1.0, norm_dev=None, loss_coef=0.0, totals=None):
+    """The totals step behind xent_targets (include/pychain_hip.h: pychain_hip_xent_add_totals), on the current stream:
+    res.totals = fp32[2] = [loss_scale * S [/ norm_dev], S], S the sum of res.objf; `totals` (the device float[8] of the step, or
+    None): [0] = [4] += loss_coef * res.totals[0], [2] += bad.  Returns `res`."""
+    dev = res.objf.device
+    with torch.cuda.device(dev):
+        res.totals = torch.empty(2, dtype=torch.float32, device=dev)
+        norm_dev = _dev_scalar(norm_dev, dev)
+        _lib.check(_lib.lib().pychain_hip_xent_add_totals(
+            res.objf.data_ptr(), int(res.objf.numel()), float(loss_scale), _ptr(norm_dev), float(loss_coef), res.totals.data_ptr(),
+            _ptr(totals), _ptr(bad), _stream(dev)), "pychain_hip_xent_add_totals")
+    return res
+
+
+def cpu_xent_targets(z, lengths, pdfs, probs, with_grad=True, grad_scale=1.0, grad_scale_dev=None, norm=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_xent_targets), fp32 z, fp64 sums.  Returns (XentResult with
+    totals = [S, S], bad_count int32 [1])."""
+    if z.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_xent_targets is for CPU tensors; device tensors run on the HIP kernels")
+    zf, lc = _host_inputs(z, lengths)
+    B, T, D = zf.shape
+    pd, pr = _target_args(pdfs, probs, B, T, torch.device("cpu"))
+    cf = lambda t: None if t is None else torch.as_tensor(t).detach().to(torch.float32).contiguous()
+    grad_scale_dev, norm = cf(grad_scale_dev), cf(norm)
+    res = XentResult()
+    res.objf = torch.empty(B, dtype=torch.float32)
+    res.grad = torch.empty(B, T, D, dtype=torch.float32) if with_grad else None
+    bad = torch.zeros(1, dtype=torch.int32)
+    _lib.check(_lib.lib().pychain_hip_cpu_xent_targets(
+        zf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), _ptr(res.grad), float(grad_scale),
+        _ptr(grad_scale_dev), _ptr(norm), res.objf.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_xent_targets")
+    S = res.objf.sum(dtype=torch.float64).to(torch.float32)
+    res.totals = torch.stack([S, S])
+    return res, bad
+
+
 _CLAMP_LIMIT = 30.0        # the kernels' own clamp: the `limit` of the out-of-range penalty (pychain_hip_output_reg)
 
 

@@ -139,8 +139,9 @@ class ShardedChainLoss(torch.nn.Module):
     def _world(self):
         return dist.get_world_size(self.group) if dist.is_available() and dist.is_initialized() else 1
 
-    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None):
-        """`utt_weights` [B_local] / `deriv_weights` [B_local, T]: this rank's rows of ChainLoss.forward's weights (shard_batch
+    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None, xent_targets=None):
+        """`xent_targets`: this rank's PosteriorTargets for the xent output (ChainLoss.forward); the term rides in the local loss.
+        `utt_weights` [B_local] / `deriv_weights` [B_local, T]: this rank's rows of ChainLoss.forward's weights (shard_batch
         returns the indices to take them by).  The global normaliser of an averaged loss is then the all-reduced sum_b u_b L_b.
         Host utterance weights that are all zero under avg=True raise where this rank is the whole world; across ranks the sum
         is only known after the collective, and a global sum of zero gives a NaN loss."""
@@ -151,7 +152,10 @@ class ShardedChainLoss(torch.nn.Module):
             if not uw.is_cuda and not bool((uw != 0).any()):
                 raise ValueError("utt_weights are all zero: an averaged loss would divide by zero weighted frames")
         # sum over local utterances
-        if utt_weights is not None or deriv_weights is not None:
+        if xent_targets is not None:
+            local = self.local(x, x_lengths, num_graphs, xent_output, utt_weights=utt_weights, deriv_weights=deriv_weights,
+                               xent_targets=xent_targets)
+        elif utt_weights is not None or deriv_weights is not None:
             local = self.local(x, x_lengths, num_graphs, xent_output, utt_weights=utt_weights, deriv_weights=deriv_weights)
         else:
             local = self.local(x, x_lengths, num_graphs) if xent_output is None else self.local(x, x_lengths, num_graphs, xent_output)
