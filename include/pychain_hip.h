@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 24
+#define PYCHAIN_HIP_ABI_VERSION 25
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -716,6 +716,44 @@ int pychain_hip_cpu_xent_targets(
     const int32_t* target_pdfs, const float* target_probs, int K, float* xent_grad,
     float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
     float* xent_objf_per_seq, int32_t* bad_count, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Boosted denominator rows (ABI 25): the margin of the boosted objective (LF-bMMI).  The denominator is evaluated with every
+ * path's score lowered by `boost` times its per-frame agreement with a reference a(b,t,n), given as sparse per-frame targets
+ * (the layout and the index type of pychain_hip_post_targets: an alignment as K = 1 hard targets, or posterior targets):
+ *   F = num(x) - log sum_paths p(path) prod_t exp(clamp(x(t, pdf_t), -30, 30) - boost * a(t, pdf_t))
+ * - bMMI up to the path-independent constant boost * T, which is dropped; THE MARGIN IS APPLIED BEHIND THE CLAMP, so it does not
+ * vanish where |x| is near 30.  This call writes the rows the denominator then reads as they are: C callers run
+ * pychain_hip_boost_rows, then pychain_hip_den_forward_backward(e, PYCHAIN_HIP_F32, input_is_exp = 1) on the same stream; the
+ * occupancies that call writes are the boosted denominator's gradient with respect to x (neither the clamp nor the reference is
+ * differentiated).  For every live frame (b, t < L_b):
+ *   e(b,t,n) = E = exp(clamp(x(b,t,n)))       every n: the clamp and the exp of the denominator kernels themselves (v_med3_f32, then
+ *                                             v_exp_f32 on the rounded product with fp32(log2 e)) - an element no entry addresses
+ *                                             has the bits the denominator would have formed from x
+ *   e(b,t,d) = fl32(E * F)                    every distinct pdf d of the frame's live entries; qd = the fp32 sum, in ascending k, of
+ *                                             the frame's q_k with pdf_k == d (handled where d occurs first: a repeated pdf is
+ *                                             applied once, nothing races, nothing is atomic), u = fl32(boost * qd),
+ *                                             F = v_exp_f32(fl32(-u * fp32(log2 e))): two roundings and the hardware exp2 make
+ *                                             F, ONE multiply makes e
+ * ENTRIES.  pdf < 0 is padding and is skipped; pdf >= D in a live frame is skipped and counted.  Rows of x, rows of e and entries
+ * with t >= L_b are NEITHER READ NOR WRITTEN.  Lengths outside [1,T] are clamped, as everywhere.  A NaN in a live row of x becomes
+ * exp(-30) (the clamp's v_med3_f32) and would reach no check of the denominator call behind, so it is counted here:
+ *   bad_count  dev int32[1], written by the call: the live entries with pdf >= D + the live frames of x that hold a NaN
+ * One streaming pass: x read once in its own type (fp32 / bf16 / fp16, any D; 16-byte accesses of the fp32 side where D is a
+ * multiple of 4), e written once in fp32.  boost must be finite and >= 0 (0: e = E everywhere); K >= 1; nnet_output and e 16-byte
+ * aligned; else PYCHAIN_HIP_EINVAL.  The entry point is a translation unit of its own (csrc/boost.hip): no other object changes,
+ * and no existing entry point launches anything it did not launch before. */
+int pychain_hip_boost_rows(
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, float boost,
+    float* e, int32_t* bad_count, void* stream);
+/* the host twin: the same on host pointers, fp32 rows, the same operation sequence with exp2f of the host's libm where the device
+ * has v_exp_f32 - its e has the device's bits wherever the two exp2 agree, and is within the two roundings and the two exp2
+ * errors otherwise; host threads over the sequences; no stream */
+int pychain_hip_cpu_boost_rows(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, float boost,
+    float* e, int32_t* bad_count, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 24
+ABI_VERSION = 25
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -103,6 +103,9 @@ _SIGNATURES = {
     "pychain_hip_xent_targets": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pychain_hip_xent_add_totals": (_i, [_vp, _i, _f, _vp, _f, _vp, _vp, _vp, _vp]),
     "pychain_hip_cpu_xent_targets": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp, _i]),
+    # (ABI 25: the rows of the boosted denominator - exp(clamp(x)) with the targeted elements scaled by exp(-boost * a))
+    "pychain_hip_boost_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp]),
+    "pychain_hip_cpu_boost_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),

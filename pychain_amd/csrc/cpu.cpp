@@ -692,6 +692,75 @@ extern "C" int pychain_hip_cpu_xent_targets(
   return PYCHAIN_HIP_OK;
 }
 
+// ---- boosted denominator rows (include/pychain_hip.h: pychain_hip_boost_rows; the device's boost.hip): the same fp32 operation
+// sequence - clamp, the rounded product with fp32(log2 e), exp2; u = boost qd, the factor by the same two steps, ONE multiply -
+// with the host's exp2f where the device has v_exp_f32
+namespace pychain_hip {
+namespace {
+inline float boost_exp(float c) {                       // device_utils.h: exp_bounded
+#pragma clang fp contract(off)
+  const float t = c * 1.44269502162933349609375f;
+  return std::exp2(t);
+}
+inline float boost_clamp_exp(float v) {                 // (v_med3_f32 turns a NaN into -30)
+  const float c = v != v ? -30.f : (v < -30.f ? -30.f : (v > 30.f ? 30.f : v));
+  return boost_exp(c);
+}
+inline float boost_scaled(float E, float boost, float qd) {
+#pragma clang fp contract(off)
+  const float u = boost * qd;
+  const float F = boost_exp(-u);
+  return E * F;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_boost_rows(
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, float boost,
+    float* e, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_boost_rows";
+  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !e || !bad_count)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if (!(boost >= 0.f) || !std::isfinite(boost)) return fail(PYCHAIN_HIP_EINVAL, "%s: boost must be finite and not negative, got %g", who, (double)boost);
+  g_cpu_calls++;
+  std::vector<int> bads((size_t)B);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int64_t l = seq_lengths[b];
+    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    int bad = 0;
+    for (int t = 0; t < L; t++) {
+      const size_t f = (size_t)b * T + t;
+      const int32_t* pd = target_pdfs + f * K;
+      const float* pr = target_probs + f * K;
+      const float* x = nnet_output + f * D;
+      float* o = e + f * D;
+      bool nan = false;
+      for (int n = 0; n < D; n++) { nan = nan || x[n] != x[n]; o[n] = boost_clamp_exp(x[n]); }
+      if (nan) bad++;
+      for (int k = 0; k < K; k++) {
+        const int d = pd[k];
+        if (d < 0) continue;
+        if (d >= D) { bad++; continue; }
+        bool first = true;
+        for (int j = 0; j < k; j++) first = first && pd[j] != d;
+        if (!first) continue;
+        float qd = pr[k];
+        for (int j = k + 1; j < K; j++)
+          if (pd[j] == d) qd = post_add(qd, pr[j]);
+        o[d] = boost_scaled(boost_clamp_exp(x[d]), boost, qd);
+      }
+    }
+    bads[b] = bad;
+  });
+  int bad = 0;
+  for (int b = 0; b < B; b++) bad += bads[b];
+  *bad_count = bad;
+  return PYCHAIN_HIP_OK;
+}
+
 extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int D, int K, float floor,
                                          int normalize, int32_t* out_pdfs, float* out_probs, int num_threads) {
   const char* who = "cpu_topk_rows";

@@ -27,7 +27,7 @@ from .graph import ChainGraphBatch
 __all__ = ["ChainFunction", "ChainLossFunction", "ChainLossXentFunction", "NumeratorXentFunction", "numerator_xent",
            "output_regularizer", "weight_rows", "ChainLoss", "PosteriorTargets", "posterior_targets", "occupancies",
            "posterior_numerator", "PosteriorNumeratorFunction", "PosteriorChainLossFunction", "PosteriorChainLossXentFunction",
-           "PosteriorXentFunction", "posterior_xent"]
+           "PosteriorXentFunction", "posterior_xent", "boost_rows", "BoostedDenominatorFunction"]
 
 
 class ChainFunction(torch.autograd.Function):
@@ -738,8 +738,11 @@ def posterior_xent(xent_output, lengths, targets):
 
 
 def _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg,
-                       xent_regularize, reg, wts):
-    """forward() of PosteriorChainLossFunction (`xent_output` None) and of PosteriorChainLossXentFunction."""
+                       xent_regularize, reg, wts, boost=None):
+    """forward() of PosteriorChainLossFunction (`xent_output` None) and of PosteriorChainLossXentFunction.  `boost` = (boost
+    targets, b > 0) or None: the boosted denominator - native.boost_rows writes e = exp(clamp(x)) with the
+    targeted elements scaled by exp(-b a), and the denominator call runs on e with input_is_exp; everything behind it reads the
+    unboosted x as before."""
     x = input.detach().contiguous()
     z = None if xent_output is None else xent_output.detach()
     B, T, D = x.shape
@@ -762,10 +765,19 @@ def _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, target
         zk = z if z.dtype in native._DTYPE_CODE else z.float()
         z_grad = bool(ctx.needs_input_grad[1])
 
+    btg = None if boost is None else boost[0].to(x.device)
+
     def evaluate(loss_scale):
-        den_objf, grad, dbad, totals = native.den_forward_backward(plan, xk, lengths, leaky_coefficient, grad_scale=hscale, totals=True)
+        if btg is None:
+            den_objf, grad, dbad, totals = native.den_forward_backward(plan, xk, lengths, leaky_coefficient, grad_scale=hscale, totals=True)
+        else:
+            e, bbad = native.boost_rows(xk, lengths, btg.pdfs, btg.probs, boost[1])
+            den_objf, grad, dbad, totals = native.den_forward_backward(plan, e, lengths, leaky_coefficient, input_is_exp=True,
+                                                                       grad_scale=hscale, totals=True)
         if dnorm is not None:
             native.rescale_(grad, torch.reciprocal(dnorm.to(grad.device)))
+        if btg is not None and grad.dtype != xk.dtype:
+            grad = grad.to(xk.dtype)          # (the boosted rows are fp32, so is their gradient: one cast for 2-byte x - §3.24)
         num_objf, tbad = native.post_targets(xk, lengths, tg.pdfs, tg.probs, grad=grad, grad_scale=-hscale, norm_dev=dnorm,
                                              den_objf=den_objf, loss_scale=loss_scale, totals=totals)
         st = native.ChainLossState()
@@ -779,6 +791,8 @@ def _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, target
             xe, xbad = native.xent_targets(zk, lengths, ztg.pdfs, ztg.probs, with_grad=z_grad, grad_scale=-c * hscale, norm_dev=dnorm)
             st.xent = native.xent_add_totals(xe, xbad, loss_scale, dnorm, -c, totals)
             bads.append(xbad)
+        if btg is not None:
+            bads.append(bbad)
         r = (den_objf, num_objf, torch.cat(bads), st, totals)
         if reg is not None:
             r = _with_output_reg(r, reg, True, hscale, dnorm, loss_scale)
@@ -832,12 +846,13 @@ class PosteriorChainLossFunction(torch.autograd.Function):
     it, which all read N on the device."""
 
     @staticmethod
-    def forward(ctx, input, input_lengths, den_graph, targets, leaky_coefficient, avg, reg=None, wts=None):
-        return _posterior_forward(ctx, input, None, input_lengths, den_graph, targets, None, leaky_coefficient, avg, 0.0, reg, wts)
+    def forward(ctx, input, input_lengths, den_graph, targets, leaky_coefficient, avg, reg=None, wts=None, boost=None):
+        return _posterior_forward(ctx, input, None, input_lengths, den_graph, targets, None, leaky_coefficient, avg, 0.0, reg, wts,
+                                  boost)
 
     @staticmethod
     def backward(ctx, objf_grad):
-        return (_posterior_backward(ctx, objf_grad)[0],) + (None,) * 7
+        return (_posterior_backward(ctx, objf_grad)[0],) + (None,) * 8
 
 
 class PosteriorChainLossXentFunction(torch.autograd.Function):
@@ -849,13 +864,75 @@ class PosteriorChainLossXentFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg, xent_regularize,
-                reg=None, wts=None):
+                reg=None, wts=None, boost=None):
         return _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, targets, xent_targets, leaky_coefficient, avg,
-                                  xent_regularize, reg, wts)
+                                  xent_regularize, reg, wts, boost)
 
     @staticmethod
     def backward(ctx, objf_grad):
-        return _posterior_backward(ctx, objf_grad) + (None,) * 9
+        return _posterior_backward(ctx, objf_grad) + (None,) * 10
+
+
+def boost_rows(x, lengths, targets, boost):
+    """The rows the boosted denominator is evaluated on, as a fresh float32 [B,T,D] tensor, not differentiable:
+    e = exp(clamp(x, -30, 30)) over the live frames, the elements `targets` (PosteriorTargets) address scaled by
+    exp(-boost * q) - a pdf that occurs several times in a frame once, by the sum of its q.  Rows beyond a length are zero.
+    Device tensors run on the HIP kernel (native.boost_rows), CPU tensors on the host twin."""
+    if not isinstance(targets, PosteriorTargets):
+        raise ValueError("boost_rows takes PosteriorTargets, got %s" % type(targets).__name__)
+    x = x.detach()
+    targets.check(*x.shape)
+    tg = targets.to(x.device)
+    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    if x.is_cuda:
+        xk = x if x.dtype in native._DTYPE_CODE else x.float()
+        return native.boost_rows(xk, lengths, tg.pdfs, tg.probs, boost, out=out)[0]
+    return native.cpu_boost_rows(x, lengths, tg.pdfs, tg.probs, boost, out=out)[0]
+
+
+class BoostedDenominatorFunction(torch.autograd.Function):
+    """sum_b den_b of the BOOSTED denominator, differentiable in the network output: ChainFunction on the
+    denominator graph with every path's score lowered by boost * a(t, pdf_t), a = `targets`.  The boosted rows (native.boost_rows,
+    or the host twin) go to the denominator as they are (input_is_exp); its occupancies are the gradient for an upstream
+    gradient of 1.  What ChainLoss's unfused route and CPU tensors put in the denominator's place when boost > 0."""
+
+    @staticmethod
+    def forward(ctx, input, input_lengths, den_graph, targets, boost, leaky_coefficient=1e-5):
+        x = input.detach()
+        targets.check(*x.shape)
+        evaluate = lambda: BoostedDenominatorFunction._occupancies(x, input_lengths, den_graph, targets, boost, leaky_coefficient)
+        objf, input_grad, bad = evaluate()
+        if ChainFunction.retain_grad_buffer:
+            ctx.save_for_backward(input_grad)
+        else:
+            ctx.grad_buf = input_grad
+            ctx.again = _recompute(x, evaluate, ChainFunction._grad_again)
+        ctx.in_dtype = input.dtype
+        out = objf.sum()
+        out._objf_per_seq = objf
+        return _attach(out, None, bad)
+
+    @staticmethod
+    def _occupancies(x, lengths, den_graph, targets, boost, leaky_coefficient):
+        """(objf per sequence, occupancies of the boosted rows, bad_count: the denominator's + the pass's)"""
+        tg = targets.to(x.device)
+        if not x.is_cuda:
+            e, bbad = native.cpu_boost_rows(x, lengths, tg.pdfs, tg.probs, boost)
+            objf, grad, bad = native.cpu_forward_backward(ChainGraphBatch(den_graph, x.size(0)), e, lengths, leaky_coefficient,
+                                                          input_is_exp=True)
+            return objf, grad, bad + bbad
+        plan = _plan.graph_plan(den_graph, x.size(2), x.device)
+        xk = x if x.dtype in native._DTYPE_CODE else x.float()
+        e, bbad = native.boost_rows(xk, lengths, tg.pdfs, tg.probs, boost)
+        objf, grad, bad = native.den_forward_backward(plan, e, lengths, leaky_coefficient, input_is_exp=True)
+        return objf, grad, bad + bbad
+
+    @staticmethod
+    def backward(ctx, objf_grad):
+        if ctx.saved_tensors:
+            input_grad, = ctx.saved_tensors
+            return (torch.mul(input_grad, objf_grad).to(ctx.in_dtype),) + (None,) * 5
+        return (_grad_written_in_forward(ctx, objf_grad),) + (None,) * 5
 
 
 class ChainLossXentFunction(torch.autograd.Function):
@@ -884,11 +961,19 @@ class ChainLoss(nn.Module):
     [/ frames] over the live frames of the network output (output_regularizer); `loss.l2_term` and `loss.out_of_range_term` are
     the two amounts, detached.  Both zero: exactly the loss without them, launch for launch.
     `forward(x, lengths, targets)` with a PosteriorTargets where the numerator graphs go: posterior-target supervision
-    (teacher-student and semi-supervised LF-MMI), loss = (sum_b den_b - sum_b sum q clamp(x)) / N - _forward_targets."""
+    (teacher-student and semi-supervised LF-MMI), loss = (sum_b den_b - sum_b sum q clamp(x)) / N - _forward_targets.
+    `boost` = b > 0: the boosted objective (LF-bMMI) - the denominator is evaluated with every path's score
+    lowered by b times its per-frame agreement with a reference a(t, n), `forward(..., boost_targets=...)`:
+        den = log sum_paths p(path) prod_t exp(clamp(x(t, pdf_t)) - b * a(t, pdf_t))
+    (bMMI up to the constant b * T, which is dropped; the margin is applied behind the clamp).  `loss.boost` is b.  b = 0:
+    exactly the loss without it, launch for launch."""
 
     def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, xent_regularize=0.0, output_l2_regularize=0.0,
-                 out_of_range_regularize=0.0):
+                 out_of_range_regularize=0.0, boost=0.0):
         super(ChainLoss, self).__init__()
+        self.boost = float(boost)
+        if not (self.boost >= 0.0) or self.boost == float("inf"):
+            raise ValueError("ChainLoss: boost must be finite and not negative (got %r)" % self.boost)
         self.den_graph = den_graph
         self.avg = avg
         self.leaky_coefficient = leaky_coefficient
@@ -909,8 +994,34 @@ class ChainLoss(nn.Module):
     def _on_kernels(self, x, num_graphs):
         return self.fused and x.is_cuda and not self.den_graph.log_domain and num_graphs.log_domain
 
-    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None, xent_targets=None):
-        """`xent_targets` (with PosteriorTargets where the numerator graphs go, and `xent_output`): the PosteriorTargets the xent
+    def _boost(self, x, num_graphs, boost_targets):
+        """(boost targets, b) of a call with boost > 0, checked against the network output; None where boost == 0: the code path
+        is then exactly the one without it."""
+        if self.boost == 0.0:
+            return None
+        if boost_targets is None and isinstance(num_graphs, PosteriorTargets):
+            boost_targets = num_graphs
+        if boost_targets is None:
+            raise ValueError("ChainLoss: boost > 0 with numerator graphs needs boost_targets, the reference the margin is measured "
+                             "against - usually PosteriorTargets.from_alignment(viterbi_align(x, lengths, num_graphs))")
+        if not isinstance(boost_targets, PosteriorTargets):
+            raise ValueError("ChainLoss: boost_targets must be PosteriorTargets, got %s" % type(boost_targets).__name__)
+        if self.den_graph.log_domain:
+            raise ValueError("ChainLoss: boost > 0 needs a probability-domain denominator graph (a log-domain one has no "
+                             "entry point that takes the boosted rows)")
+        boost_targets.check(x.size(0), x.size(1), x.size(2))
+        return (boost_targets, self.boost)
+
+    def forward(self, x, x_lengths, num_graphs, xent_output=None, utt_weights=None, deriv_weights=None, xent_targets=None,
+                boost_targets=None):
+        """`boost_targets` (with boost > 0): the PosteriorTargets a(t, n) the margin is measured against.  With PosteriorTargets
+        where the numerator graphs go they default to those; with numerator graphs they are required - usually
+        `PosteriorTargets.from_alignment(viterbi_align(x, lengths, num_graphs))`.  Posterior supervision on device tensors keeps
+        its one-call route: native.boost_rows in front of the denominator call, which then reads the boosted rows as they are
+        (`loss.bad_count` gains a last word: the pass's own count).  Graph numerators take the unfused route - the boosted
+        denominator (BoostedDenominatorFunction), then the numerator through ChainFunction -, with time windows, xent_output, the
+        regularisers and the weights as that route has them; CPU tensors likewise, on the host twins.  Ignored when boost == 0.
+        `xent_targets` (with PosteriorTargets where the numerator graphs go, and `xent_output`): the PosteriorTargets the xent
         output is trained against - usually the same object, `criterion(y, lengths, targets, xent_output=z, xent_targets=targets)`;
         the loss is LF-MMI_KL - c * xent (posterior_xent), `loss.bad_count` gains a third word, the xent entries that name a pdf
         z does not have.  Graph numerators bring their own posteriors: `xent_targets` with them raises.
@@ -935,6 +1046,11 @@ class ChainLoss(nn.Module):
         wts = None
         if utt_weights is not None or deriv_weights is not None:
             wts = _check_weights(utt_weights, deriv_weights, x.size(0), x.size(1), self.avg)
+        boost = self._boost(x, num_graphs, boost_targets)
+        if boost is not None:
+            out = self._forward_boosted(x, x_lengths, num_graphs, xent_output, z, reg, wts, xent_targets, boost)
+            out.boost = self.boost
+            return out
         if isinstance(num_graphs, PosteriorTargets):
             return self._forward_targets(x, x_lengths, num_graphs, xent_output, reg, wts, xent_targets)
         if xent_targets is not None:
@@ -952,7 +1068,18 @@ class ChainLoss(nn.Module):
         return ChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, num_graphs, self.leaky_coefficient, self.avg,
                                            self.xent_regularize, reg, wts)
 
-    def _forward_targets(self, x, x_lengths, targets, xent_output, reg, wts, xent_targets=None):
+    def _forward_boosted(self, x, x_lengths, num_graphs, xent_output, z, reg, wts, xent_targets, boost):
+        """boost > 0: posterior supervision keeps _forward_targets' routes, with the boosted rows in front of the denominator;
+        graph numerators go through _forward_separate - existing entry points only - with the boosted denominator in the
+        denominator's place."""
+        if isinstance(num_graphs, PosteriorTargets):
+            return self._forward_targets(x, x_lengths, num_graphs, xent_output, reg, wts, xent_targets, boost)
+        if xent_targets is not None:
+            raise ValueError("ChainLoss: xent_targets go with PosteriorTargets as the numerator (numerator graphs bring their own "
+                             "posteriors: the xent term takes its targets from them)")
+        return self._forward_separate(x, x_lengths, num_graphs, z, reg, wts, boost=boost)
+
+    def _forward_targets(self, x, x_lengths, targets, xent_output, reg, wts, xent_targets=None, boost=None):
         """`targets`: PosteriorTargets where the numerator graphs go (teacher-student and semi-supervised LF-MMI; Kaldi's "KL"
         objective): loss = (sum_b den_b - sum_b num_b) / N with num_b = sum_{t < L_b} sum_k q_k clamp(x(b,t,pdf_k), -30, 30), plus
         the regularisers, under the weights, N as for graphs.  The gradient is (gamma_den - q) / N.  Device tensors with
@@ -972,16 +1099,17 @@ class ChainLoss(nn.Module):
                 raise ValueError("xent_output has shape %s, the chain output %s" % (tuple(z.shape), tuple(x.shape)))
             xent_targets.check(x.size(0), x.size(1), x.size(2))
         if not (self.fused and x.is_cuda and not self.den_graph.log_domain):
-            return self._forward_separate(x, x_lengths, targets, z, reg, wts, xent_targets)
+            return self._forward_separate(x, x_lengths, targets, z, reg, wts, xent_targets, boost)
         if wts is not None:
             dev = lambda w: None if w is None else w.to(x.device, non_blocking=True)
             wts = (dev(wts[0]), dev(wts[1]), wts[0])
         if z is None:
-            return PosteriorChainLossFunction.apply(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, self.avg, reg, wts)
+            return PosteriorChainLossFunction.apply(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, self.avg, reg, wts,
+                                                    boost)
         return PosteriorChainLossXentFunction.apply(x, z, x_lengths, self.den_graph, targets, xent_targets, self.leaky_coefficient,
-                                                    self.avg, self.xent_regularize, reg, wts)
+                                                    self.avg, self.xent_regularize, reg, wts, boost)
 
-    def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts, xent_targets=None):
+    def _forward_separate(self, x, x_lengths, num_graphs, z, reg, wts, xent_targets=None, boost=None):
         """The unfused route and CPU tensors: two ChainFunction calls as in the reference, the cross-entropy term through
         numerator_xent (`z`; with PosteriorTargets as the numerator: posterior_xent against `xent_targets`), the regularisers through output_regularizer (`reg`), each where it is switched on.
         Under weights `wts` = (u, f) the gradient comes from the loss as it is, evaluated on weight_rows(x, w) - its backward
@@ -999,7 +1127,10 @@ class ChainLoss(nn.Module):
         # sum of two does not depend on which arrives first: x.grad is (the gradient without the terms) + the term, rounded once
         # more)
         xv = x if reg is None else x.view_as(x)
-        den = ChainFunction.apply(xv, x_lengths, ChainGraphBatch(self.den_graph, x.size(0)), self.leaky_coefficient)
+        if boost is None:
+            den = ChainFunction.apply(xv, x_lengths, ChainGraphBatch(self.den_graph, x.size(0)), self.leaky_coefficient)
+        else:
+            den = BoostedDenominatorFunction.apply(xv, x_lengths, self.den_graph, boost[0], boost[1], self.leaky_coefficient)
         if isinstance(num_graphs, PosteriorTargets):
             num = posterior_numerator(xv, x_lengths, num_graphs)
         else:

@@ -603,6 +603,62 @@ def cpu_post_targets(x, lengths, pdfs, probs, grad=None, grad_scale=1.0, grad_sc
     return num_objf, bad
 
 
+def _check_boost(boost):
+    boost = float(boost)
+    if not (boost >= 0.0) or boost == float("inf"):
+        raise ValueError("boost must be finite and not negative, got %r" % boost)
+    return boost
+
+
+def boost_rows(x, lengths, pdfs, probs, boost, out=None):
+    """The rows of the boosted denominator on the GPU (include/pychain_hip.h: pychain_hip_boost_rows), on the current stream:
+    e = exp(clamp(x)) over the live frames, the elements the frame's entries address scaled by exp(-boost * qd).  `x` ([B,T,D],
+    fp32 / bf16 / fp16) goes to the kernel as it is; `pdfs` / `probs`: [B,T,K].  Returns (e float32 [B,T,D] - rows beyond a
+    length are not written -, bad_count int32 [1]).  `out` None: e is a view of the cached workspace of the caller's stream (key
+    "boost") - the next boost_rows on that stream overwrites it, so it goes straight into den_forward_backward(...,
+    input_is_exp=True)."""
+    _require_device(x, "nnet_output")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
+    boost = _check_boost(boost)
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    dev = x.device
+    with torch.cuda.device(dev):
+        ld = _lengths_dev(lengths, dev)
+        pd, pr = _target_args(pdfs, probs, B, T, dev)
+        if out is None:
+            n = B * T * D
+            out = _workspace(4 * n, dev, "boost")[:4 * n].view(torch.float32).view(B, T, D)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous() or out.device != dev:
+            raise ValueError("boost_rows: out must be a contiguous float32 tensor of the network output's shape and device")
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        _lib.check(_lib.lib().pychain_hip_boost_rows(
+            x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), boost,
+            out.data_ptr(), bad.data_ptr(), _stream(dev)), "pychain_hip_boost_rows")
+    return out, bad
+
+
+def cpu_boost_rows(x, lengths, pdfs, probs, boost, out=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_boost_rows), fp32 rows.  `out` None: a fresh buffer."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_boost_rows is for CPU tensors; device tensors run on the HIP kernels")
+    boost = _check_boost(boost)
+    xf, lc = _host_inputs(x, lengths)
+    B, T, D = xf.shape
+    pd, pr = _target_args(pdfs, probs, B, T, torch.device("cpu"))
+    if out is None:
+        out = torch.empty(B, T, D, dtype=torch.float32)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous() or out.is_cuda:
+        raise ValueError("cpu_boost_rows: out must be a contiguous float32 CPU tensor of the network output's shape")
+    bad = torch.zeros(1, dtype=torch.int32)
+    _lib.check(_lib.lib().pychain_hip_cpu_boost_rows(
+        xf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), boost, out.data_ptr(),
+        bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_boost_rows")
+    return out, bad
+
+
 def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     """Sparse targets out of dense posterior rows on the GPU (include/pychain_hip.h: pychain_hip_topk_rows), on the current
     stream: `rows` [B,T,D] in fp32 / bf16 / fp16 as it is.  Returns (pdfs int32 [B,T,k], probs float32 [B,T,k])."""
