@@ -743,7 +743,7 @@ def _posterior_forward(ctx, input, xent_output, input_lengths, den_graph, target
     targets, b > 0) or None: the boosted denominator - native.boost_rows writes e = exp(clamp(x)) with the
     targeted elements scaled by exp(-b a), and the denominator call runs on e with input_is_exp; everything behind it reads the
     unboosted x as before."""
-    x = input.detach().contiguous()
+    x = native._kernel_tensor(input.detach())      # (once for every pass of the step: they all read the same rows)
     z = None if xent_output is None else xent_output.detach()
     B, T, D = x.shape
     targets.check(B, T, D)

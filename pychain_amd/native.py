@@ -143,6 +143,24 @@ def _dev_scalar(t, device):
     return None if t is None else t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def _kernel_tensor(t):
+    """`t` as a device entry point takes it: contiguous and starting on a 16-byte boundary (every HIP entry point refuses any
+    other pointer - include/pychain_hip.h: its kernels read and write the rows 16 bytes at a time).  An aligned contiguous tensor
+    comes back as it is, without a launch; a strided view, or a contiguous one whose offset into its buffer is no multiple of
+    16 bytes (`y[1:]` at an odd T * D, one half of a wider layer's output), costs one copy of that tensor."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() & 15 else t
+
+
+def _kernel_buffer(t):
+    """(the buffer a kernel updates in place of the caller's contiguous `t`, what to call behind the launch): `t` itself and a
+    no-op where it starts on a 16-byte boundary, else an aligned copy and the copy back into `t`."""
+    if t is None or not t.data_ptr() & 15:
+        return t, lambda: None
+    k = t.clone()
+    return k, lambda: t.copy_(k)
+
+
 def _ptr(t):
     return None if t is None else t.data_ptr()
 
@@ -188,7 +206,7 @@ def den_forward_backward(plan, x, lengths, leaky_coefficient=1e-5, input_is_exp=
     include/pychain_hip.h (sum of the objectives, frames, bad count - from the call's last kernel, no extra launch)."""
     _require_device(x, "nnet_output")
     num_states = plan.num_states
-    x = x.contiguous()
+    x = _kernel_tensor(x)
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     L = _lib.lib()
@@ -219,7 +237,7 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
     """Numerator on the GPU.  `gt`: dict of device graph tensors; `windows`: int32 [B, H, 2] device time windows or None.
     Returns (objf_per_seq[B], grad[B,T,D], bad_count[1])."""
     _require_device(x, "nnet_output")
-    x = x.contiguous()
+    x = _kernel_tensor(x)
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     K = gt["forward_transitions"].shape[1]
@@ -235,6 +253,7 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
             grad = grad_out
         else:
             grad = torch.empty(x.shape, dtype=torch.float32, device=dev)     # (this entry point's gradient is fp32 whatever it read)
+        gk, put_back = _kernel_buffer(grad)              # (a caller's buffer off the 16-byte grid: updated through an aligned copy)
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         nws = L.pychain_hip_num_workspace_bytes(B, T, int(num_states), K, D)
         ws = _workspace(nws, dev, "num")
@@ -244,8 +263,9 @@ def num_forward_backward(gt, graph_stride, num_states, x, lengths, grad_mode=_li
         _lib.check(L.pychain_hip_num_forward_backward_xent(
             *_graph_ptrs(gt), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(grad_mode), float(grad_scale),
-            objf.data_ptr(), grad.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), _ptr(windows), None),
+            objf.data_ptr(), gk.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev), _ptr(windows), None),
             "pychain_hip_num_forward_backward_xent")
+        put_back()
     return objf, grad, bad
 
 
@@ -265,7 +285,7 @@ def _xent_arg(z, shape, H, K, with_grad, grad_scale, loss_coef, res):
     if z.dtype not in _DTYPE_CODE:
         raise ValueError("xent_output must be float32, bfloat16 or float16, got %s" % z.dtype)
     dev = z.device
-    zc = z.detach().contiguous()
+    zc = _kernel_tensor(z.detach())
     res.objf = torch.empty(B, dtype=torch.float32, device=dev)
     res.totals = torch.empty(2, dtype=torch.float32, device=dev)
     res.grad = torch.empty_like(zc) if with_grad else None
@@ -279,7 +299,7 @@ def num_xent(gt, graph_stride, num_states, x, lengths, z, with_grad=True, window
     """The numerator posteriors of (x, graphs) as cross-entropy targets of z on the GPU: pychain_hip_num_forward_backward_xent
     without a dense numerator gradient.  Returns an XentResult (grad for an upstream gradient of 1)."""
     _require_device(x, "nnet_output")
-    x = x.detach().contiguous()
+    x = _kernel_tensor(x.detach())
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     K = gt["forward_transitions"].shape[1]
@@ -340,7 +360,7 @@ def xent_targets(z, lengths, pdfs, probs, with_grad=True, grad_scale=1.0, grad_s
     _require_device(z, "xent_output")
     if z.dtype not in _DTYPE_CODE:
         raise ValueError("xent_output must be float32, bfloat16 or float16, got %s" % z.dtype)
-    zc = z.detach().contiguous()
+    zc = _kernel_tensor(z.detach())
     B, T, D = zc.shape
     _check_lengths(lengths, B, T)
     L = _lib.lib()
@@ -417,7 +437,7 @@ def output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, with_
     _require_device(x, "nnet_output")
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
-    x = x.detach().contiguous()
+    x = _kernel_tensor(x.detach())
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     L = _lib.lib()
@@ -436,12 +456,14 @@ def output_reg(x, lengths, l2, oor, grad=None, grad_mode=_lib.GRAD_LINEAR, with_
         res.per_seq = torch.empty(B, 2, dtype=torch.float32, device=dev)
         res.totals = torch.empty(3, dtype=torch.float32, device=dev)
         res.grad = grad
+        grad, put_back = _kernel_buffer(grad)
         grad_scale_dev, norm_dev = _dev_scalar(grad_scale_dev, dev), _dev_scalar(norm_dev, dev)
         ws = _workspace(L.pychain_hip_output_reg_workspace_bytes(B, T), dev, "outreg")
         _lib.check(L.pychain_hip_output_reg(
             x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, float(l2), float(oor), _CLAMP_LIMIT, int(grad_mode),
             _ptr(grad), float(grad_scale), _ptr(grad_scale_dev), _ptr(norm_dev), res.per_seq.data_ptr(), float(loss_scale),
             res.totals.data_ptr(), _ptr(totals), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_output_reg")
+        put_back()
     return res
 
 
@@ -507,10 +529,12 @@ def weight_rows(grad, lengths, utt_weights=None, deriv_weights=None, shape=None,
         if den_objf is not None:
             weighted = torch.empty(5, dtype=torch.float32, device=dev)
         norm_dev = _dev_scalar(norm_dev, dev)
+        grad, put_back = _kernel_buffer(grad)
         _lib.check(_lib.lib().pychain_hip_weight_rows(
             _ptr(grad), _DTYPE_CODE[grad.dtype] if grad is not None else _lib.F32, ld.data_ptr(), B, T, D, _ptr(u), _ptr(f),
             _ptr(den_objf), _ptr(num_objf), _ptr(xent_objf), float(xent_coef), _ptr(reg_per_seq), float(l2), float(oor),
             float(loss_scale), _ptr(norm_dev), _ptr(totals), _ptr(weighted), _stream(dev)), "pychain_hip_weight_rows")
+        put_back()
     return weighted
 
 
@@ -556,7 +580,7 @@ def post_targets(x, lengths, pdfs, probs, grad=None, grad_scale=1.0, grad_scale_
     _require_device(x, "nnet_output")
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
-    x = x.detach().contiguous()
+    x = x.detach().contiguous()            # (read one element at a time, csrc/post.hip: any element-aligned start will do)
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     L = _lib.lib()
@@ -572,10 +596,12 @@ def post_targets(x, lengths, pdfs, probs, grad=None, grad_scale=1.0, grad_scale_
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         grad_scale_dev, norm_dev = _dev_scalar(grad_scale_dev, dev), _dev_scalar(norm_dev, dev)
         ws = _workspace(L.pychain_hip_post_targets_workspace_bytes(B, T), dev, "post")
+        grad, put_back = _kernel_buffer(grad)
         _lib.check(L.pychain_hip_post_targets(
             x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), _ptr(grad),
             float(grad_scale), _ptr(grad_scale_dev), _ptr(norm_dev), _ptr(den_objf), num_objf.data_ptr(), bad.data_ptr(),
             float(loss_scale), _ptr(totals), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_post_targets")
+        put_back()
     return num_objf, bad
 
 
@@ -621,7 +647,7 @@ def boost_rows(x, lengths, pdfs, probs, boost, out=None):
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
     boost = _check_boost(boost)
-    x = x.detach().contiguous()
+    x = _kernel_tensor(x.detach())
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     dev = x.device
@@ -634,9 +660,11 @@ def boost_rows(x, lengths, pdfs, probs, boost, out=None):
         elif out.dtype != torch.float32 or tuple(out.shape) != (B, T, D) or not out.is_contiguous() or out.device != dev:
             raise ValueError("boost_rows: out must be a contiguous float32 tensor of the network output's shape and device")
         bad = torch.empty(1, dtype=torch.int32, device=dev)
+        ek, put_back = _kernel_buffer(out)
         _lib.check(_lib.lib().pychain_hip_boost_rows(
             x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), boost,
-            out.data_ptr(), bad.data_ptr(), _stream(dev)), "pychain_hip_boost_rows")
+            ek.data_ptr(), bad.data_ptr(), _stream(dev)), "pychain_hip_boost_rows")
+        put_back()
     return out, bad
 
 
@@ -665,7 +693,7 @@ def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     _require_device(rows, "rows")
     if rows.dtype not in _DTYPE_CODE:
         raise ValueError("rows must be float32, bfloat16 or float16, got %s" % rows.dtype)
-    rows = rows.detach().contiguous()
+    rows = rows.detach().contiguous()      # (csrc/post.hip picks element-wise loads for a start off the 16-byte grid itself)
     B, T, D = rows.shape
     _check_lengths(lengths, B, T)
     dev = rows.device
@@ -697,7 +725,7 @@ def align(gt, graph_stride, num_states, x, lengths):
     """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
     _require_device(x, "nnet_output")
-    x = x.detach().contiguous()
+    x = _kernel_tensor(x.detach())
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     K = gt["backward_transitions"].shape[1]
@@ -743,7 +771,7 @@ def _chain_loss_args(plan, gt, graph_stride, num_states_num, x, lengths, leaky_c
     the arguments both begin with.  Returns (x, lengths on the device, den_objf [B], num_objf [B], bad_count [2], windows, K,
     the leading arguments: plan, leaky coefficient, numerator graphs, x, lengths, B, T, D)."""
     _require_device(x, "nnet_output")
-    x = x.contiguous()
+    x = _kernel_tensor(x)
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     K = gt["forward_transitions"].shape[1]

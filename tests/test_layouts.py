@@ -1,0 +1,106 @@
+"""Views, slices and tensors off the 16-byte grid through every public entry point, CPU tensors on the host twins: the matrix
+of tests/layout_cases.py (what a case asserts is written there) on a machine without a GPU, and the layout functions themselves
+(tests/layouts.py).  The host twins have no alignment requirement: a failure here is a stride bug."""
+import pytest
+import torch
+
+import layout_cases as lc
+import layouts as ly
+
+DEV = "cpu"
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16, torch.int32, torch.int64])
+@pytest.mark.parametrize("shape", [(), (4,), (4, 23), (4, 23, 41), (4, 23, 40), (4, 7, 2)])
+def test_the_layout_functions(shape, dtype):
+    """every layout: the input's values, shape and dtype; is_contiguous() and data_ptr() % 16 as its name promises; everything
+    else in the buffer is poison"""
+    g = torch.Generator().manual_seed(len(shape))
+    t = (torch.randn(shape, generator=g) * 3).to(dtype) if dtype.is_floating_point else torch.randint(0, 50, shape, generator=g).to(dtype)
+    for name, make in ly.LAYOUTS.items():
+        if not ly.applies(name, len(shape), True):
+            continue
+        if len(shape) == 0 and name != "fresh" and name not in ly.OFFSETS:
+            continue
+        src = t[..., :1].expand(shape).contiguous() if name == "expanded" else t
+        v = make(src)
+        assert v.shape == src.shape and v.dtype == src.dtype and v.device == src.device and torch.equal(v, src), name
+        assert v.is_contiguous() == ly.is_contiguous(name, shape), name
+        base = ly.base_of(v)
+        assert base.data_ptr() % 16 == 0 and base.is_contiguous()
+        assert v.data_ptr() % 16 == (ly.element_offset(name, shape) * src.element_size()) % 16, name
+        assert (v.data_ptr() - base.data_ptr()) == v.storage_offset() * src.element_size()
+        out = ly.outside(v)
+        assert out.numel() == base.numel() - (src[..., :1].numel() if name == "expanded" else src.numel()), name
+        assert ly.is_poison(out, src), name
+        if name == "fresh":
+            assert base is v and v.data_ptr() != t.data_ptr()
+        elif name != "time_major":                    # (a transposed buffer has no element outside the view)
+            assert out.numel() > 0
+        if dtype.is_floating_point:
+            leaf = make(src, leaf=True)
+            assert ly.base_of(leaf).requires_grad and ly.base_of(leaf).is_leaf and torch.equal(leaf.detach(), src)
+    # the byte offsets the offset layouts are there for
+    if len(shape) == 3 and dtype in (torch.float32, torch.bfloat16):
+        want = [4, 8, 12, 0] if dtype == torch.float32 else [2, 4, 6, 8]
+        assert [ly.LAYOUTS[n](t).data_ptr() % 16 for n in ly.OFFSETS] == want
+    if shape == (4, 23, 41) and dtype == torch.float32:
+        assert ly.LAYOUTS["batch_slice"](t).data_ptr() % 16 == 12 and ly.LAYOUTS["head_hi"](t).storage_offset() % 2 == 0
+    assert ly.LAYOUTS["expanded"](torch.ones(4, 23)).stride() == (3, 0) if len(shape) == 2 else True
+
+
+def test_the_matrix_covers_every_entry_and_layout():
+    names = {e.name for e in lc.ENTRIES if not e.gpu_only}
+    seen = {}
+    for name, mode, layout in lc.matrix(DEV):
+        seen.setdefault(name, set()).add(layout)
+    assert set(seen) == names
+    for e in lc.ENTRIES:
+        if e.gpu_only:
+            continue
+        for a in e.args:
+            assert set(lc.arg_layouts(a)) <= seen[e.name], (e.name, a)
+        for layout in seen[e.name]:
+            assert lc.variants(e, layout), (e.name, layout)
+    lay, eq = lc.variants(lc.BY_NAME["loss_all"], "everything")[0]
+    assert len(set(lay.values())) == len(lay) == 4 and "fresh" not in lay.values()
+
+
+def _controls(dev):
+    return [(e.name, m) for e in lc.ENTRIES if not (e.gpu_only and dev == "cpu") for m in lc.entry_modes(e, dev)]
+
+
+@pytest.mark.parametrize("D,dname", lc.CONFIGS)
+@pytest.mark.parametrize("name,mode", _controls(DEV))
+def test_control_is_stable_and_meets_its_float64_reference(name, mode, D, dname):
+    e = lc.BY_NAME[name]
+    lc.fresh_is_stable(e, DEV, D, dname, mode)
+    d = lc.check_reference(e, lc.control(e, DEV, D, dname, mode), DEV, D, dname, mode)
+    print(name, mode, D, dname, d)
+
+
+def _make(entry, dev, cases):
+    @pytest.mark.parametrize("D,dname", lc.CONFIGS)
+    @pytest.mark.parametrize("mode,layout", cases)
+    def test(mode, layout, D, dname):
+        for lay, eq in lc.variants(entry, layout):
+            res = lc.run(entry, dev, D, dname, mode, lay, eq)
+            lc.assert_same(res, lc.control(entry, dev, D, dname, mode, eq), "%s %s %s" % (entry.name, mode, lay))
+    test.__name__ = "test_" + entry.name
+    return test
+
+
+for _e in lc.ENTRIES:
+    _cases = [(m, l) for n, m, l in lc.matrix(DEV) if n == _e.name]
+    if _cases:
+        globals()["test_" + _e.name] = _make(_e, DEV, _cases)
+
+
+@pytest.mark.parametrize("D,dname", lc.CONFIGS)
+def test_two_heads_of_one_layer(D, dname):
+    loss, wide, ctl = lc.two_heads(DEV, D, dname, None)
+    # (autograd ADDS the two heads' gradients at the leaf: a -0 of a padded row meets the other head's +0 and becomes +0 - the
+    # values are compared, which differs from the bits in the sign of a zero only)
+    assert lc.same_bits(loss, ctl.values["loss"])
+    assert torch.equal(wide[..., :D], ctl.grads["x"]["inside"]) and torch.equal(wide[..., D + 1:], ctl.grads["z"]["inside"])
+    assert not bool(wide[..., D].any()) and wide.dtype == lc.DTYPES[dname]
