@@ -248,7 +248,9 @@ int pychain_hip_den_plan_info(const void* host_blob, size_t blob_bytes, int32_t 
  *   totals[2] = bad_count as a float; totals[4] = totals[0] once more (ABI 14: the scalar a host framework hands out as the
  *   loss, apart from the statistics in [0..3] that it may all-reduce or keep); totals[5] = speculated rows of a time-segmented
  *   call that did not verify (0, or the call ran its recursions again unsegmented), totals[6] = its segments per (sequence,
- *   direction) (1: not segmented), totals[7] = the worst mismatch of a speculated row (max |p - q| / max p; the bound is 4e-6).
+ *   direction) (1: not segmented), totals[7] = the worst mismatch of a speculated row q against the true row p, per state: max_i |q_i - c p_i| / (c p_i) with
+ *   c = sum q / sum p (the bound is 9e-6 / (2 (segments - 1)): 4.5e-6 for two segments, 1.5e-6 for four; +inf where a row is dead
+ *   or only one of the two has a state at zero).
  * workspace: the stored alpha' / beta rows (4 B T roundup64(num_states) bytes each), per-frame totals, counters, and - in a
  *   call of the denominator alone - a [B,T,D] buffer for the rows exp'd ahead of the recursions (den_exp_rows_kernel: C4
  *   4.80 -> 4.57 ms): pychain_hip_den_workspace_bytes; pychain_hip_den_workspace_min_bytes is the size without it.

@@ -132,8 +132,14 @@ struct DenArgs {
   // from the ordinary start vector - a forward / backward filter forgets where it started (profiles/r05_forgetting_table.md:
   // 1e-7 after 192 frames on the benchmark graphs) - with the rows of its burn-in discarded, except the one next to the segment:
   // that one goes to splice[((b * 2 + dir) * kMaxTimeSegs + k) * 2 * Hp] and den_splice_check_kernel compares it with the TRUE row
-  // the neighbouring segment stored; any mismatch beyond 4e-6 sets *redo (and counts into respec), and the recursion launch that
-  // follows - the ordinary one, launched with redo_if - runs only then.  Sequences shorter than 2 tburn frames run as one segment.
+  // the neighbouring segment stored, STATE BY STATE: once the rows' free scale c = sum q / sum p is fixed, any state with
+  // |q_i - c p_i| > eps c p_i, eps = 9e-6 / (2 (S - 1)), sets *redo (and counts into respec), and the recursion launch that follows -
+  // the ordinary one, launched with redo_if - runs only then.  Agreement per state is what a frame of either recursion cannot make
+  // worse (a nonnegative linear map and a positive scaling do not increase Hilbert's projective distance); the neighbour's row is
+  // itself speculated, so the distances add up over the S - 1 splices of a (sequence, direction), and eps is chosen so that the
+  // gradient of a call cut in S stays within 9e-6 of its maximum.  Agreement relative to the LARGEST state - the check up to ABI
+  // 27 - does not have that property: a light state that is wrong decides the row as soon as the network's peak moves onto its
+  // successors (den_kernels.hip: den_splice_check_kernel).  Sequences shorter than 2 tburn frames run as one segment.
   int tseg, tburn;
   // The burn-in controller of a plan (include/pychain_hip.h: pychain_hip_den_tseg_state): how long a recursion needs
   // to forget where it started depends on the DATA, and a call whose speculated rows do not verify runs its recursions twice.  A
@@ -145,7 +151,7 @@ struct DenArgs {
   // by half while three of them fit the sequence, else the plan cools down for kTsegCooldown calls.  Null: tburn as given.
   int32_t* tstate;
   float* splice;                 // [B][2][kMaxTimeSegs][2][Hp]: the speculated row next to a segment; a row nobody reads (workspace)
-  int32_t* redo;                 // [4]: [0] != 0: a splice did not verify; [1]: how many; [2]: the worst mismatch as float bits (reported); [3]: what the segmented launch counted into `bad` - merged by den_finish_kernel only if [0] == 0 (zeroed with the progress counters)
+  int32_t* redo;                 // [4]: [0] != 0: a splice did not verify; [1]: how many; [2]: the worst mismatch max_i |q_i - c p_i| / (c p_i) as float bits (reported); [3]: what the segmented launch counted into `bad` - merged by den_finish_kernel only if [0] == 0 (zeroed with the progress counters)
   int redo_if;                   // this recursion launch is the fallback: its workgroups leave at once unless *redo != 0
   CallKnobs knobs;               // this call's snapshot of the library settings (host side only)
 };

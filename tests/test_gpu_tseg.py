@@ -2,7 +2,9 @@
 few sequences).  With B <= 32 the chain of T dependent frames IS the step and most CUs idle: the lazy recursions of a
 (sequence, direction) are cut into 2 or 4 time segments, each started `den_tburn` frames outside itself from the ordinary start
 vector - a forward / backward filter forgets where it started (profiles/r05_forgetting_table.md) - its burn-in rows discarded.
-The row next to every segment is compared on the device with the TRUE row the neighbouring segment stored (1e-6 as distributions);
+The row next to every segment is compared on the device with the TRUE row the neighbouring segment stored, state by state
+(every ratio within 9e-6 / (2 (S - 1)) of the rows' common scale: the one agreement that cannot grow inside a segment, with room
+for the S - 1 splices that chain up - den_kernels.hip);
 a miss makes the call run its recursions again, unsegmented, and is reported (totals[5]).  Replaces the T-long dependent chain of
 chain-computation.cc:196-207,332-342."""
 import numpy as np
@@ -10,7 +12,8 @@ import pytest
 import torch
 
 import oracle as orc
-from helpers import rel_err
+import peaky as pk
+from helpers import rel_err, record_parity
 from pychain_amd import ChainFunction, ChainGraphBatch, ChainLoss, _lib, _plan, native, synthetic as syn
 
 pytestmark = pytest.mark.gpu
@@ -183,3 +186,35 @@ def test_a_plan_that_keeps_missing_cools_down_and_c_callers_get_the_same():
     assert all(s[0] == 1 and s[1] == 0 for s in seen[1:]) and seen[-1][3] == 497 and seen[-1][4] == 4, seen
     assert torch.equal(g, g0)                                                # a cooled-down call IS the uncut call
     st.zero_()
+
+
+@pytest.mark.parametrize("name,S,burn,direction", sorted(pk.SPLICE_PINS))
+def test_the_splice_check_cannot_be_fooled_by_a_trained_looking_output(name, S, burn, direction):
+    """Network outputs with one pdf far above the rest that follow a path through the graph (tests/peaky.py), cut with burn-ins
+    so short that the check is the only guard.  Sequence 0 has a jump nobody announced right behind every splice (alpha: the
+    segment starts; beta: the segment ends): the states that hold the mass at the checked row lead nowhere, and the row two
+    frames on is decided by states that held 1e-6 of it.  tests/test_peaky.py proves in float64 that the max-norm check of
+    ABI <= 27 accepts every splice of the pinned calls and returns a gradient up to 1.5e-3 from the uncut call's (kept rows 1e-3 off).  EITHER the call reports missed rows, and then it
+    is the uncut call bit for bit, OR objective and gradient are within 1e-5 of the uncut call; never `bad`.  The uncut call
+    itself against the float64 oracle, under the oracle's own fp32-to-fp64 distance + 1e-5 (at most 1e-4)."""
+    g, G, D = pk.splice_graph(name)
+    plan = _plan.graph_plan(g, D, torch.device(DEV))
+    x_cpu = torch.from_numpy(pk.pinned_splice_case(name, S, burn, direction))
+    x, L = x_cpu.to(DEV), torch.tensor(pk.SPLICE_LENGTHS)
+    o0, g0, b0, t0 = _den(plan, x, L, den_tseg=0)
+    o, gr, b, t = _den(plan, x, L, den_tseg=S, den_tburn=burn)
+    eo = float((o - o0).abs().max()) / float(o0.abs().max())
+    eg = rel_err(gr.cpu().numpy(), g0.cpu().numpy())
+    ro, rg, bar_o, bar_g, own, ok = pk.oracle_bars("den", x_cpu, L, ChainGraphBatch(g, 2))
+    fo, fg = abs(float(o0.sum()) - ro) / abs(ro), rel_err(g0.cpu().numpy(), rg)
+    print("splice", name, S, burn, direction, "missed rows", int(t[5]), "worst per-state mismatch %.3g" % float(t[7]),
+          "cut vs uncut: objf %.3g grad %.3g; uncut vs f64: objf %.3g (bar %.3g) grad %.3g (bar %.3g)" % (eo, eg, fo, bar_o, fg, bar_g))
+    record_parity("splice_%s_S%d_burn%d_dir%d" % (name, S, burn, direction), missed=int(t[5]), worst=min(float(t[7]), 1e30),
+                  cut_vs_uncut_objf=eo, cut_vs_uncut_grad=eg, uncut_vs_f64_objf=fo, uncut_vs_f64_grad=fg, bar_grad=bar_g)
+    assert ok and b0 == 0 and b == 0 and int(t0[6]) == 1 and int(t[6]) == S
+    if int(t[5]) > 0:
+        assert torch.equal(o, o0) and torch.equal(gr, g0)
+    else:
+        assert eo <= 1e-5 and eg <= 1e-5
+    assert fo <= bar_o and fg <= bar_g
+    assert bool((gr[1, 399:] == 0).all())

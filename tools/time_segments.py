@@ -37,7 +37,7 @@ for name, B, T, mode in (("C3", 4, 1500, "ragged"), ("C3", 16, 1500, "ragged"), 
     print("%s B=%d %s: " % (name, B, mode) + " | ".join(cells))
     native.release_workspaces(); torch.cuda.empty_cache()
 print()
-print("== worst mismatch of a speculated row (max |p - q| / max p; bound 4e-6), 4 segments, 3 draws of the network output, by burn-in")
+print("== worst mismatch of a speculated row (per state, max |q - c p| / (c p); bound 1.5e-6 for 4 segments), 4 segments, 3 draws of the network output, by burn-in")
 for name, B, T in (("C3", 32, 1500), ("C4", 16, 2000)):
     cfg = syn.CONFIGS[name]
     den = syn.make_den_graph(cfg["H"], cfg["K"], cfg["D"], seed=0)
