@@ -113,7 +113,10 @@ def plan_info(blob):
 # ($PYCHAIN_PLAN_CACHE_DIR, default ~/.cache/pychain_amd/plans, created 0700; "0" / "off" disables).  Writes are
 # atomic (temp file + rename): ranks racing on one graph all end up with the same bytes.  A file is only
 # believed if its header matches the request AND its payload matches the checksum in the header.
-_KNOBS = ("PYCHAIN_PLAN_GENERAL", "PYCHAIN_PLAN_SLACK", "PYCHAIN_PLAN_BALANCE", "PYCHAIN_PLAN_ANNEAL", "PYCHAIN_PLAN_FIT", "PYCHAIN_PLAN_LINEAR", "PYCHAIN_PLAN_SPLIT", "PYCHAIN_PLAN_GAMMA_BOUND", "PYCHAIN_PLAN_SG")
+_KNOBS = ("PYCHAIN_PLAN_GENERAL", "PYCHAIN_PLAN_SLACK", "PYCHAIN_PLAN_BALANCE", "PYCHAIN_PLAN_ANNEAL", "PYCHAIN_PLAN_FIT", "PYCHAIN_PLAN_LINEAR", "PYCHAIN_PLAN_SPLIT", "PYCHAIN_PLAN_GAMMA_BOUND", "PYCHAIN_PLAN_SG",
+          "PYCHAIN_PLAN_SLOTS")
+# raised with csrc/plan.cpp: kSolverRevision - the same graph and knobs may compile to other bytes than under the revision before
+_SOLVER_REVISION = 2
 
 
 def _cache_dir():
@@ -141,8 +144,8 @@ def _build_id():
 
 def _plan_key(arrays, num_pdfs):
     h = hashlib.sha256()
-    h.update(b"pychain_amd plan v%d abi %d pdfs %d build %s" % (_plan_format_version(), _lib.ABI_VERSION, int(num_pdfs),
-                                                                 _build_id().encode()))
+    h.update(b"pychain_amd plan v%d solver %d abi %d pdfs %d build %s" % (_plan_format_version(), _SOLVER_REVISION, _lib.ABI_VERSION,
+                                                                           int(num_pdfs), _build_id().encode()))
     for k in _KNOBS:
         h.update(("%s=%s;" % (k, os.environ.get(k, ""))).encode())
     h.update(("plan_split=%s;" % (_lib.get_option("plan_split") or "")).encode())

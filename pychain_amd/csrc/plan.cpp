@@ -12,7 +12,7 @@
 //   2. every recursion group gets spare slot-rows, as many as the register-resident loop of the
 //      kernel walks anyway: a half-group that is 97 % full cannot avoid a bank holding more
 //      than its share of the arcs;
-//   3. a row may issue its arcs in any slot order                     (SlotOrder, annealing).
+//   3. a row may issue its arcs in any slot order        (SlotOrder: edge colouring, annealing).
 // Modelled LDS cycles per half slot-row for the two gathers of an arc on the C3 graph
 // (2.0 = conflict-free): natural order 7.0, slot order alone 3.8, all three 2.3 at 19 % more
 // slot-rows.  Deterministic (fixed-seed LCG): the same graph always gives the same plan.
@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <sched.h>
 #include <thread>
 #include <vector>
 
@@ -198,9 +199,10 @@ struct Balancer {
 };
 
 // ---- freedom 3: slot order ------------------------------------------------------------------------
-// cell[g][lane][slot] = index of the arc in its row's list, -1 = padding.  Per half-group: greedy
-// placement, then simulated annealing on  sum over columns and operands of
-// kLambda * (max bank load) + sum of squared bank loads;  a move swaps two slots of one row.
+// cell[g][lane][slot] = index of the arc in its row's list, -1 = padding.  Per half-group: an exact
+// start for one operand (edge colouring, colour_half), then simulated annealing on  sum over columns
+// and operands of  kW * (max bank load) + sum of squared bank loads;  a move swaps two slots of one
+// row - the partner slot priced from the bank loads - or of a Kempe chain of rows (group_coloured).
 struct SlotOrder {
   const Tile& t;
   const Layouts& lay;
@@ -244,7 +246,95 @@ struct SlotOrder {
     else { while (c.mx[hh][op] > 0 && c.nm[hh][op][c.mx[hh][op]] == 0) c.mx[hh][op]--; }
     return col_energy_op(c, op) + x * x - before;
   }
-  void group(int g, long moves_per_cell) {
+  // ---- the exact start (PYCHAIN_PLAN_SLOTS != 0) ----
+  // For one operand, a half-group is a bipartite multigraph lanes x banks (an arc = an edge), and a slot order is an edge
+  // colouring with A colours in which a lane - degree <= A - sees every colour at most once.  Split a bank of degree d into
+  // ceil(d / A) copies of degree <= A: the graph then has maximum degree A, Koenig's alternating-path argument colours it with
+  // A colours, and no column holds more than ceil(d / A) arcs of that bank (de Werra's equitable colouring, upper half): the
+  // operand is conflict-free wherever no bank holds more than A arcs, which is what the row placement worked for.  Among the
+  // colours free at both ends the one with the fewest arcs in the OTHER operand's bank is taken.
+  struct Edge { int r, a, x[2]; };
+  void colour_half(const std::vector<Edge>& ed, int A, int P, std::vector<int>& colour) const {
+    const int ne = (int)ed.size();
+    colour.assign(ne, -1);
+    int deg[32] = {0}, first_copy[33], seen[32] = {0};
+    for (const Edge& e : ed) deg[e.x[P]]++;
+    first_copy[0] = 0;
+    for (int b = 0; b < 32; b++) first_copy[b + 1] = first_copy[b] + (deg[b] + A - 1) / A;
+    const int nv = first_copy[32];
+    std::vector<int> copy_of(ne), lane_at(32 * A, -1), copy_at((size_t)std::max(nv, 1) * A, -1), other(32 * A, 0);
+    for (int i = 0; i < ne; i++) {                     // a bank's arcs are dealt to its copies in turn: copies of near-equal degree
+      const int b = ed[i].x[P], nc = first_copy[b + 1] - first_copy[b];
+      copy_of[i] = first_copy[b] + seen[b]++ % nc;
+    }
+    auto put = [&](int i, int j) { colour[i] = j; lane_at[(ed[i].r & 31) * A + j] = i; copy_at[copy_of[i] * A + j] = i; other[j * 32 + ed[i].x[1 - P]]++; };
+    auto take = [&](int i) { const int j = colour[i]; lane_at[(ed[i].r & 31) * A + j] = -1; copy_at[copy_of[i] * A + j] = -1; other[j * 32 + ed[i].x[1 - P]]--; };
+    std::vector<int> path;
+    for (int i = 0; i < ne; i++) {
+      const int u = ed[i].r & 31, v = copy_of[i];
+      int both = -1, fu = -1, fv = -1;
+      for (int j = 0; j < A; j++) {
+        const bool free_u = lane_at[u * A + j] < 0, free_v = copy_at[v * A + j] < 0;
+        if (free_u && fu < 0) fu = j;
+        if (free_v && fv < 0) fv = j;
+        if (free_u && free_v && (both < 0 || other[j * 32 + ed[i].x[1 - P]] < other[both * 32 + ed[i].x[1 - P]])) both = j;
+      }
+      if (both >= 0) { put(i, both); continue; }
+      // fu is free at the lane and taken at the copy, fv the reverse: flip the fu / fv alternating path that starts at the copy.
+      // It enters lanes by edges of colour fu only, so it never reaches this lane, and ends: afterwards fu is free at both ends.
+      path.clear();
+      for (int cv = v;;) {
+        const int e1 = copy_at[cv * A + fu];
+        if (e1 < 0) break;
+        path.push_back(e1);
+        const int e2 = lane_at[(ed[e1].r & 31) * A + fv];
+        if (e2 < 0) break;
+        path.push_back(e2);
+        cv = copy_of[e2];
+      }
+      std::vector<int> was(path.size());
+      for (size_t k = 0; k < path.size(); k++) { was[k] = colour[path[k]]; take(path[k]); }
+      for (size_t k = 0; k < path.size(); k++) put(path[k], was[k] == fu ? fv : fu);
+      put(i, fu);
+    }
+  }
+  // the shipped energy of one half's colouring (col_energy_op + squares, as col_add accumulates them)
+  long half_energy(const std::vector<Edge>& ed, int A, const std::vector<int>& colour) const {
+    std::vector<int> cnt((size_t)A * 64, 0);
+    for (size_t i = 0; i < ed.size(); i++) for (int op = 0; op < (ignore_op1 ? 1 : 2); op++) cnt[(colour[i] * 2 + op) * 32 + ed[i].x[op]]++;
+    long e = 0;
+    for (int j = 0; j < 2 * A; j++) {
+      int mx = 0;
+      for (int b = 0; b < 32; b++) { const int x = cnt[j * 32 + b]; mx = std::max(mx, x); e += x * x; }
+      e += kW * mx;
+    }
+    return e;
+  }
+  std::atomic<long> bound{0};                        // sum over half-groups and operands of max(A, fullest bank's arcs): no slot order of this placement goes below
+  // PYCHAIN_PLAN_SLOTS=0: the solver this one replaced - greedy start, single swaps (kept for A/B runs and the tests)
+  const bool coloured = env_long("PYCHAIN_PLAN_SLOTS", 1) != 0;
+  // One move in eight is a Kempe chain.  Modelled on C3 (alpha / beta, 3000 moves per cell): none 2.607 / 2.613, one 2.608 /
+  // 2.614, two 2.630 / 2.621, three 2.688 / 2.684 (with half of the partners chosen blindly); the structured graph sits at
+  // its bound with any share.  The chains re-deal the other operand wholesale and are seldom accepted: one eighth keeps the
+  // move at no cost, more only spends the budget.
+  static constexpr int kempe_eighths = 1;
+  std::atomic<long> bound_op[2] = {{0}, {0}};        // ... per operand
+  long placement_bound(int g, int A, int nr) {
+    long bnd = 0;
+    for (int hh = 0; hh < 2; hh++) {
+      int deg[2][32] = {{0}};
+      for (int r = 32 * hh; r < std::min(nr, 32 * hh + 32); r++)
+        for (const Arc& a : (*t.rows)[t.order[g * 64 + r]]) { deg[0][lay.bank(t.lay[0], a.e0)]++; deg[1][lay.bank(t.lay[1], a.e1)]++; }
+      for (int op = 0; op < 2; op++) {
+        const int x = (op == 1 && ignore_op1) ? A : std::max(A, *std::max_element(deg[op], deg[op] + 32));
+        bnd += x; bound_op[op] += x;
+      }
+    }
+    return bnd;
+  }
+
+  // Slot order of group g: the exact start per half and operand, then annealing on the shipped energy with three kinds of move.
+  void group_coloured(int g, long moves_per_cell) {
     Lcg rng{0x9E3779B9u ^ (uint32_t)((g * 2) * 2654435761u)};   // per group: results do not depend on the thread count
     const int A = t.gsl[g];
     int nr = 0;
@@ -254,6 +344,173 @@ struct SlotOrder {
     std::vector<Col> cs(A);
     for (auto& c : cs) { memset(&c, 0, sizeof(c)); for (int hh = 0; hh < 2; hh++) c.nm[hh][0][0] = c.nm[hh][1][0] = 32; }
     std::vector<int> b0(nr * A, -1), b1(nr * A, -1);   // banks of a cell's arc
+    auto arcs_of = [&](int r) -> const std::vector<Arc>& { return (*t.rows)[t.order[g * 64 + r]]; };
+    bound += placement_bound(g, A, nr);
+    for (int hh = 0; hh < 2; hh++) {
+      std::vector<int> rorder;
+      for (int r = 32 * hh; r < std::min(nr, 32 * hh + 32); r++) rorder.push_back(r);
+      std::stable_sort(rorder.begin(), rorder.end(), [&](int x, int y) { return arcs_of(x).size() > arcs_of(y).size(); });
+      std::vector<Edge> ed;
+      for (int r : rorder) {
+        const auto& arcs = arcs_of(r);
+        for (int a = 0; a < (int)arcs.size(); a++) {
+          const Edge e{r, a, {lay.bank(t.lay[0], arcs[a].e0), lay.bank(t.lay[1], arcs[a].e1)}};
+          ed.push_back(e);
+        }
+      }
+      // both operands are weighted alike in the energy: the start is the colouring - exact for operand 0 or for operand 1 -
+      // that the energy prefers
+      std::vector<int> colour, alt;
+      colour_half(ed, A, 0, colour);
+      if (!ignore_op1) {
+        colour_half(ed, A, 1, alt);
+        if (half_energy(ed, A, alt) < half_energy(ed, A, colour)) colour.swap(alt);
+      }
+      for (size_t i = 0; i < ed.size(); i++) {
+        const int at = ed[i].r * A + colour[i];
+        cl[at] = ed[i].a; b0[at] = ed[i].x[0]; b1[at] = ed[i].x[1];
+        col_add(cs[colour[i]], hh, 0, ed[i].x[0], +1); col_add(cs[colour[i]], hh, 1, ed[i].x[1], +1);
+      }
+    }
+    // lane r's cells ja and jb trade places; returns the energy change (calling it again undoes it exactly)
+    auto trade = [&](int r, int ja, int jb) {
+      const int hh = r >> 5, a1 = r * A + ja, a2 = r * A + jb;
+      int d = 0;
+      if (b0[a1] >= 0) d += col_add(cs[ja], hh, 0, b0[a1], -1) + col_add(cs[ja], hh, 1, b1[a1], -1);
+      if (b0[a2] >= 0) d += col_add(cs[jb], hh, 0, b0[a2], -1) + col_add(cs[jb], hh, 1, b1[a2], -1);
+      if (b0[a1] >= 0) d += col_add(cs[jb], hh, 0, b0[a1], +1) + col_add(cs[jb], hh, 1, b1[a1], +1);
+      if (b0[a2] >= 0) d += col_add(cs[ja], hh, 0, b0[a2], +1) + col_add(cs[ja], hh, 1, b1[a2], +1);
+      std::swap(cl[a1], cl[a2]); std::swap(b0[a1], b0[a2]); std::swap(b1[a1], b1[a2]);
+      return d;
+    };
+    if (A >= 2) {
+      const long iters = moves_per_cell * nr * A;
+      const double t0 = 3.0, t1 = 0.03;
+      const double cool = iters > 1 ? pow(t1 / t0, 1.0 / (double)iters) : 1.0;
+      const int kempe = kempe_eighths;
+      double T = t0;
+      int chain[32];
+      // The partner slot of lane r's cell j1 that the energy likes best, from the bank loads alone (the two arcs are priced as
+      // if they shared no bank; the trade itself is priced exactly).  The scan starts at jstart: ties stay with the first.
+      auto best_partner = [&](int r, int j1, int jstart, int& bd) {
+        const int hh = r >> 5;
+        auto leave = [&](int j, int x0, int x1) {
+          const Col& c = cs[j];
+          int d = -(2 * c.cnt[hh][0][x0] - 1) - (c.cnt[hh][0][x0] == c.mx[hh][0] && c.nm[hh][0][c.mx[hh][0]] == 1 ? kW : 0);
+          if (!ignore_op1) d += -(2 * c.cnt[hh][1][x1] - 1) - (c.cnt[hh][1][x1] == c.mx[hh][1] && c.nm[hh][1][c.mx[hh][1]] == 1 ? kW : 0);
+          return d;
+        };
+        auto enter = [&](int j, int x0, int x1) {
+          const Col& c = cs[j];
+          int d = 2 * c.cnt[hh][0][x0] + 1 + (c.cnt[hh][0][x0] + 1 > c.mx[hh][0] ? kW : 0);
+          if (!ignore_op1) d += 2 * c.cnt[hh][1][x1] + 1 + (c.cnt[hh][1][x1] + 1 > c.mx[hh][1] ? kW : 0);
+          return d;
+        };
+        const int i1 = r * A + j1, out1 = leave(j1, b0[i1], b1[i1]);
+        int best = -1;
+        bd = 0;
+        for (int q = 0; q < A; q++) {
+          int j = jstart + q; if (j >= A) j -= A;
+          if (j == j1) continue;
+          const int i2 = r * A + j;
+          int d = out1 + enter(j, b0[i1], b1[i1]);
+          if (b0[i2] >= 0) d += leave(j, b0[i2], b1[i2]) + enter(j1, b0[i2], b1[i2]);
+          if (best < 0 || d < bd) { best = j; bd = d; }
+        }
+        return best;
+      };
+      for (long it = 0; it < iters; it++, T *= cool) {
+        int r = rng.next() % nr;
+        const int j1 = rng.next() % A;
+        int j2 = rng.next() % (A - 1); if (j2 >= j1) j2++;
+        bool lane_chosen = false;
+        if (rng.next() & 1) {
+          // half of the moves start from a lane that sits in a fullest bank of a conflicting half-column: of those lanes, the
+          // one whose best partner slot the energy likes best
+          const int hh = rng.next() & 1, op = ignore_op1 ? 0 : (int)(rng.next() & 1);
+          const Col& c = cs[j1];
+          if (c.mx[hh][op] >= 2) {
+            int bmax = -1, seen = 0;
+            for (int b = 0; b < 32; b++) if (c.cnt[hh][op][b] == c.mx[hh][op] && (rng.next() % ++seen) == 0) bmax = b;
+            const std::vector<int>& bank = op ? b1 : b0;
+            int pick = -1, pd = 0, pj = j2;
+            for (int rr = 32 * hh; rr < std::min(nr, 32 * hh + 32); rr++)
+              if (bank[rr * A + j1] == bmax) {
+                int d;
+                const int j = best_partner(rr, j1, j2, d);
+                if (pick < 0 || d < pd) { pick = rr; pd = d; pj = j; }
+              }
+            if (pick >= 0) { r = pick; j2 = pj; lane_chosen = true; }
+          }
+        }
+        if (!lane_chosen && b0[r * A + j1] >= 0) { int d; j2 = best_partner(r, j1, j2, d); }
+        if (b0[r * A + j1] < 0 && b0[r * A + j2] < 0) continue;
+        int n = 1, dE;
+        chain[0] = r;
+        if ((int)(rng.next() & 7) >= kempe) {
+          dE = trade(r, j1, j2);                       // one lane: the move the annealing had before
+        } else {
+          // Kempe chain in the lanes x banks graph of operand `op`: lane r's trade moves an arc of a bank from column j1 to j2
+          // (and one of another bank back); a further lane that holds the same bank in j2 trades too, and so on along the
+          // alternating j1 / j2 path - inside the chain every bank keeps its load in both columns, so operand `op` changes at
+          // the ends of the chain at most, and the other operand is re-dealt between the two columns.
+          const int op = ignore_op1 ? 0 : (int)(rng.next() & 1), hh = r >> 5;
+          const std::vector<int>& bk = op ? b1 : b0;
+          const int lo = 32 * hh, hi = std::min(nr, lo + 32);
+          int imb[32] = {0};                           // > 0: the bank gained an arc in j2 and lost one in j1
+          uint32_t visited = 0, dead = 0;
+          auto touch = [&](int rr) {
+            if (bk[rr * A + j1] >= 0) imb[bk[rr * A + j1]]++;
+            if (bk[rr * A + j2] >= 0) imb[bk[rr * A + j2]]--;
+            visited |= 1u << (rr - lo);
+            return trade(rr, j1, j2);
+          };
+          dE = touch(r);
+          while (n < 32) {
+            int b = -1;
+            for (int q = 0; q < 32; q++) if (imb[q] != 0 && !((dead >> q) & 1)) { b = q; break; }
+            if (b < 0) break;
+            const int from = imb[b] > 0 ? j2 : j1;     // a lane that holds bank b there gives it back
+            const int start = (int)(rng.next() & 31);
+            int pick = -1;
+            for (int q = 0; q < 32 && pick < 0; q++) {
+              const int rr = lo + ((start + q) & 31);
+              if (rr < hi && !((visited >> (rr - lo)) & 1) && bk[rr * A + from] == b) pick = rr;
+            }
+            if (pick < 0) { dead |= 1u << b; continue; }
+            dE += touch(pick);
+            chain[n++] = pick;
+          }
+        }
+        if (!(dE <= 0 || rng.unit() < exp(-(double)dE / T)))
+          for (int k = n - 1; k >= 0; k--) trade(chain[k], j1, j2);
+        for (int k = 1; k < n && it + 1 < iters; k++) { it++; T *= cool; }   // the budget counts lanes traded
+      }
+    }
+    long cyc0 = 0, cyc1 = 0, extra = 0;
+    for (int j = 0; j < A; j++) {
+      for (int hh = 0; hh < 2; hh++) { cyc0 += std::max(cs[j].mx[hh][0], 1); cyc1 += std::max(cs[j].mx[hh][1], 1); }
+      for (int op = 0; op < 2; op++) extra += extra_tenths(op, std::max(cs[j].mx[0][op], cs[j].mx[1][op]));
+    }
+    cycles += cyc0 + cyc1; columns += 2 * A;
+    cycles_op[0] += cyc0; cycles_op[1] += cyc1;
+    cost_tenths += extra; slot_rows += A;
+  }
+  void group(int g, long moves_per_cell) {
+    if (coloured) group_coloured(g, moves_per_cell); else group_greedy(g, moves_per_cell);
+  }
+  // the solver of PYCHAIN_PLAN_SLOTS=0: greedy placement, then single swaps
+  void group_greedy(int g, long moves_per_cell) {
+    Lcg rng{0x9E3779B9u ^ (uint32_t)((g * 2) * 2654435761u)};   // per group: results do not depend on the thread count
+    const int A = t.gsl[g];
+    int nr = 0;
+    for (int r = 0; r < 64; r++) if (g * 64 + r < (int)t.order.size()) nr = r + 1;
+    if (A == 0 || nr == 0) return;
+    int* cl = &cell[cell_off[g]];                    // [row][slot]
+    std::vector<Col> cs(A);
+    for (auto& c : cs) { memset(&c, 0, sizeof(c)); for (int hh = 0; hh < 2; hh++) c.nm[hh][0][0] = c.nm[hh][1][0] = 32; }
+    std::vector<int> b0(nr * A, -1), b1(nr * A, -1);   // banks of a cell's arc
+    bound += placement_bound(g, A, nr);
     // greedy: rows with most arcs first; each arc goes to the free slot of its row with fewest collisions in its half
     std::vector<int> rorder(nr);
     std::iota(rorder.begin(), rorder.end(), 0);
@@ -335,17 +592,33 @@ struct SlotOrder {
     cycles_op[0] += cyc0; cycles_op[1] += cyc1;
     cost_tenths += extra; slot_rows += A;
   }
-  // groups are independent: annealed on up to 32 host threads
-  void run(long moves_per_cell) {
-    const int n = (int)t.gsl.size();
+  // Groups are independent: the groups of all tiles given are annealed by one pool of host threads.  The pool is sized by
+  // the CPUs this process may run on (its affinity mask - a container sees the whole machine's count elsewhere), at most 16;
+  // PYCHAIN_PLAN_THREADS overrides.  Every group has its own random stream: the result does not depend on the pool.
+  static int pool_threads() {
+    long n = env_long("PYCHAIN_PLAN_THREADS", 0);
+    if (n <= 0) {
+      n = 1;
+      cpu_set_t set;
+      if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);
+    }
+    return (int)std::max(1L, std::min(16L, n));
+  }
+  struct Job { SlotOrder* so; long moves_per_cell; };
+  static void run_all(const std::vector<Job>& jobs) {
+    std::vector<std::pair<int, int>> items;            // (job, group)
+    for (size_t k = 0; k < jobs.size(); k++)
+      for (int g = 0; g < (int)jobs[k].so->t.gsl.size(); g++) items.push_back({(int)k, g});
+    const int n = (int)items.size();
     std::atomic<int> next{0};
-    auto work = [&]() { for (int i; (i = next++) < n;) group(i, moves_per_cell); };
-    const int nthreads = (int)std::min<long>(std::min<unsigned>(32u, std::max(1u, std::thread::hardware_concurrency())), (long)n);
+    auto work = [&]() { for (int i; (i = next++) < n;) jobs[items[i].first].so->group(items[i].second, jobs[items[i].first].moves_per_cell); };
+    const int nthreads = std::min(pool_threads(), std::max(n, 1));
     std::vector<std::thread> pool;
     for (int i = 1; i < nthreads; i++) pool.emplace_back(work);
     work();
     for (auto& th : pool) th.join();
   }
+  void run(long moves_per_cell) { run_all({Job{this, moves_per_cell}}); }
   // modelled LDS-busy cycles of the tile per frame: every slot-row issues one gather per operand
   double lds_cycles() const {
     const double base = (wide_op[0] ? 2.3 : 2.0) + (wide_op[1] ? 2.3 : 2.0);
@@ -771,6 +1044,9 @@ int64_t plan_build_impl(const int32_t* ft, const int32_t* fi, const float* fp, c
 // C3-size graph).  The sizing call keeps what it built, keyed by a hash of every input byte and the knobs; the fill call
 // with the same inputs copies it.  One entry per host thread.
 struct LastPlan { uint64_t key = 0; std::vector<char> blob; };
+// Raised whenever the same graph and knobs may compile to other bytes than before (2: slot order by edge colouring and Kempe
+// chains).  Part of the key here; the on-disk cache keeps its own copy (_plan.py: _SOLVER_REVISION) beside the library's hash.
+constexpr int kSolverRevision = 2;
 uint64_t fnv64(uint64_t h, const void* p, size_t n) {
   const unsigned char* c = (const unsigned char*)p;
   for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; }
@@ -787,13 +1063,13 @@ extern "C" int64_t pychain_hip_den_plan_build(
     return plan_build_impl(ft, fi, fp, bt, bi, bp, leaky, initial, final_, H, K, D, blob, blob_bytes);   // (reports the error)
   static thread_local LastPlan last;
   uint64_t key = 14695981039346656037ull;
-  const int dims[4] = {H, K, D, pychain_hip::call_knobs().plan_split};
+  const int dims[5] = {H, K, D, pychain_hip::call_knobs().plan_split, kSolverRevision};
   key = fnv64(key, dims, sizeof(dims));
   key = fnv64(key, ft, (size_t)K * 12); key = fnv64(key, fi, (size_t)H * 8); key = fnv64(key, fp, (size_t)K * 4);
   key = fnv64(key, bt, (size_t)K * 12); key = fnv64(key, bi, (size_t)H * 8); key = fnv64(key, bp, (size_t)K * 4);
   key = fnv64(key, leaky, (size_t)H * 4); key = fnv64(key, initial, (size_t)H * 4); key = fnv64(key, final_, (size_t)H * 4);
   for (const char* knob : {"PYCHAIN_PLAN_GENERAL", "PYCHAIN_PLAN_SLACK", "PYCHAIN_PLAN_BALANCE", "PYCHAIN_PLAN_ANNEAL", "PYCHAIN_PLAN_FIT",
-                           "PYCHAIN_PLAN_LINEAR", "PYCHAIN_PLAN_SPLIT", "PYCHAIN_PLAN_GAMMA_BOUND", "PYCHAIN_PLAN_SG"}) {
+                           "PYCHAIN_PLAN_LINEAR", "PYCHAIN_PLAN_SPLIT", "PYCHAIN_PLAN_GAMMA_BOUND", "PYCHAIN_PLAN_SG", "PYCHAIN_PLAN_SLOTS"}) {
     const char* v = getenv(knob);
     key = fnv64(key, knob, strlen(knob));
     if (v) key = fnv64(key, v, strlen(v));
@@ -964,17 +1240,20 @@ int64_t plan_build_impl(
   if (stats) fprintf(stderr, "[plan] pdf by state (one gather per arc): %s\n", pdf_by_state ? "yes" : "no");
   so_a.ignore_op1 = so_b.ignore_op1 = pdf_by_state;
   auto moves = [&](const Tile& t) { return anneal_knob >= 0 ? anneal_knob : (t.fitted ? 3000L : 200L); };
-  {
-    // the three tiles are independent (and every group has its own random stream: the result does not depend on the threads)
-    std::thread tb([&]() { so_b.run(moves(tiles[1])); }), tg([&]() { so_g.run(moves(tiles[2])); });
-    so_a.run(moves(tiles[0]));
-    tb.join(); tg.join();
-  }
+  // (the three tiles are independent: one pool takes the groups of all of them)
+  SlotOrder::run_all({{&so_a, moves(tiles[0])}, {&so_b, moves(tiles[1])}, {&so_g, moves(tiles[2])}});
   if (stats)
     fprintf(stderr, "[plan] modelled LDS cycles per half slot-row (2.0 = conflict-free): alpha %.3f beta %.3f gamma %.3f; "
                     "half slot-rows %ld %ld %ld\n", (double)so_a.cycles / std::max(1L, so_a.columns.load()),
             (double)so_b.cycles / std::max(1L, so_b.columns.load()), (double)so_g.cycles / std::max(1L, so_g.columns.load()),
             so_a.columns.load(), so_b.columns.load(), so_g.columns.load());
+  if (stats)
+    fprintf(stderr, "[plan] de Werra bound of this row placement, same unit (no slot order goes below): alpha %.3f (%.3f + %.3f) beta %.3f (%.3f + %.3f) gamma %.3f\n",
+            (double)so_a.bound / std::max(1L, so_a.columns.load()), (double)so_a.bound_op[0] / std::max(1L, so_a.columns.load()),
+            (double)so_a.bound_op[1] / std::max(1L, so_a.columns.load()),
+            (double)so_b.bound / std::max(1L, so_b.columns.load()), (double)so_b.bound_op[0] / std::max(1L, so_b.columns.load()),
+            (double)so_b.bound_op[1] / std::max(1L, so_b.columns.load()),
+            (double)so_g.bound / std::max(1L, so_g.columns.load()));
   if (stats)
     fprintf(stderr, "[plan] modelled LDS-busy cycles per frame (gfx950 gather costs): alpha %.0f (%ld slot-rows, conflicts %.0f) beta %.0f (%ld, %.0f)\n",
             so_a.lds_cycles(), so_a.slot_rows.load(), 0.1 * so_a.cost_tenths.load(), so_b.lds_cycles(), so_b.slot_rows.load(),
