@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 25
+#define PYCHAIN_HIP_ABI_VERSION 26
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -400,7 +400,8 @@ int pychain_hip_cpu_align(
  * bad_count, totals).  A sequence whose windows admit no path gets logP = -inf and counts in bad_count, like a graph with no
  * path of length L.  Option num_compat = 1 (the reference's own arithmetic) takes no windows: such a call fails
  * (PYCHAIN_HIP_EUNSUPPORTED, pychain_hip_last_error says why).  The fused calls offset the windows with the sequences of a
- * slice; pychain_hip_chain_loss_backward reads the stored rows and takes none.  pychain_hip_align takes none either. */
+ * slice; pychain_hip_chain_loss_backward reads the stored rows and takes none.  pychain_hip_align takes them as pychain_hip_align_tw
+ * (ABI 26, below). */
 int pychain_hip_num_forward_backward_tw(
     const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
     const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
@@ -436,6 +437,38 @@ int pychain_hip_cpu_num_forward_backward_tw(
     const float* nnet_output, const int64_t* seq_lengths,
     int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows);
+
+/* ------------------------------------------------------------------------
+ * Constrained re-alignment (ABI 26): pychain_hip_align under the time windows above - the best path among the paths that keep
+ * every state inside its window.  pychain_hip_align_tw / pychain_hip_cpu_align_tw are pychain_hip_align / pychain_hip_cpu_align
+ * with one argument more, last: time_windows, int32 [B][H][2] = {lo, hi} (dev; the host twin: host), one row per sequence also
+ * where the graph is shared, adm(t,h) iff lo <= t <= hi for the time index t in [0, L] exactly as above.  With the arcs, x and
+ * the arithmetic of pychain_hip_align (fp64 adds and compares only, its association, its tie rules):
+ *   s(0,h)   = initial(h)                                                     if adm(0,h)   else -inf
+ *   s(t+1,h) = max over k in [lo,hi) of  s(t,src_k) + ((double)lp_k + x(t,pdf_k))     if adm(t+1,h) else -inf
+ *   score    = max over the h with adm(L,h) of  s(L,h) + (double)final(h)             ties: the lowest h
+ * The mask is a select AFTER the max, and the NaN rule follows the numerator's ("a NaN term that reaches only masked states
+ * goes no further"): an arc term counts towards the NaN score only if its destination is admissible at t+1, a final term only
+ * if its state is admissible at L.  A sequence whose windows admit no path gets score -inf, every row -1 and one count in
+ * bad_count, as a graph with no path of length L does.  time_windows NULL: exactly pychain_hip_align, which forwards NULL.
+ * Windows that admit every state at every time (lo <= 0 and hi >= L; also -1 .. 2^31-1) give the same bits as NULL: score
+ * words, states, pdfs and bad_count.  The device and the host twin give the same bits.  The workspace is that of
+ * pychain_hip_align (pychain_hip_align_workspace_bytes); the windows are read where they are. */
+int pychain_hip_align_tw(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows);
+int pychain_hip_cpu_align_tw(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads, const int32_t* time_windows);
 
 /* ------------------------------------------------------------------------
  * Numerator posteriors as cross-entropy targets (ABI 20): the "xent regularisation" of chain training.  A second output of the

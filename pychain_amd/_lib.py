@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 25
+ABI_VERSION = 26
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -113,6 +113,9 @@ _SIGNATURES = {
     "pychain_hip_align": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "pychain_hip_align_half_native": (_i, [_i, _i, _i]),
     "pychain_hip_cpu_align": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    # (ABI 26: the same two under alignment time windows, one pointer more, last)
+    "pychain_hip_align_tw": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "pychain_hip_cpu_align_tw": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
     "pychain_hip_den_tseg_state": (_i, [_vp, _vp]),
     "pychain_hip_den_tseg_state_bytes": (_sz, []),
     "pychain_hip_rescale": (_i, [_vp, _i, _sz, _vp, _vp]),

@@ -19,6 +19,13 @@ model trains on numerators restricted to the previous model's alignment plus a t
     ali = viterbi_align(x_flat_start, lengths, num_graphs)
     num_graphs.set_time_windows(alignment_windows(ali, num_graphs.num_states, tolerance=2))
     loss = ChainLoss(den_graph)(x, lengths, num_graphs)
+
+and the pass after that re-aligns with the new model INSIDE the windows of the previous alignment, at a wider tolerance, so that
+alignments cannot jump between passes (constrained re-alignment, include/pychain_hip.h: pychain_hip_align_tw) -
+
+    num_graphs.set_time_windows(alignment_windows(ali, num_graphs.num_states, tolerance=6))
+    ali = viterbi_align(x_new_model, lengths, num_graphs, time_windows=True)
+    num_graphs.set_time_windows(alignment_windows(ali, num_graphs.num_states, tolerance=2))
 """
 import collections
 
@@ -32,13 +39,37 @@ __all__ = ["Alignment", "viterbi_align", "alignment_windows"]
 Alignment = collections.namedtuple("Alignment", ["pdfs", "states", "score", "ok"])
 
 
-def viterbi_align(nnet_output, input_lengths, num_graphs):
-    """Best path through every sequence's log-domain numerator graph (a ChainGraphBatch, from one shared graph or a list)."""
+def _explicit_windows(windows, num_graphs):
+    """Explicit windows with the checks, the dtype conversion and the saturation of ChainGraphBatch.set_time_windows."""
+    if not isinstance(windows, torch.Tensor) or windows.dtype not in (torch.int32, torch.int64, torch.int16, torch.int8,
+                                                                      torch.uint8):
+        raise ValueError("viterbi_align: time_windows must be None, True or an integer tensor, got %s"
+                         % (getattr(windows, "dtype", type(windows)),))
+    if tuple(windows.shape) != (num_graphs.batch_size, num_graphs.num_states, 2):
+        raise ValueError("viterbi_align: time_windows must have the shape [batch_size, num_states, 2] = [%d, %d, 2], got %s"
+                         % (num_graphs.batch_size, num_graphs.num_states, list(windows.shape)))
+    if windows.dtype == torch.int64:
+        windows = windows.clamp(-2 ** 31, 2 ** 31 - 1)          # (any int32 value is legal: saturate, do not wrap)
+    return windows.to(torch.int32).contiguous()
+
+
+def viterbi_align(nnet_output, input_lengths, num_graphs, time_windows=None):
+    """Best path through every sequence's log-domain numerator graph (a ChainGraphBatch, from one shared graph or a list).
+
+    `time_windows`: None - the free best path (a batch that carries windows is refused: say which you mean); True - the best
+    path among those that keep every state inside the batch's own windows (set_time_windows); an integer tensor
+    [batch_size, num_states, 2] on any device - the same under these windows, whatever the batch carries.  A sequence whose
+    windows admit no path has score -inf, ok False and every row -1."""
     if not isinstance(num_graphs, ChainGraphBatch):
         raise TypeError("viterbi_align: num_graphs must be a ChainGraphBatch")
-    if getattr(num_graphs, "time_windows", None) is not None:
-        raise ValueError("viterbi_align: this batch carries time windows (set_time_windows); constrained re-alignment is not "
-                         "supported - align on a batch without them")
+    own = getattr(num_graphs, "time_windows", None)
+    if time_windows is None and own is not None:
+        raise ValueError("viterbi_align: this batch carries time windows (set_time_windows); pass time_windows=True to align "
+                         "inside them (constrained re-alignment), explicit windows as a tensor, or align on a batch without them")
+    if time_windows is True and own is None:
+        raise ValueError("viterbi_align: time_windows=True, but this batch carries no time windows (set_time_windows)")
+    if time_windows is False:
+        raise ValueError("viterbi_align: time_windows must be None, True or an integer tensor")
     if not num_graphs.log_domain:
         raise ValueError("viterbi_align: the graphs must be log-domain numerator graphs (log_domain=True); denominator graphs "
                          "(leaky-HMM, probability domain) have no best-path meaning here")
@@ -49,12 +80,18 @@ def viterbi_align(nnet_output, input_lengths, num_graphs):
             .format(B, num_graphs.batch_size))
     x = nnet_output.detach()
     with torch.no_grad():
+        if time_windows is None:
+            tw = None
+        elif time_windows is True:
+            tw = num_graphs.device_time_windows(x.device) if x.is_cuda else own
+        else:
+            tw = _explicit_windows(time_windows, num_graphs).to(x.device)
         if not x.is_cuda:
-            score, states, pdfs, _ = native.cpu_align(num_graphs, x, input_lengths)
+            score, states, pdfs, _ = native.cpu_align(num_graphs, x, input_lengths, windows=tw)
         else:
             gt = num_graphs.device_tensors(x.device)
             gstride = 0 if num_graphs.shared_graph is not None else 1
-            score, states, pdfs, _ = native.align(gt, gstride, num_graphs.num_states, x, input_lengths)
+            score, states, pdfs, _ = native.align(gt, gstride, num_graphs.num_states, x, input_lengths, windows=tw)
         ok = torch.isfinite(score)
     return Alignment(pdfs, states, score, ok)
 

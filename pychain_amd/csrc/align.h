@@ -25,6 +25,7 @@ struct AlignArgs {
   int Hb;                    // row stride of bp16 (H rounded up to even: rows are read back as 32-bit words)
   int walk_bytes;            // tile: LDS bytes of the region the backtrace stages rows in (>= the score + row buffers it reuses)
   int general;               // graphs beyond the tile kernels (num_needs_general)
+  const int32_t* windows;    // [B,H,2] {lo, hi} alignment time windows (pychain_hip_align_tw), nullptr = none
 };
 
 int align_walk_bytes(int H, int K, int D);

@@ -9,11 +9,16 @@
 //                          wave, turned into the winning arc's packed (state, pdf) and staged in LDS, while one lane walks the
 //                          previous block inside LDS (one dependent LDS read per frame) - double-buffered, one barrier per block.
 //   align_general_kernel   graphs beyond the tile kernels (num_needs_general): score vectors and int32 backpointers in the
-//                          workspace, states strided over 1024 threads, a barrier per frame, a plain walk at the end.
+//                          workspace, states strided over 1024 threads, a barrier per frame, a plain walk at the end.  It
+//                          reads the time windows from global memory where they are.
 //
 // Both reach the same bits as the host twin (cpu.cpp: align_one): fp64 adds and compares only, in the association
 //   s(t+1,h) = max_k  s(t,src_k) + ((double)lp_k + (double)clamp(x(t,pdf_k)))      (first k in list order wins ties)
 //   score    = max_h  s(L,h) + (double)final(h)                                      (lowest h wins ties)
+// TW: alignment time windows (AlignArgs::windows, include/pychain_hip.h: pychain_hip_align_tw): a state outside its window at
+// time t gets -inf and backpointer 0 and skips its arcs - the select after the max, and a NaN term that reaches only masked
+// states goes no further; the initial row and the final argmax take the mask.  A flag of the template, as num_fb_kernel's: the
+// instantiations without it keep their instructions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -65,7 +70,7 @@ __device__ __forceinline__ void pad_rows(const AlignArgs& a, int b, int L, bool 
   for (int t = (ok ? L + 1 : 0) + tid; t <= a.T; t += nt) st[t] = -1;
 }
 
-template <int VEC, int XCH, int LD, bool XH = false>
+template <int VEC, int XCH, int LD, bool XH = false, bool TW = false>
 __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
   constexpr int NTOT = kAlNT + LD;
   constexpr int NW = NTOT / 64;
@@ -113,18 +118,26 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
   };
   uint16_t* bps = a.bp16 + (size_t)b * T * a.Hb;
   const int2* idx = reinterpret_cast<const int2*>(a.bwd_idx + g * H * 2);
+  const int32_t* win = TW ? a.windows + (size_t)b * H * 2 : nullptr;         // {lo, hi} per state: one row per sequence
+  auto adm_at = [&](int h, int t) { return win[2 * h] <= t && t <= win[2 * h + 1]; };
 
   const int h0 = tid;
   const bool own = h0 < H && tid < kAlNT;
   int2 be = make_int2(0, 0);
   if (own) be = idx[h0];
+  int wlo = 0, whi = 0;
+  if constexpr (TW) if (own) { wlo = win[2 * h0]; whi = win[2 * h0 + 1]; }
   XRow<LD ? LD : kAlNT, VEC, XCH> xq;
   const int xt = LD ? tid - kAlNT : tid;
   {
     const float* xrow = XH ? nullptr : xseq;
     if (!LD || tid >= kAlNT) xload(xq, 0, xt);
     if (tid < kAlNT)
-      for (int h = tid; h < H; h += kAlNT) va[h] = (double)a.initial[g * H + h];
+      for (int h = tid; h < H; h += kAlNT) {
+        double v = (double)a.initial[g * H + h];
+        if constexpr (TW) if (!adm_at(h, 0)) v = -INFINITY;
+        va[h] = v;
+      }
     if (!LD || tid >= kAlNT) stage(xq, xr0, xrow, xt);
   }
   __syncthreads();
@@ -171,16 +184,17 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
       if (own) {
         double best = -INFINITY;
         int bi = 0;
-        if (n0 > 0) {
+        const bool adm = !TW || (wlo <= s && s <= whi);          // (a masked state: -inf, backpointer 0, no arc term counts)
+        if (adm && n0 > 0) {
           best = vin[w0.pk & 0xffffu] + ((double)w0.lp + (double)xcur[w0.pk >> 16]);
           nanf |= best != best;
         }
-        if (n0 > 1) {
+        if (adm && n0 > 1) {
           const double e = vin[w1.pk & 0xffffu] + ((double)w1.lp + (double)xcur[w1.pk >> 16]);
           nanf |= e != e;
           if (e > best) { best = e; bi = 1; }
         }
-        for (int k = be.x + 2; k < be.y; k++) {
+        for (int k = be.x + 2; k < (adm ? be.y : 0); k++) {
           const AArc w = arc[k];
           const double e = vin[w.pk & 0xffffu] + ((double)w.lp + (double)xcur[w.pk >> 16]);
           nanf |= e != e;
@@ -190,7 +204,8 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
         brow[h0] = (uint16_t)bi;
       }
       for (int h = h0 + kAlNT; h < H; h += kAlNT) {             // graphs with more than 512 states
-        const int2 e2 = idx[h];
+        int2 e2 = idx[h];
+        if constexpr (TW) if (!adm_at(h, s)) e2.y = e2.x;
         double best = -INFINITY;
         int bi = 0;
         for (int k = e2.x; k < e2.y; k++) {
@@ -213,6 +228,7 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
   int mi = 0x7fffffff;
   if (tid < kAlNT)
     for (int h = tid; h < H; h += kAlNT) {
+      if constexpr (TW) if (!adm_at(h, L)) continue;
       const double e = vL[h] + (double)a.final_[g * H + h];
       nanf |= e != e;
       if (e > mx) { mx = e; mi = h; }
@@ -322,6 +338,7 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
 // ------------------------------------------------------------------------------------
 // graphs beyond the tile kernel: everything in global memory
 // ------------------------------------------------------------------------------------
+template <bool TW>
 __global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a) {
   __shared__ double redd[kAlGT / 64];
   __shared__ int redi[kAlGT / 64], redn[kAlGT / 64];
@@ -336,7 +353,13 @@ __global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a)
   const float* xseq = a.x + (size_t)b * T * D;
   double* sc = a.gen_sc + (size_t)b * 2 * H;
   int32_t* bps = a.bp32 + (size_t)b * T * H;
-  for (int h = tid; h < H; h += kAlGT) sc[h] = (double)a.initial[g * H + h];
+  const int32_t* win = TW ? a.windows + (size_t)b * H * 2 : nullptr;
+  auto adm_at = [&](int h, int t) { return win[2 * h] <= t && t <= win[2 * h + 1]; };
+  for (int h = tid; h < H; h += kAlGT) {
+    double v = (double)a.initial[g * H + h];
+    if constexpr (TW) if (!adm_at(h, 0)) v = -INFINITY;
+    sc[h] = v;
+  }
   __threadfence();
   __syncthreads();
   int nanf = 0;
@@ -346,7 +369,8 @@ __global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a)
     const float* xrow = xseq + (size_t)(s - 1) * D;
     int32_t* brow = bps + (size_t)(s - 1) * H;
     for (int h = tid; h < H; h += kAlGT) {
-      const int2 be = idx[h];
+      int2 be = idx[h];
+      if constexpr (TW) if (!adm_at(h, s)) be.y = be.x;
       double best = -INFINITY;
       int bi = 0;
       for (int k = be.x; k < be.y; k++) {
@@ -364,6 +388,7 @@ __global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a)
   double mx = -INFINITY;
   int mi = 0x7fffffff;
   for (int h = tid; h < H; h += kAlGT) {
+    if constexpr (TW) if (!adm_at(h, L)) continue;
     const double e = fresh_f64(vL + h) + (double)a.final_[g * H + h];
     nanf |= e != e;
     if (e > mx) { mx = e; mi = h; }
@@ -394,13 +419,17 @@ __global__ __launch_bounds__(kAlGT) void align_general_kernel(const AlignArgs a)
   }
 }
 
-template <int VEC, int XCH, int LD, bool XH>
-hipError_t launch_align_x(const AlignArgs& a, size_t lds, hipStream_t st) {
-  auto k = align_kernel<VEC, XCH, LD, XH>;
+template <int VEC, int XCH, int LD, bool XH, bool TW>
+hipError_t launch_align_w(const AlignArgs& a, size_t lds, hipStream_t st) {
+  auto k = align_kernel<VEC, XCH, LD, XH, TW>;
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3(a.B), dim3(kAlNT + LD), lds, st, a);
   return hipGetLastError();
+}
+template <int VEC, int XCH, int LD, bool XH>
+hipError_t launch_align_x(const AlignArgs& a, size_t lds, hipStream_t st) {
+  return a.windows ? launch_align_w<VEC, XCH, LD, XH, true>(a, lds, st) : launch_align_w<VEC, XCH, LD, XH, false>(a, lds, st);
 }
 template <int VEC, int XCH, int LD = 0>
 hipError_t launch_align_t(const AlignArgs& a, size_t lds, hipStream_t st) {
@@ -430,7 +459,8 @@ size_t align_lds_bytes(int H, int K, int D) { return (size_t)align_walk_bytes(H,
 
 hipError_t launch_align(const AlignArgs& a, hipStream_t st, const char** why) {
   if (a.general) {
-    hipLaunchKernelGGL(align_general_kernel, dim3(a.B), dim3(kAlGT), 0, st, a);
+    if (a.windows) hipLaunchKernelGGL(align_general_kernel<true>, dim3(a.B), dim3(kAlGT), 0, st, a);
+    else hipLaunchKernelGGL(align_general_kernel<false>, dim3(a.B), dim3(kAlGT), 0, st, a);
     return hipGetLastError();
   }
   const size_t lds = align_lds_bytes(a.H, a.K, a.D);

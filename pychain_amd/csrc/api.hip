@@ -692,14 +692,14 @@ extern "C" int pychain_hip_align_half_native(int H, int K, int D) {
   return align_half_native(H, K, D) ? 1 : 0;
 }
 
-extern "C" int pychain_hip_align(
+extern "C" int pychain_hip_align_tw(
     const int32_t* ft, const int32_t* fi, const float* fp,
     const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
     int B, int T, int D, int H, int K,
     double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream) {
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
   const char* who = "align";
   (void)ft; (void)fi; (void)fp;                      // (the recursion gathers over the arcs entering each state only)
   if (nnet_output_dtype < PYCHAIN_HIP_F32 || nnet_output_dtype > PYCHAIN_HIP_F16)
@@ -725,6 +725,7 @@ extern "C" int pychain_hip_align(
   a.graph_stride = graph_batch_stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
   a.Hb = (H + 1) & ~1;
   a.general = num_needs_general(H, K, D) ? 1 : 0;
+  a.windows = time_windows;                          // (nullptr: the kernels without the mask, exactly the call before ABI 26)
   char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
   if (a.general) { a.bp32 = (int32_t*)(ws + c.bp); a.gen_sc = (double*)(ws + c.sc); }
   else { a.bp16 = (uint16_t*)(ws + c.bp); a.walk_bytes = align_walk_bytes(H, K, D); }
@@ -736,6 +737,18 @@ extern "C" int pychain_hip_align(
   if (e != hipSuccess)
     return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_align(
+    const int32_t* ft, const int32_t* fi, const float* fp,
+    const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  return pychain_hip_align_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
+                              B, T, D, H, K, score_per_seq, states, pdfs, bad_count, workspace, workspace_bytes, stream, nullptr);
 }
 
 // ---- fused ChainLoss ------------------------------------------------------------------

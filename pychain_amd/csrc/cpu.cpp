@@ -213,13 +213,16 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
 
 // ---- Viterbi alignment over a numerator graph (include/pychain_hip.h: pychain_hip_cpu_align; the device's align.hip) ----------
 // fp64 adds and compares only, in the association and with the tie rules the device kernels use, so both give the same bits.
+// win: the sequence's time windows, {lo, hi} per state, or nullptr (pychain_hip_cpu_align_tw): a state outside its window gets
+// -inf, selected after its max, and its arc terms (its final term at L) do not count towards the NaN flag - as on the device
 bool align_one(const Csr& bwd, const float* init, const float* fin, const float* x, int L, int T, int D, int H, double* score,
-               int32_t* states, int64_t* pdfs) {
+               int32_t* states, int64_t* pdfs, const int32_t* win) {
   const double ninf = -std::numeric_limits<double>::infinity();
+  auto adm = [win](int h, int t) { return !win || (win[2 * h] <= t && t <= win[2 * h + 1]); };
   std::vector<double> sa((size_t)H), sb((size_t)H);
   std::vector<int32_t> bp((size_t)L * H);           // winning arc (absolute index) of every (frame, state)
   bool nan = false;
-  for (int h = 0; h < H; h++) sa[h] = (double)init[h];
+  for (int h = 0; h < H; h++) sa[h] = adm(h, 0) ? (double)init[h] : ninf;
   for (int t = 0; t < L; t++) {
     const float* xr = x + (size_t)t * D;
     const double* vin = (t & 1) ? sb.data() : sa.data();
@@ -229,6 +232,7 @@ bool align_one(const Csr& bwd, const float* init, const float* fin, const float*
       const int lo = bwd.idx[2 * h], hi = bwd.idx[2 * h + 1];
       double best = ninf;
       int bk = lo;
+      if (!adm(h, t + 1)) { vout[h] = ninf; brow[h] = lo; continue; }
       for (int k = lo; k < hi; k++) {
         const double e = vin[bwd.trans[3 * k]] + ((double)bwd.prob[k] + (double)clamp30(xr[bwd.trans[3 * k + 2]]));
         nan = nan || e != e;
@@ -242,6 +246,7 @@ bool align_one(const Csr& bwd, const float* init, const float* fin, const float*
   double best = ninf;
   int hstar = 0;
   for (int h = 0; h < H; h++) {
+    if (!adm(h, L)) continue;
     const double e = vL[h] + (double)fin[h];
     nan = nan || e != e;
     if (e > best) { best = e; hstar = h; }
@@ -362,11 +367,11 @@ extern "C" int pychain_hip_cpu_num_forward_backward(
                                                  B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, num_threads, nullptr);
 }
 
-extern "C" int pychain_hip_cpu_align(
+extern "C" int pychain_hip_cpu_align_tw(
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K,
-    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads) {
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads, const int32_t* time_windows) {
   const char* who = "cpu_align";
   int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, score_per_seq, states, bad_count,
                         B, T, D, H, K);
@@ -379,11 +384,21 @@ extern "C" int pychain_hip_cpu_align(
     const size_t g = (size_t)b * graph_batch_stride;
     const Csr bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
     const bool ok = align_one(bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
-                              score_per_seq + b, states + (size_t)b * (T + 1), pdfs + (size_t)b * T);
+                              score_per_seq + b, states + (size_t)b * (T + 1), pdfs + (size_t)b * T,
+                              time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
     if (!ok) bad++;
   });
   *bad_count = bad.load();
   return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_align(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K,
+    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads) {
+  return pychain_hip_cpu_align_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, seq_lengths, B, T, D, H, K,
+                                  score_per_seq, states, pdfs, bad_count, num_threads, nullptr);
 }
 
 extern "C" int pychain_hip_cpu_num_forward_backward_xent(

@@ -721,8 +721,9 @@ def cpu_topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     return pdfs, probs
 
 
-def align(gt, graph_stride, num_states, x, lengths):
-    """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors.
+def align(gt, graph_stride, num_states, x, lengths, windows=None):
+    """Viterbi alignment on the GPU (include/pychain_hip.h: pychain_hip_align).  `gt`: dict of device graph tensors; `windows`:
+    int32 [B, H, 2] device time windows (pychain_hip_align_tw: the best path inside them) or None.
     Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32), all on x's device."""
     _require_device(x, "nnet_output")
     x = _kernel_tensor(x.detach())
@@ -739,17 +740,19 @@ def align(gt, graph_stride, num_states, x, lengths):
         pdfs = torch.empty(B, T, dtype=torch.int64, device=dev)
         bad = torch.empty(1, dtype=torch.int32, device=dev)
         ws = _workspace(L.pychain_hip_align_workspace_bytes(B, T, int(num_states), K, D), dev, "align")
-        _lib.check(L.pychain_hip_align(
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states), dev)
+        _lib.check(L.pychain_hip_align_tw(
             *_graph_ptrs(gt), int(graph_stride),
             x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K,
-            score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)),
-            "pychain_hip_align")
+            score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev),
+            _ptr(windows)), "pychain_hip_align_tw")
     return score, states, pdfs, bad
 
 
-def cpu_align(graphs, x, lengths):
+def cpu_align(graphs, x, lengths, windows=None):
     """Viterbi alignment on CPU tensors (the host twin, pychain_hip_cpu_align): same results, bit for bit, as `align` on the
-    fp32 value of the same input.  Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32)."""
+    fp32 value of the same input.  `windows`: int32 [B, H, 2] time windows (pychain_hip_cpu_align_tw) or None.  Returns (score[B] float64, states[B,T+1] int32, pdfs[B,T] int64, bad_count[1] int32)."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_align is for CPU tensors; device tensors run on the HIP kernels")
     xf, lc = _host_inputs(x, lengths)
@@ -760,9 +763,10 @@ def cpu_align(graphs, x, lengths):
     states = torch.empty(B, T + 1, dtype=torch.int32)
     pdfs = torch.empty(B, T, dtype=torch.int64)
     bad = torch.zeros(1, dtype=torch.int32)
-    _lib.check(_lib.lib().pychain_hip_cpu_align(
+    tw = None if windows is None else _check_windows(windows.cpu(), B, H)
+    _lib.check(_lib.lib().pychain_hip_cpu_align_tw(
         *[t.data_ptr() for t in ts], stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K,
-        score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_align")
+        score.data_ptr(), states.data_ptr(), pdfs.data_ptr(), bad.data_ptr(), int(CPU_THREADS), _ptr(tw)), "pychain_hip_cpu_align_tw")
     return score, states, pdfs, bad
 
 
