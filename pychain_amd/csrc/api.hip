@@ -17,9 +17,7 @@
 #include "den_policy.h"
 #include "device_utils.h"
 #include "num_kernels.h"
-#include "outreg.h"
 #include "plan_format.h"
-#include "weights.h"
 #include "xent.h"
 
 namespace pychain_hip {
@@ -61,7 +59,6 @@ int option_int(const char* name) {            // (a name of kOptions)
   return option_value(name, &v) ? atoi(v.c_str()) : find_option(name)->dflt;
 }
 bool option_set(const char* name) { std::string v; return option_value(name, &v); }
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 }  // namespace
 
 CallKnobs call_knobs() {
@@ -1092,82 +1089,6 @@ extern "C" int pychain_hip_loss_total(const float* den_objf_per_seq, const float
                      norm_dev, out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "loss_total: %s", hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
-}
-
-// ---- output regularisers (include/pychain_hip.h: pychain_hip_output_reg; outreg.hip) ------------------------------------
-extern "C" size_t pychain_hip_output_reg_workspace_bytes(int B, int T) {
-  if (B <= 0 || T <= 0) return 0;
-  return align256(outreg_workspace_bytes(B, T)) + 256;
-}
-
-extern "C" int pychain_hip_output_reg(
-    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
-    float l2, float oor, float limit, int grad_mode, void* grad,
-    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
-    float* reg_per_seq, float loss_scale, float* reg_totals, float* totals,
-    void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "output_reg";
-  if (nnet_output_dtype < PYCHAIN_HIP_F32 || nnet_output_dtype > PYCHAIN_HIP_F16)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, nnet_output_dtype);
-  if (!nnet_output || !seq_lengths || !reg_per_seq || !workspace) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
-  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
-  if (!(l2 >= 0.f) || !(oor >= 0.f) || !(limit >= 0.f))
-    return fail(PYCHAIN_HIP_EINVAL, "%s: l2, oor and limit must not be negative (got %g, %g, %g)", who, (double)l2, (double)oor, (double)limit);
-  if (grad_mode != PYCHAIN_HIP_GRAD_ACCUM && grad_mode != PYCHAIN_HIP_GRAD_LINEAR)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: grad_mode must be PYCHAIN_HIP_GRAD_ACCUM or PYCHAIN_HIP_GRAD_LINEAR, got %d", who, grad_mode);
-  if (((uintptr_t)nnet_output | (uintptr_t)grad | (uintptr_t)workspace) & 15)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output, grad and workspace must be 16-byte aligned", who);
-  const size_t need = pychain_hip_output_reg_workspace_bytes(B, T);
-  if (workspace_bytes < need) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  OutRegArgs a;
-  memset(&a, 0, sizeof(a));
-  a.x = nnet_output; a.x_half = nnet_output_dtype; a.grad = grad;
-  a.mode = !grad ? kRegNoGrad : (grad_mode == PYCHAIN_HIP_GRAD_ACCUM ? kRegAccum : kRegLinear);
-  a.l2 = l2; a.oor = oor; a.limit = limit; a.scale = grad_scale; a.scale_dev = grad_scale_dev; a.norm_dev = loss_norm_dev;
-  a.lengths = seq_lengths; a.frame_pairs = (double*)ws; a.seq_pairs = (double*)(ws + 16 * (size_t)B * T); a.per_seq = reg_per_seq;
-  a.B = B; a.T = T; a.D = D;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = launch_outreg_rows(a, st);
-  if (e == hipSuccess && (reg_totals || totals)) e = launch_outreg_totals(a.seq_pairs, B, l2, oor, loss_scale, loss_norm_dev, reg_totals, totals, st);
-  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
-}
-
-// ---- utterance and derivative weights (include/pychain_hip.h: pychain_hip_weight_rows; weights.hip) ---------------------
-extern "C" int pychain_hip_weight_rows(
-    void* grad, int grad_dtype, const int64_t* seq_lengths, int B, int T, int D,
-    const float* utt_weights, const float* deriv_weights,
-    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
-    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
-    float* totals, float* weighted, void* stream) {
-  const char* who = "weight_rows";
-  if (!utt_weights && !deriv_weights) return fail(PYCHAIN_HIP_EINVAL, "%s: neither utt_weights nor deriv_weights", who);
-  if (!seq_lengths) return fail(PYCHAIN_HIP_EINVAL, "%s: null seq_lengths", who);
-  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
-  if (grad && (grad_dtype < PYCHAIN_HIP_F32 || grad_dtype > PYCHAIN_HIP_F16)) return fail(PYCHAIN_HIP_EINVAL, "%s: unknown grad_dtype %d", who, grad_dtype);
-  if ((uintptr_t)grad & 15) return fail(PYCHAIN_HIP_EINVAL, "%s: grad must be 16-byte aligned", who);
-  const bool sums = totals || weighted;
-  if (!grad && !sums) return fail(PYCHAIN_HIP_EINVAL, "%s: nothing to do (no grad, no totals, no weighted)", who);
-  if (sums && (!den_objf_per_seq || !num_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: the sums need den_objf_per_seq and num_objf_per_seq", who);
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipSuccess;
-  if (grad) {
-    WeightRowsArgs a;
-    memset(&a, 0, sizeof(a));
-    a.grad = grad; a.dtype = grad_dtype; a.lengths = seq_lengths; a.u = utt_weights; a.f = deriv_weights; a.B = B; a.T = T; a.D = D;
-    e = launch_weight_rows(a, st);
-  }
-  if (e == hipSuccess && sums) {
-    WeightSumsArgs s;
-    memset(&s, 0, sizeof(s));
-    s.lengths = seq_lengths; s.u = utt_weights; s.den = den_objf_per_seq; s.num = num_objf_per_seq; s.xent = xent_objf_per_seq;
-    s.reg = reg_per_seq; s.xent_coef = xent_coef; s.l2 = l2; s.oor = oor; s.loss_scale = loss_scale; s.norm_dev = loss_norm_dev;
-    s.totals = totals; s.weighted = weighted; s.B = B; s.T = T;
-    e = launch_weight_sums(s, st);
-  }
-  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
   return PYCHAIN_HIP_OK;
 }
 

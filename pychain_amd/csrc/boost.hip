@@ -38,7 +38,7 @@
 #include "../../include/pychain_hip.h"
 #include "boost.h"
 #include "common.h"
-#include "device_utils.h"
+#include "row_access.h"
 
 namespace pychain_hip {
 namespace {
@@ -46,35 +46,7 @@ namespace {
 constexpr int kBoNT = 256;                          // four waves
 constexpr int kBoRows = 2;                          // rows in flight per wave
 constexpr int kBoChunk = (kBoNT / 64) * kBoRows;    // frames of one work item
-constexpr int kBoMaxGrid = 2048;                    // 256 CUs x 8 workgroups: the rest is strided over
 
-// VW elements at element offset e, widened to fp32: 16 bytes of fp32, 8 bytes of a 2-byte type, or one element
-template <int XH, int VW>
-__device__ __forceinline__ void bo_load(const void* p, size_t e, float (&v)[VW]) {
-  static_assert(VW == 4 || VW == 1, "four elements or one");
-  if constexpr (XH == kXF32) {
-    if constexpr (VW == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + e);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      v[0] = reinterpret_cast<const float*>(p)[e];
-    }
-  } else {
-    constexpr bool BF = XH == kXBf16;
-    const uint16_t* h = reinterpret_cast<const uint16_t*>(p) + e;
-    if constexpr (VW == 4) {
-      const uint2 q = *reinterpret_cast<const uint2*>(h);
-      half2_to_f32(q.x, BF, v[0], v[1]); half2_to_f32(q.y, BF, v[2], v[3]);
-    } else {
-      v[0] = half_bits_to_f32(*h, BF);
-    }
-  }
-}
-template <int VW>
-__device__ __forceinline__ void bo_store(float* p, size_t e, const float (&v)[VW]) {
-  if constexpr (VW == 4) *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
-  else p[e] = v[0];
-}
 // exp(-boost * qd): the product rounded, then exp_bounded's two instructions
 __device__ __forceinline__ float bo_factor(float boost, float qd) {
 #pragma clang fp contract(off)
@@ -138,14 +110,15 @@ __device__ __forceinline__ void bo_targets(const BoostArgs& a, size_t f, int lan
       const float fu = lane_float(fac, j);
       if (((du / VW) & 63) == lane) {                             // the lane whose dense store wrote this element
         float v[1];
-        bo_load<XH, 1>(a.x, row + du, v);
+        row_load<XH, 1>(a.x, row + du, v);
         a.e[row + du] = bo_mul(clamp_exp(v[0], kXExpClamp), fu);
       }
     }
   }
 }
 
-// XH: x's element type; VW: elements per access (1: rows that are no multiple of 4 elements)
+// XH: x's element type; VW: elements per access, 4 or 1 (1: rows that are no multiple of 4 elements) - row_load<XH, VW> of x,
+// row_store<kXF32, VW> of e, row_load<XH, 1> where an entry is applied
 template <int XH, int VW>
 __global__ __launch_bounds__(kBoNT) void boost_rows_kernel(const BoostArgs a, int nchunk, int nitems) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -163,8 +136,8 @@ __global__ __launch_bounds__(kBoNT) void boost_rows_kernel(const BoostArgs a, in
 #pragma unroll 2
     for (int e = lane * VW; e < D; e += 64 * VW) {
       float xa[VW], xb[VW];
-      bo_load<XH, VW>(a.x, row0 + e, xa);
-      bo_load<XH, VW>(a.x, row1 + e, xb);
+      row_load<XH, VW>(a.x, row0 + e, xa);
+      row_load<XH, VW>(a.x, row1 + e, xb);
 #pragma unroll
       for (int i = 0; i < VW; i++) {
         nan0 = nan0 || xa[i] != xa[i];
@@ -172,8 +145,8 @@ __global__ __launch_bounds__(kBoNT) void boost_rows_kernel(const BoostArgs a, in
         xa[i] = clamp_exp(xa[i], kXExpClamp);
         xb[i] = clamp_exp(xb[i], kXExpClamp);
       }
-      bo_store<VW>(a.e, row0 + e, xa);
-      if (two) bo_store<VW>(a.e, row1 + e, xb);
+      row_store<kXF32, VW>(a.e, row0 + e, xa);
+      if (two) row_store<kXF32, VW>(a.e, row1 + e, xb);
     }
     bo_targets<XH, VW>(a, f0, lane, bad);
     if (two) bo_targets<XH, VW>(a, f0 + 1, lane, bad);
@@ -197,7 +170,7 @@ hipError_t launch_boost_rows(const BoostArgs& a, hipStream_t st) {
   const int nchunk = (a.T + kBoChunk - 1) / kBoChunk;
   const size_t items = (size_t)a.B * nchunk;
   if (items > (size_t)INT_MAX || (size_t)a.B * a.T > (size_t)INT_MAX) return hipErrorInvalidValue;
-  const int nitems = (int)items, grid = nitems < kBoMaxGrid ? nitems : kBoMaxGrid;
+  const int nitems = (int)items, grid = nitems < kRowPassMaxGrid ? nitems : kRowPassMaxGrid;
   hipError_t e = hipMemsetAsync(a.bad_count, 0, sizeof(int32_t), st);
   if (e != hipSuccess) return e;
   if (a.x_half == kXF32) return launch_as<kXF32>(a, grid, nchunk, nitems, st);

@@ -3,6 +3,7 @@
 #define PYCHAIN_HIP_COMMON_H_
 
 #include <cstdarg>
+#include <cstddef>
 #include <cstdio>
 
 namespace pychain_hip {
@@ -41,6 +42,9 @@ struct CallKnobs {
   float corrupt_scale;
 };
 CallKnobs call_knobs();
+
+// workspace layouts: every part starts on a multiple of 256 bytes
+inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 inline int fail(int code, const char* fmt, ...) {
   va_list ap;

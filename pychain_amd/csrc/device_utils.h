@@ -1,4 +1,5 @@
-// device_utils.h - small device helpers shared by the den and num kernels.
+// device_utils.h - small device helpers shared by the den and num kernels and, through row_access.h (the typed row loads and
+// stores built on the 2-byte conversions below), by the row passes: outreg.hip, weights.hip, post.hip, boost.hip, xent.hip.
 #ifndef PYCHAIN_HIP_DEVICE_UTILS_H_
 #define PYCHAIN_HIP_DEVICE_UTILS_H_
 

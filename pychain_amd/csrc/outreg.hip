@@ -34,67 +34,38 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstring>
 
-#include "device_utils.h"
-#include "outreg.h"
+#include "../../include/pychain_hip.h"
+#include "common.h"
+#include "row_access.h"
 
 namespace pychain_hip {
+
+enum { kRegNoGrad = 0, kRegAccum = 1, kRegLinear = 2 };
+
+// (used by this file alone; outside the unnamed namespace because the kernels' symbols carry its name)
+struct OutRegArgs {
+  const void* x;             // [B,T,D] raw, x_half: 0 fp32, kXBf16 / kXF16 (device_utils.h): 2-byte rows are read as they are
+  int x_half;
+  void* grad;                // [B,T,D] in x's type, or nullptr (mode kRegNoGrad)
+  int mode;
+  float l2, oor, limit;
+  float scale;               // s = scale [* *scale_dev] [/ *norm_dev]
+  const float* scale_dev;
+  const float* norm_dev;
+  const int64_t* lengths;    // [B]
+  double* frame_pairs;       // [B,T,2] scratch: {sum x^2, sum e^2} of every live frame
+  double* seq_pairs;         // [B,2] scratch: the unrounded per-sequence sums
+  float* per_seq;            // [B,2] out
+  int B, T, D;
+};
+
 namespace {
 
 constexpr int kRgNT = 256;                          // four waves
 constexpr int kRgRows = 2;                          // frames in flight per wave
 constexpr int kRgChunk = (kRgNT / 64) * kRgRows;    // frames of one work item
-constexpr int kRgMaxGrid = 2048;                    // 256 CUs x 8 workgroups: the rest is strided over
-
-// VW elements at element offset e: 16 bytes (fp32 x 4, 2-byte x 8), 8 bytes (2-byte x 4) or one element
-template <int XH, int VW>
-__device__ __forceinline__ void rg_load(const void* p, size_t e, float (&v)[VW]) {
-  if constexpr (XH == kXF32) {
-    static_assert(VW == 4 || VW == 1, "fp32 rows: float4 or one element");
-    if constexpr (VW == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + e);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      v[0] = reinterpret_cast<const float*>(p)[e];
-    }
-  } else {
-    static_assert(VW == 8 || VW == 4 || VW == 1, "2-byte rows: eight, four or one element");
-    constexpr bool BF = XH == kXBf16;
-    const uint16_t* h = reinterpret_cast<const uint16_t*>(p) + e;
-    if constexpr (VW == 8) {
-      const uint4 q = *reinterpret_cast<const uint4*>(h);
-      half2_to_f32(q.x, BF, v[0], v[1]); half2_to_f32(q.y, BF, v[2], v[3]);
-      half2_to_f32(q.z, BF, v[4], v[5]); half2_to_f32(q.w, BF, v[6], v[7]);
-    } else if constexpr (VW == 4) {
-      const uint2 q = *reinterpret_cast<const uint2*>(h);
-      half2_to_f32(q.x, BF, v[0], v[1]); half2_to_f32(q.y, BF, v[2], v[3]);
-    } else {
-      v[0] = half_bits_to_f32(*h, BF);
-    }
-  }
-}
-template <int XH, int VW>
-__device__ __forceinline__ void rg_store(void* p, size_t e, const float (&v)[VW]) {
-  if constexpr (XH == kXF32) {
-    if constexpr (VW == 4) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p) + e) = make_float4(v[0], v[1], v[2], v[3]);
-    else reinterpret_cast<float*>(p)[e] = v[0];
-  } else {
-    constexpr bool BF = XH == kXBf16;
-    uint16_t* h = reinterpret_cast<uint16_t*>(p) + e;
-    if constexpr (VW == 8) {
-      uint4 q;
-      q.x = pack_half2(v[0], v[1], BF); q.y = pack_half2(v[2], v[3], BF);
-      q.z = pack_half2(v[4], v[5], BF); q.w = pack_half2(v[6], v[7], BF);
-      *reinterpret_cast<uint4*>(h) = q;
-    } else if constexpr (VW == 4) {
-      uint2 q;
-      q.x = pack_half2(v[0], v[1], BF); q.y = pack_half2(v[2], v[3], BF);
-      *reinterpret_cast<uint2*>(h) = q;
-    } else {
-      *h = (uint16_t)f32_to_half_bits(v[0], BF);
-    }
-  }
-}
 
 // the two sums of one element (header: fp64 from the first add)
 __device__ __forceinline__ void rg_sums(float x, double limd, double& r2, double& ro) {
@@ -115,12 +86,9 @@ __device__ __forceinline__ float rg_grad(float x, float g, float l2, float oor2,
   if constexpr (ACCUM) return g + term;
   else return term;
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
-// XH: x's (and the gradient's) element type; VW: elements per load (1: rows whose base is not aligned); MODE: kReg*
+// XH: x's (and the gradient's) element type; VW: elements per load and store (row_access.h: fp32 4 / 1, 2-byte 8 / 4 / 1, the
+// widest that divides D); MODE: kReg*
 template <int XH, int VW, int MODE>
 __global__ __launch_bounds__(kRgNT) void outreg_rows_kernel(const OutRegArgs a, int nchunk, int nitems) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -144,11 +112,11 @@ __global__ __launch_bounds__(kRgNT) void outreg_rows_kernel(const OutRegArgs a, 
 #pragma unroll 2
       for (int e = lane * VW; e < D; e += 64 * VW) {
         float xa[VW], xb[VW], ga[VW], gb[VW];
-        rg_load<XH, VW>(a.x, row0 + e, xa);
-        rg_load<XH, VW>(a.x, row1 + e, xb);
+        row_load<XH, VW>(a.x, row0 + e, xa);
+        row_load<XH, VW>(a.x, row1 + e, xb);
         if constexpr (MODE == kRegAccum) {
-          rg_load<XH, VW>(a.grad, row0 + e, ga);
-          rg_load<XH, VW>(a.grad, row1 + e, gb);
+          row_load<XH, VW>(a.grad, row0 + e, ga);
+          row_load<XH, VW>(a.grad, row1 + e, gb);
         }
 #pragma unroll
         for (int i = 0; i < VW; i++) {
@@ -160,8 +128,8 @@ __global__ __launch_bounds__(kRgNT) void outreg_rows_kernel(const OutRegArgs a, 
           }
         }
         if constexpr (MODE != kRegNoGrad) {
-          rg_store<XH, VW>(a.grad, row0 + e, ga);
-          if (two) rg_store<XH, VW>(a.grad, row1 + e, gb);
+          row_store<XH, VW>(a.grad, row0 + e, ga);
+          if (two) row_store<XH, VW>(a.grad, row1 + e, gb);
         }
       }
       r2a = wave_sum_f64(r2a); roa = wave_sum_f64(roa);
@@ -180,7 +148,7 @@ __global__ __launch_bounds__(kRgNT) void outreg_rows_kernel(const OutRegArgs a, 
         const int t = t0 + r;
         if (t >= L && t < T) {
           const size_t row = (seq + t) * D;
-          for (int e = lane * VW; e < D; e += 64 * VW) rg_store<XH, VW>(a.grad, row + e, z);
+          for (int e = lane * VW; e < D; e += 64 * VW) row_store<XH, VW>(a.grad, row + e, z);
         }
       }
     }
@@ -228,36 +196,71 @@ hipError_t launch_rows_as(const OutRegArgs& a, int grid, int nchunk, int nitems,
   else hipLaunchKernelGGL((outreg_rows_kernel<XH, VW, kRegNoGrad>), dim3(grid), dim3(kRgNT), 0, st, a, nchunk, nitems);
   return hipGetLastError();
 }
-template <int XH>
-hipError_t launch_rows_half(const OutRegArgs& a, int grid, int nchunk, int nitems, hipStream_t st) {
-  if (a.D % 8 == 0) return launch_rows_as<XH, 8>(a, grid, nchunk, nitems, st);
-  if (a.D % 4 == 0) return launch_rows_as<XH, 4>(a, grid, nchunk, nitems, st);
-  return launch_rows_as<XH, 1>(a, grid, nchunk, nitems, st);
-}
-
-}  // namespace
-
-size_t outreg_workspace_bytes(int B, int T) { return 16 * (size_t)B * T + 16 * (size_t)B; }
-
+// the streaming pass over the live rows, then the per-sequence sums of the frame pairs in fp64, fixed order
 hipError_t launch_outreg_rows(const OutRegArgs& a, hipStream_t st) {
   const int nchunk = (a.T + kRgChunk - 1) / kRgChunk;
   const size_t items = (size_t)a.B * nchunk;
   if (items > (size_t)INT_MAX) return hipErrorInvalidValue;
   if ((a.mode == kRegNoGrad) != (a.grad == nullptr)) return hipErrorInvalidValue;
-  const int nitems = (int)items, grid = nitems < kRgMaxGrid ? nitems : kRgMaxGrid;
-  hipError_t e;
-  if (a.x_half == kXF32) e = a.D % 4 == 0 ? launch_rows_as<kXF32, 4>(a, grid, nchunk, nitems, st) : launch_rows_as<kXF32, 1>(a, grid, nchunk, nitems, st);
-  else if (a.x_half == kXBf16) e = launch_rows_half<kXBf16>(a, grid, nchunk, nitems, st);
-  else e = launch_rows_half<kXF16>(a, grid, nchunk, nitems, st);
+  const int nitems = (int)items, grid = nitems < kRowPassMaxGrid ? nitems : kRowPassMaxGrid;
+  const hipError_t e = row_width_dispatch(a.x_half, a.D, [&](auto xh, auto vw) {
+    return launch_rows_as<decltype(xh)::value, decltype(vw)::value>(a, grid, nchunk, nitems, st);
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(outreg_seq_sum_kernel, dim3(a.B), dim3(kRgNT), 0, st, a.frame_pairs, a.lengths, a.T, a.seq_pairs, a.per_seq);
   return hipGetLastError();
 }
 
+// reg_totals[0] = loss_scale * (0.5 l2 S2 + oor SO) [/ *norm_dev], [1] = S2, [2] = SO; totals (or nullptr): [0] and [4] += that
 hipError_t launch_outreg_totals(const double* seq_pairs, int B, float l2, float oor, float loss_scale, const float* norm_dev,
                                 float* reg_totals, float* totals, hipStream_t st) {
   hipLaunchKernelGGL(outreg_totals_kernel, dim3(1), dim3(1), 0, st, seq_pairs, B, l2, oor, loss_scale, norm_dev, reg_totals, totals);
   return hipGetLastError();
 }
 
+size_t outreg_workspace_bytes(int B, int T) { return 16 * (size_t)B * T + 16 * (size_t)B; }
+
+}  // namespace
 }  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+// ---- the entry points (include/pychain_hip.h) -----------------------------------------------------------------------------------
+extern "C" size_t pychain_hip_output_reg_workspace_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  return align256(outreg_workspace_bytes(B, T)) + 256;
+}
+
+extern "C" int pychain_hip_output_reg(
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    float l2, float oor, float limit, int grad_mode, void* grad,
+    float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
+    float* reg_per_seq, float loss_scale, float* reg_totals, float* totals,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "output_reg";
+  if (nnet_output_dtype < PYCHAIN_HIP_F32 || nnet_output_dtype > PYCHAIN_HIP_F16)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, nnet_output_dtype);
+  if (!nnet_output || !seq_lengths || !reg_per_seq || !workspace) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (!(l2 >= 0.f) || !(oor >= 0.f) || !(limit >= 0.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: l2, oor and limit must not be negative (got %g, %g, %g)", who, (double)l2, (double)oor, (double)limit);
+  if (grad_mode != PYCHAIN_HIP_GRAD_ACCUM && grad_mode != PYCHAIN_HIP_GRAD_LINEAR)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: grad_mode must be PYCHAIN_HIP_GRAD_ACCUM or PYCHAIN_HIP_GRAD_LINEAR, got %d", who, grad_mode);
+  if (((uintptr_t)nnet_output | (uintptr_t)grad | (uintptr_t)workspace) & 15)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output, grad and workspace must be 16-byte aligned", who);
+  const size_t need = pychain_hip_output_reg_workspace_bytes(B, T);
+  if (workspace_bytes < need) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, need);
+  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  OutRegArgs a;
+  memset(&a, 0, sizeof(a));
+  a.x = nnet_output; a.x_half = nnet_output_dtype; a.grad = grad;
+  a.mode = !grad ? kRegNoGrad : (grad_mode == PYCHAIN_HIP_GRAD_ACCUM ? kRegAccum : kRegLinear);
+  a.l2 = l2; a.oor = oor; a.limit = limit; a.scale = grad_scale; a.scale_dev = grad_scale_dev; a.norm_dev = loss_norm_dev;
+  a.lengths = seq_lengths; a.frame_pairs = (double*)ws; a.seq_pairs = (double*)(ws + 16 * (size_t)B * T); a.per_seq = reg_per_seq;
+  a.B = B; a.T = T; a.D = D;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = launch_outreg_rows(a, st);
+  if (e == hipSuccess && (reg_totals || totals)) e = launch_outreg_totals(a.seq_pairs, B, l2, oor, loss_scale, loss_norm_dev, reg_totals, totals, st);
+  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}

@@ -34,35 +34,20 @@
 
 #include "../../include/pychain_hip.h"
 #include "common.h"
-#include "device_utils.h"
 #include "post.h"
+#include "row_access.h"
 
 namespace pychain_hip {
 namespace {
 
 constexpr int kPtNT = 256;                          // four waves
-constexpr int kPtMaxGrid = 2048;
 
-template <int XH>
-__device__ __forceinline__ float pt_load(const void* p, size_t e) {
-  if constexpr (XH == kXF32) return reinterpret_cast<const float*>(p)[e];
-  else return half_bits_to_f32(reinterpret_cast<const uint16_t*>(p)[e], XH == kXBf16);
-}
-template <int XH>
-__device__ __forceinline__ void pt_store(void* p, size_t e, float v) {
-  if constexpr (XH == kXF32) reinterpret_cast<float*>(p)[e] = v;
-  else reinterpret_cast<uint16_t*>(p)[e] = (uint16_t)f32_to_half_bits(v, XH == kXBf16);
-}
 __device__ __forceinline__ float pt_add(float a, float b) {
 #pragma clang fp contract(off)
   return a + b;
 }
-__device__ __forceinline__ double wave_sum_f64(double v) {
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
-// XH: x's (and the gradient's) element type; GRAD: a gradient to update
+// XH: x's (and the gradient's) element type (one element at a time: row_load1, row_store1); GRAD: a gradient to update
 template <int XH, bool GRAD>
 __global__ __launch_bounds__(kPtNT) void post_frames_kernel(const PostArgs a, int nframes) {
   const int T = a.T, D = a.D, K = a.K;
@@ -85,7 +70,7 @@ __global__ __launch_bounds__(kPtNT) void post_frames_kernel(const PostArgs a, in
       if (d < 0) continue;                                    // padding
       if (d >= D) { bad++; continue; }
       const float q = pr[k];
-      const double xd = (double)pt_load<XH>(a.x, row + d);
+      const double xd = (double)row_load1<XH>(a.x, row + d);
       const double c = xd < -30.0 ? -30.0 : (xd > 30.0 ? 30.0 : xd);
       acc = fma((double)q, c, acc);
       if constexpr (GRAD) {
@@ -95,7 +80,7 @@ __global__ __launch_bounds__(kPtNT) void post_frames_kernel(const PostArgs a, in
           float qd = q;
           for (int j = k + 1; j < K; j++)
             if (pd[j] == d) qd = pt_add(qd, pr[j]);
-          pt_store<XH>(a.grad, row + d, __builtin_fmaf(s, qd, pt_load<XH>(a.grad, row + d)));
+          row_store1<XH>(a.grad, row + d, __builtin_fmaf(s, qd, row_load1<XH>(a.grad, row + d)));
         }
       }
     }
@@ -152,7 +137,8 @@ __device__ __forceinline__ bool tk_better(float v, int i, float bv, int bi) {
   return i != INT_MAX && (bi == INT_MAX || v > bv || (v == bv && i < bi));
 }
 
-// XH: the rows' element type; VW: elements per load into LDS (1: rows whose base is not aligned); CHIP: the row is held in LDS
+// XH: the rows' element type; VW: elements per load into LDS (1: rows whose base is not aligned, row_load1; 4 fp32 / 8 2-byte:
+// written out here, the row goes to LDS in two float4 halves); CHIP: the row is held in LDS
 template <int XH, int VW, bool CHIP>
 __global__ __launch_bounds__(kPtNT) void topk_rows_kernel(const TopkArgs a, int dpad) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_smem[];
@@ -174,7 +160,7 @@ __global__ __launch_bounds__(kPtNT) void topk_rows_kernel(const TopkArgs a, int 
   if constexpr (CHIP) {
     for (int e = tid * VW; e < D; e += kPtNT * VW) {
       if constexpr (VW == 1) {
-        lrow[e] = pt_load<XH>(a.rows, row + e);
+        lrow[e] = row_load1<XH>(a.rows, row + e);
       } else if constexpr (XH == kXF32) {
         *reinterpret_cast<float4*>(lrow + e) = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(a.rows) + row + e);
       } else {
@@ -197,7 +183,7 @@ __global__ __launch_bounds__(kPtNT) void topk_rows_kernel(const TopkArgs a, int 
     for (int i = tid; i < D; i += kPtNT) {
       float v;
       if constexpr (CHIP) v = lrow[i];
-      else v = pt_load<XH>(a.rows, row + i);
+      else v = row_load1<XH>(a.rows, row + i);
       // behind the previous pick in the order, at or above the floor (a NaN fails both), and above this thread's best so far
       const bool ok = v >= floor && (lasti < 0 || v < lastv || (v == lastv && i > lasti));
       if (ok && (bi == INT_MAX || v > bv)) { bv = v; bi = i; }
@@ -267,7 +253,7 @@ size_t post_workspace_bytes(int B, int T) { return 12 * (size_t)B * T + 12 * (si
 hipError_t launch_post_frames(const PostArgs& a, hipStream_t st) {
   const size_t frames = (size_t)a.B * a.T;
   if (frames > (size_t)INT_MAX) return hipErrorInvalidValue;
-  const int nframes = (int)frames, blocks = (nframes + kPtNT - 1) / kPtNT, grid = blocks < kPtMaxGrid ? blocks : kPtMaxGrid;
+  const int nframes = (int)frames, blocks = (nframes + kPtNT - 1) / kPtNT, grid = blocks < kRowPassMaxGrid ? blocks : kRowPassMaxGrid;
   if (a.x_half == kXF32) launch_frames<kXF32>(a, grid, nframes, st);
   else if (a.x_half == kXBf16) launch_frames<kXBf16>(a, grid, nframes, st);
   else launch_frames<kXF16>(a, grid, nframes, st);
@@ -299,7 +285,7 @@ using namespace pychain_hip;
 // ---- the entry points (include/pychain_hip.h) -----------------------------------------------------------------------------------
 extern "C" size_t pychain_hip_post_targets_workspace_bytes(int B, int T) {
   if (B <= 0 || T <= 0) return 0;
-  return ((post_workspace_bytes(B, T) + 255) & ~(size_t)255) + 256;
+  return align256(post_workspace_bytes(B, T)) + 256;
 }
 
 extern "C" int pychain_hip_post_targets(

@@ -22,67 +22,43 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cstring>
 
-#include "device_utils.h"
-#include "weights.h"
+#include "../../include/pychain_hip.h"
+#include "common.h"
+#include "row_access.h"
 
 namespace pychain_hip {
+
+// (both used by this file alone; outside the unnamed namespace because the kernels' symbols carry their names)
+struct WeightRowsArgs {
+  void* grad;                // [B,T,D], dtype: 0 fp32, kXBf16 / kXF16 (device_utils.h)
+  int dtype;
+  const int64_t* lengths;    // [B]
+  const float* u;            // [B] or nullptr (= 1)
+  const float* f;            // [B,T] or nullptr (= 1)
+  int B, T, D;
+};
+
+struct WeightSumsArgs {
+  const int64_t* lengths;    // [B]
+  const float* u;            // [B] or nullptr (= 1)
+  const float* den;          // [B]
+  const float* num;          // [B]
+  const float* xent;         // [B] or nullptr
+  const float* reg;          // [B][2] = {R2_b, RO_b} or nullptr
+  float xent_coef, l2, oor, loss_scale;
+  const float* norm_dev;     // or nullptr
+  float* totals;             // [PYCHAIN_HIP_TOTALS] or nullptr
+  float* weighted;           // [5] or nullptr
+  int B, T;
+};
+
 namespace {
 
 constexpr int kWtNT = 256;                 // four waves
 constexpr int kWtItem = 32768;             // elements of one work item, about
-constexpr int kWtMaxGrid = 2048;           // 256 CUs x 8 workgroups: the rest is strided over
 constexpr int kWtFlatBelow = 64;           // rows narrower than a wave: the flat form
-
-// VW elements at element offset e: 16 bytes (fp32 x 4, 2-byte x 8), 8 bytes (2-byte x 4) or one element
-template <int XH, int VW>
-__device__ __forceinline__ void wt_load(const void* p, size_t e, float (&v)[VW]) {
-  if constexpr (XH == kXF32) {
-    static_assert(VW == 4 || VW == 1, "fp32 rows: float4 or one element");
-    if constexpr (VW == 4) {
-      const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(p) + e);
-      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-    } else {
-      v[0] = reinterpret_cast<const float*>(p)[e];
-    }
-  } else {
-    static_assert(VW == 8 || VW == 4 || VW == 1, "2-byte rows: eight, four or one element");
-    constexpr bool BF = XH == kXBf16;
-    const uint16_t* h = reinterpret_cast<const uint16_t*>(p) + e;
-    if constexpr (VW == 8) {
-      const uint4 q = *reinterpret_cast<const uint4*>(h);
-      half2_to_f32(q.x, BF, v[0], v[1]); half2_to_f32(q.y, BF, v[2], v[3]);
-      half2_to_f32(q.z, BF, v[4], v[5]); half2_to_f32(q.w, BF, v[6], v[7]);
-    } else if constexpr (VW == 4) {
-      const uint2 q = *reinterpret_cast<const uint2*>(h);
-      half2_to_f32(q.x, BF, v[0], v[1]); half2_to_f32(q.y, BF, v[2], v[3]);
-    } else {
-      v[0] = half_bits_to_f32(*h, BF);
-    }
-  }
-}
-template <int XH, int VW>
-__device__ __forceinline__ void wt_store(void* p, size_t e, const float (&v)[VW]) {
-  if constexpr (XH == kXF32) {
-    if constexpr (VW == 4) *reinterpret_cast<float4*>(reinterpret_cast<float*>(p) + e) = make_float4(v[0], v[1], v[2], v[3]);
-    else reinterpret_cast<float*>(p)[e] = v[0];
-  } else {
-    constexpr bool BF = XH == kXBf16;
-    uint16_t* h = reinterpret_cast<uint16_t*>(p) + e;
-    if constexpr (VW == 8) {
-      uint4 q;
-      q.x = pack_half2(v[0], v[1], BF); q.y = pack_half2(v[2], v[3], BF);
-      q.z = pack_half2(v[4], v[5], BF); q.w = pack_half2(v[6], v[7], BF);
-      *reinterpret_cast<uint4*>(h) = q;
-    } else if constexpr (VW == 4) {
-      uint2 q;
-      q.x = pack_half2(v[0], v[1], BF); q.y = pack_half2(v[2], v[3], BF);
-      *reinterpret_cast<uint2*>(h) = q;
-    } else {
-      *h = (uint16_t)f32_to_half_bits(v[0], BF);
-    }
-  }
-}
 
 // w(b,t) = fl32(u_b * f_bt), a missing factor is 1
 __device__ __forceinline__ float wt_weight(const float* f, float ub, size_t bt) { return f ? ub * f[bt] : ub; }
@@ -95,14 +71,15 @@ __device__ __forceinline__ void wt_apply(void* g, size_t e, float w) {
 #pragma unroll
     for (int i = 0; i < VW; i++) v[i] = 0.f;
   } else {
-    wt_load<XH, VW>(g, e, v);
+    row_load<XH, VW>(g, e, v);
 #pragma unroll
     for (int i = 0; i < VW; i++) v[i] = v[i] * w;
   }
-  wt_store<XH, VW>(g, e, v);
+  row_store<XH, VW>(g, e, v);
 }
 
 // rows form: `chunk` frames per item (a multiple of 4), wave `k` of the item takes its frames k, k + 4, ...
+// (both forms: VW = row_access.h's widths - fp32 4 / 1, 2-byte 8 / 4 / 1, the widest that divides D)
 template <int XH, int VW>
 __global__ __launch_bounds__(kWtNT) void weight_rows_kernel(const WeightRowsArgs a, int chunk, int nchunk, int nitems) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -181,7 +158,7 @@ hipError_t launch_as(const WeightRowsArgs& a, hipStream_t st) {
     const int nchunk = (a.T + chunk - 1) / chunk;
     const size_t items = (size_t)a.B * nchunk;
     if (items > (size_t)INT_MAX) return hipErrorInvalidValue;
-    const int grid = items < (size_t)kWtMaxGrid ? (int)items : kWtMaxGrid;
+    const int grid = items < (size_t)kRowPassMaxGrid ? (int)items : kRowPassMaxGrid;
     hipLaunchKernelGGL((weight_rows_kernel<XH, VW>), dim3(grid), dim3(kWtNT), 0, st, a, chunk, nchunk, (int)items);
   } else {
     const size_t live = (size_t)a.T * a.D;
@@ -189,30 +166,60 @@ hipError_t launch_as(const WeightRowsArgs& a, hipStream_t st) {
     const int nspan = (int)((live + kWtItem - 1) / kWtItem);
     const size_t items = (size_t)a.B * nspan;
     if (items > (size_t)INT_MAX) return hipErrorInvalidValue;
-    const int grid = items < (size_t)kWtMaxGrid ? (int)items : kWtMaxGrid;
+    const int grid = items < (size_t)kRowPassMaxGrid ? (int)items : kRowPassMaxGrid;
     hipLaunchKernelGGL((weight_flat_kernel<XH, VW>), dim3(grid), dim3(kWtNT), 0, st, a, kWtItem, nspan, (int)items);
   }
   return hipGetLastError();
 }
-template <int XH>
-hipError_t launch_half(const WeightRowsArgs& a, hipStream_t st) {
-  if (a.D % 8 == 0) return launch_as<XH, 8>(a, st);
-  if (a.D % 4 == 0) return launch_as<XH, 4>(a, st);
-  return launch_as<XH, 1>(a, st);
-}
-
-}  // namespace
-
+// the streaming pass over the live rows whose weight is neither 1 (not touched) nor 0 (zeros stored, nothing loaded)
 hipError_t launch_weight_rows(const WeightRowsArgs& a, hipStream_t st) {
   if (!a.grad || !a.lengths || (!a.u && !a.f) || a.B <= 0 || a.T <= 0 || a.D <= 0) return hipErrorInvalidValue;
-  if (a.dtype == kXF32) return a.D % 4 == 0 ? launch_as<kXF32, 4>(a, st) : launch_as<kXF32, 1>(a, st);
-  if (a.dtype == kXBf16) return launch_half<kXBf16>(a, st);
-  return launch_half<kXF16>(a, st);
+  return row_width_dispatch(a.dtype, a.D, [&](auto xh, auto vw) { return launch_as<decltype(xh)::value, decltype(vw)::value>(a, st); });
 }
 
+// one thread, fp64, ascending b, in stream order behind whatever wrote `totals` and the per-sequence arrays
 hipError_t launch_weight_sums(const WeightSumsArgs& s, hipStream_t st) {
   hipLaunchKernelGGL(weight_sums_kernel, dim3(1), dim3(1), 0, st, s);
   return hipGetLastError();
 }
 
+}  // namespace
 }  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+// ---- the entry point (include/pychain_hip.h) ------------------------------------------------------------------------------------
+extern "C" int pychain_hip_weight_rows(
+    void* grad, int grad_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const float* utt_weights, const float* deriv_weights,
+    const float* den_objf_per_seq, const float* num_objf_per_seq, const float* xent_objf_per_seq, float xent_coef,
+    const float* reg_per_seq, float l2, float oor, float loss_scale, const float* loss_norm_dev,
+    float* totals, float* weighted, void* stream) {
+  const char* who = "weight_rows";
+  if (!utt_weights && !deriv_weights) return fail(PYCHAIN_HIP_EINVAL, "%s: neither utt_weights nor deriv_weights", who);
+  if (!seq_lengths) return fail(PYCHAIN_HIP_EINVAL, "%s: null seq_lengths", who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (grad && (grad_dtype < PYCHAIN_HIP_F32 || grad_dtype > PYCHAIN_HIP_F16)) return fail(PYCHAIN_HIP_EINVAL, "%s: unknown grad_dtype %d", who, grad_dtype);
+  if ((uintptr_t)grad & 15) return fail(PYCHAIN_HIP_EINVAL, "%s: grad must be 16-byte aligned", who);
+  const bool sums = totals || weighted;
+  if (!grad && !sums) return fail(PYCHAIN_HIP_EINVAL, "%s: nothing to do (no grad, no totals, no weighted)", who);
+  if (sums && (!den_objf_per_seq || !num_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: the sums need den_objf_per_seq and num_objf_per_seq", who);
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipSuccess;
+  if (grad) {
+    WeightRowsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.grad = grad; a.dtype = grad_dtype; a.lengths = seq_lengths; a.u = utt_weights; a.f = deriv_weights; a.B = B; a.T = T; a.D = D;
+    e = launch_weight_rows(a, st);
+  }
+  if (e == hipSuccess && sums) {
+    WeightSumsArgs s;
+    memset(&s, 0, sizeof(s));
+    s.lengths = seq_lengths; s.u = utt_weights; s.den = den_objf_per_seq; s.num = num_objf_per_seq; s.xent = xent_objf_per_seq;
+    s.reg = reg_per_seq; s.xent_coef = xent_coef; s.l2 = l2; s.oor = oor; s.loss_scale = loss_scale; s.norm_dev = loss_norm_dev;
+    s.totals = totals; s.weighted = weighted; s.B = B; s.T = T;
+    e = launch_weight_sums(s, st);
+  }
+  if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "%s: %s", who, hipGetErrorString(e));
+  return PYCHAIN_HIP_OK;
+}

@@ -19,7 +19,7 @@
 
 #include "../../include/pychain_hip.h"
 #include "common.h"
-#include "device_utils.h"
+#include "row_access.h"
 #include "xent.h"
 
 namespace pychain_hip {
@@ -28,38 +28,6 @@ namespace {
 constexpr int kXnNT = 256;
 constexpr size_t kXnMaxLdsRow = 96 * 1024;      // rows beyond: re-read from global memory (dense gamma and sparse entries)
 constexpr int kXnCompact = 0, kXnDense = 1, kXnSparse = 2;      // where the targets of a frame come from
-
-template <int ZH>
-__device__ __forceinline__ void z_load4(const void* z, size_t e, float (&v)[4]) {
-  if constexpr (ZH == kXF32) {
-    const float4 q = *reinterpret_cast<const float4*>(reinterpret_cast<const float*>(z) + e);
-    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
-  } else {
-    const uint2 q = *reinterpret_cast<const uint2*>(reinterpret_cast<const uint16_t*>(z) + e);
-    half2_to_f32(q.x, ZH == kXBf16, v[0], v[1]);
-    half2_to_f32(q.y, ZH == kXBf16, v[2], v[3]);
-  }
-}
-template <int ZH>
-__device__ __forceinline__ float z_load1(const void* z, size_t e) {
-  if constexpr (ZH == kXF32) return reinterpret_cast<const float*>(z)[e];
-  else return half_bits_to_f32(reinterpret_cast<const uint16_t*>(z)[e], ZH == kXBf16);
-}
-template <int ZH>
-__device__ __forceinline__ void z_store4(void* g, size_t e, float v0, float v1, float v2, float v3) {
-  if constexpr (ZH == kXF32) {
-    *reinterpret_cast<float4*>(reinterpret_cast<float*>(g) + e) = make_float4(v0, v1, v2, v3);
-  } else {
-    uint2 q;
-    q.x = pack_half2(v0, v1, ZH == kXBf16); q.y = pack_half2(v2, v3, ZH == kXBf16);
-    *reinterpret_cast<uint2*>(reinterpret_cast<uint16_t*>(g) + e) = q;
-  }
-}
-template <int ZH>
-__device__ __forceinline__ void z_store1(void* g, size_t e, float v) {
-  if constexpr (ZH == kXF32) reinterpret_cast<float*>(g)[e] = v;
-  else reinterpret_cast<uint16_t*>(g)[e] = (uint16_t)f32_to_half_bits(v, ZH == kXBf16);
-}
 
 // reductions over the workgroup in a FIXED order (xor butterfly in the wave - every lane ends with the same bits -, then the
 // four waves' values pairwise): the same call gives the same bits
@@ -103,7 +71,8 @@ __device__ __forceinline__ bool sparse_first(const int32_t* pd, const float* pr,
   return true;
 }
 
-// ZH: z's element type; VEC: rows of a multiple of four elements (vector loads and stores); GRAD: the gradient row is stored;
+// ZH: z's element type; VEC: rows of a multiple of four elements (row_load<ZH, 4>, row_store4_late; else row_load1, row_store1);
+// GRAD: the gradient row is stored;
 // SRC: gamma from the compact occupancy row (kXnCompact), from a dense fp32 row (kXnDense) or from sparse entries (kXnSparse);
 // INLDS: the row fits LDS (else !VEC and not compact: every pass reads z again - rows of more than 24 576 pdfs, which only the
 // general numerator kernels and sparse entries take)
@@ -141,8 +110,11 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
   }
   if (!live) {
     if constexpr (GRAD) {
-      if constexpr (VEC) { for (int e = tid * 4; e < D; e += 4 * kXnNT) z_store4<ZH>(a.grad, row + e, 0.f, 0.f, 0.f, 0.f); }
-      else { for (int e = tid; e < D; e += kXnNT) z_store1<ZH>(a.grad, row + e, 0.f); }
+      if constexpr (VEC) {
+        const float zero[4] = {0.f, 0.f, 0.f, 0.f};
+        for (int e = tid * 4; e < D; e += 4 * kXnNT) row_store4_late<ZH>(a.grad, row + e, zero);
+      }
+      else { for (int e = tid; e < D; e += kXnNT) row_store1<ZH>(a.grad, row + e, 0.f); }
     }
     if (tid == 0) a.frame_objf[fr] = 0.0;
     return;
@@ -152,19 +124,19 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
   if constexpr (VEC) {
     for (int e = tid * 4; e < D; e += 4 * kXnNT) {
       float v[4];
-      z_load4<ZH>(a.z, row + e, v);
+      row_load<ZH, 4>(a.z, row + e, v);
       *reinterpret_cast<float4*>(srow + e) = make_float4(v[0], v[1], v[2], v[3]);
       m = fmaxf(fmaxf(m, fmaxf(v[0], v[1])), fmaxf(v[2], v[3]));
     }
   } else {
     for (int e = tid; e < D; e += kXnNT) {
-      const float v = z_load1<ZH>(a.z, row + e);
+      const float v = row_load1<ZH>(a.z, row + e);
       if constexpr (INLDS) srow[e] = v;
       m = fmaxf(m, v);
     }
   }
   m = block_max(m, red[0]);                          // (its barriers: the LDS row is complete)
-  auto zv = [&](int e) -> float { if constexpr (INLDS) return srow[e]; else return z_load1<ZH>(a.z, row + e); };
+  auto zv = [&](int e) -> float { if constexpr (INLDS) return srow[e]; else return row_load1<ZH>(a.z, row + e); };
   // 2. sum of exp(z - max), s = sum of gamma, sum of gamma z - over this thread's elements, then over the workgroup
   float se = 0.f, s = 0.f, dot = 0.f;
   const int e0 = VEC ? tid * 4 : tid, estep = VEC ? 4 * kXnNT : kXnNT, ew = VEC ? 4 : 1;
@@ -233,8 +205,8 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
       else if constexpr (SCATTER) o[i] = sc * srow[e + i];
       else o[i] = sc * -(s * expf(zv(e + i) - lse));
     }
-    if constexpr (VEC) z_store4<ZH>(a.grad, row + e, o[0], o[1], o[2], o[3]);
-    else z_store1<ZH>(a.grad, row + e, o[0]);
+    if constexpr (VEC) row_store4_late<ZH>(a.grad, row + e, o);
+    else row_store1<ZH>(a.grad, row + e, o[0]);
   }
   if constexpr (SPARSE && !INLDS) {
     // the re-reading form: the addressed elements are patched behind the row store (the barrier orders this workgroup's two
@@ -243,7 +215,7 @@ __global__ __launch_bounds__(kXnNT) void xent_row_kernel(const XentArgs a) {
     for (int u = tid; u < a.K; u += kXnNT) {
       int n;
       float g;
-      if (sparse_first(tpd, tpr, a.K, u, D, n, g)) z_store1<ZH>(a.grad, row + n, sc * (-(s * expf(zv(n) - lse)) + g));
+      if (sparse_first(tpd, tpr, a.K, u, D, n, g)) row_store1<ZH>(a.grad, row + n, sc * (-(s * expf(zv(n) - lse)) + g));
     }
   }
 }
@@ -374,14 +346,10 @@ hipEvent_t xent_join_event(hipStream_t caller) {
 using namespace pychain_hip;
 
 // ---- sparse entries as the targets: the entry points (include/pychain_hip.h: pychain_hip_xent_targets) -----------------------
-namespace {
-inline size_t xt_align(size_t n) { return (n + 255) & ~(size_t)255; }
-}  // namespace
-
 extern "C" size_t pychain_hip_xent_targets_workspace_bytes(int B, int T) {
   if (B <= 0 || T <= 0) return 0;
   // frame objectives (fp64), the frames' bad entries, the sequences' - and the slack of the alignment to 256 bytes
-  return xt_align(xent_frame_bytes(B, T)) + xt_align(4 * (size_t)B * T) + xt_align(4 * (size_t)B) + 256;
+  return align256(xent_frame_bytes(B, T)) + align256(4 * (size_t)B * T) + align256(4 * (size_t)B) + 256;
 }
 
 extern "C" int pychain_hip_xent_targets(
@@ -405,8 +373,8 @@ extern "C" int pychain_hip_xent_targets(
   a.z = z; a.z_half = z_dtype; a.grad = xent_grad; a.scale = grad_scale; a.scale_dev = grad_scale_dev; a.norm_dev = loss_norm_dev;
   a.lengths = seq_lengths; a.tpdfs = target_pdfs; a.tprobs = target_probs; a.K = K;
   a.frame_objf = (double*)ws;
-  a.frame_bad = (int32_t*)(ws + xt_align(xent_frame_bytes(B, T)));
-  a.seq_bad = (int32_t*)(ws + xt_align(xent_frame_bytes(B, T)) + xt_align(4 * (size_t)B * T));
+  a.frame_bad = (int32_t*)(ws + align256(xent_frame_bytes(B, T)));
+  a.seq_bad = (int32_t*)(ws + align256(xent_frame_bytes(B, T)) + align256(4 * (size_t)B * T));
   a.objf = xent_objf_per_seq; a.B = B; a.T = T; a.D = D;
   const char* why = "";
   hipStream_t st = (hipStream_t)stream;
