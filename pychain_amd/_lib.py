@@ -29,6 +29,24 @@ class Xent(ctypes.Structure):
 
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 
+# the argument groups the numerator, alignment and fused-loss entry points are made of (include/pychain_hip.h)
+_GRAPHS = [_vp] * 8 + [_i]                       # ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride
+_ROWS = [_vp, _i, _vp]                           # nnet_output, nnet_output_dtype, seq_lengths
+_CPU_ROWS = [_vp, _vp]                           # (the host twins: fp32 rows)
+_SIZES = [_i] * 5                                # B, T, D, H, K
+_WS = [_vp, _sz]                                 # a workspace and its bytes
+_DEN_PLAN = [_vp, _i64, _i, _i]                  # plans_dev, plan_stride_bytes, hint, den_H
+_NUM_OUT = [_i, _f, _vp, _vp, _vp]               # grad_mode, grad_scale, objf_per_seq, grad, bad_count
+_ALIGN_OUT = [_vp] * 4                           # score_per_seq, states, pdfs, bad_count
+_NUM = _GRAPHS + _ROWS + _SIZES + _NUM_OUT + _WS + [_vp]                     # ..., stream
+_ALIGN = _GRAPHS + _ROWS + _SIZES + _ALIGN_OUT + _WS + [_vp]
+_CPU_NUM = _GRAPHS + _CPU_ROWS + _SIZES + _NUM_OUT + [_i]                    # ..., num_threads
+_CPU_ALIGN = _GRAPHS + _CPU_ROWS + _SIZES + _ALIGN_OUT + [_i]
+_FUSED_HEAD = _DEN_PLAN + [_f] + _GRAPHS + [_i, _i] + _ROWS + [_i] * 3       # plan, leaky, graphs, num_H, num_K, rows, B, T, D
+_FUSED_TAIL = [_f, _vp, _vp] + _WS + _WS + [_vp]                             # loss_scale, loss_norm_dev, totals, den_ws, num_ws, stream
+_FORWARD = _FUSED_HEAD + [_vp, _vp, _vp, _f, _vp] + _FUSED_TAIL              # den_objf, num_objf, grad, grad_scale, bad_count
+_FORWARD_BACKWARD = _FUSED_HEAD + [_f] + [_vp] * 4 + _FUSED_TAIL             # grad_scale, den_objf, num_objf, grad, bad_count
+
 _SIGNATURES = {
     "pychain_hip_abi_version": (_i, []),
     "pychain_hip_last_error": (ctypes.c_char_p, []),
@@ -56,35 +74,20 @@ _SIGNATURES = {
     "pychain_hip_chain_loss_half_native": (_i, [_i64, _i, _i, _i, _i, _i, _i, _i]),
     "pychain_hip_chain_loss_slices": (_i, [_i64, _i, _i]),
     "pychain_hip_num_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "pychain_hip_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f,
-                                              _vp, _vp, _vp, _vp, _sz, _vp]),
-    "pychain_hip_chain_loss_forward_backward": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                                + [_vp, _i, _vp, _i, _i, _i, _f] + [_vp] * 4 + [_f, _vp, _vp]
-                                                + [_vp, _sz, _vp, _sz, _vp]),
-    "pychain_hip_chain_loss_forward": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                       + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
-                                       + [_vp, _sz, _vp, _sz, _vp]),
+    "pychain_hip_num_forward_backward": (_i, _NUM),
+    "pychain_hip_chain_loss_forward_backward": (_i, _FORWARD_BACKWARD),
+    "pychain_hip_chain_loss_forward": (_i, _FORWARD),
     # (ABI 19: the same four with alignment time windows, one pointer more, last - include/pychain_hip.h)
-    "pychain_hip_num_forward_backward_tw": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f,
-                                                 _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pychain_hip_chain_loss_forward_backward_tw": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                                   + [_vp, _i, _vp, _i, _i, _i, _f] + [_vp] * 4 + [_f, _vp, _vp]
-                                                   + [_vp, _sz, _vp, _sz, _vp, _vp]),
-    "pychain_hip_chain_loss_forward_tw": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                          + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
-                                          + [_vp, _sz, _vp, _sz, _vp, _vp]),
-    "pychain_hip_cpu_num_forward_backward_tw": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp]),
+    "pychain_hip_num_forward_backward_tw": (_i, _NUM + [_vp]),
+    "pychain_hip_chain_loss_forward_backward_tw": (_i, _FORWARD_BACKWARD + [_vp]),
+    "pychain_hip_chain_loss_forward_tw": (_i, _FORWARD + [_vp]),
+    "pychain_hip_cpu_num_forward_backward_tw": (_i, _CPU_NUM + [_vp]),
     # (ABI 20: the same four with the numerator posteriors as cross-entropy targets, a pointer to a pychain_hip_xent more, last)
     "pychain_hip_xent_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "pychain_hip_num_forward_backward_xent": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _f,
-                                                   _vp, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
-    "pychain_hip_chain_loss_forward_backward_xent": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                                     + [_vp, _i, _vp, _i, _i, _i, _f] + [_vp] * 4 + [_f, _vp, _vp]
-                                                     + [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
-    "pychain_hip_chain_loss_forward_xent": (_i, [_vp, _i64, _i, _i, _f] + [_vp] * 8 + [_i, _i, _i]
-                                            + [_vp, _i, _vp, _i, _i, _i] + [_vp, _vp, _vp, _f, _vp] + [_f, _vp, _vp]
-                                            + [_vp, _sz, _vp, _sz, _vp, _vp, _vp]),
-    "pychain_hip_cpu_num_forward_backward_xent": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i, _vp, _vp]),
+    "pychain_hip_num_forward_backward_xent": (_i, _NUM + [_vp, _vp]),
+    "pychain_hip_chain_loss_forward_backward_xent": (_i, _FORWARD_BACKWARD + [_vp, _vp]),
+    "pychain_hip_chain_loss_forward_xent": (_i, _FORWARD + [_vp, _vp]),
+    "pychain_hip_cpu_num_forward_backward_xent": (_i, _CPU_NUM + [_vp, _vp]),
     # (ABI 21: output L2 and the out-of-range penalty over the network output itself)
     "pychain_hip_output_reg_workspace_bytes": (_sz, [_i, _i]),
     "pychain_hip_output_reg": (_i, [_vp, _i, _vp, _i, _i, _i, _f, _f, _f, _i, _vp, _f, _vp, _vp, _vp, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -108,20 +111,20 @@ _SIGNATURES = {
     "pychain_hip_cpu_boost_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
-    "pychain_hip_cpu_num_forward_backward": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _i]),
+    "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),
     "pychain_hip_align_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "pychain_hip_align": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "pychain_hip_align": (_i, _ALIGN),
     "pychain_hip_align_half_native": (_i, [_i, _i, _i]),
-    "pychain_hip_cpu_align": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i]),
+    "pychain_hip_cpu_align": (_i, _CPU_ALIGN),
     # (ABI 26: the same two under alignment time windows, one pointer more, last)
-    "pychain_hip_align_tw": (_i, [_vp] * 8 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "pychain_hip_cpu_align_tw": (_i, [_vp] * 8 + [_i, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp]),
+    "pychain_hip_align_tw": (_i, _ALIGN + [_vp]),
+    "pychain_hip_cpu_align_tw": (_i, _CPU_ALIGN + [_vp]),
     "pychain_hip_den_tseg_state": (_i, [_vp, _vp]),
     "pychain_hip_den_tseg_state_bytes": (_sz, []),
     "pychain_hip_rescale": (_i, [_vp, _i, _sz, _vp, _vp]),
     "pychain_hip_loss_total": (_i, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
-    "pychain_hip_chain_loss_backward": (_i, [_vp, _i64, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _i,
-                                             _f, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "pychain_hip_chain_loss_backward": (_i, _DEN_PLAN + [_vp, _vp, _vp, _i, _i, _i] + _ROWS + [_i] * 3      # ft, fi, fp, stride, num_H, num_K
+                                        + [_f, _vp, _vp, _vp] + _WS + _WS + [_vp]),     # grad_scale, grad_scale_dev, grad, bad_count
     "pychain_hip_batch_layout": (_i64, [_i, _i, _i, _i, _vp, _vp]),
     "pychain_hip_batch_pack": (_i, [_i, _i, _i, _i, _vp, _vp, _sz]),
     "pychain_hip_batch_reorder": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp]),

@@ -21,14 +21,38 @@
 // instantiations without it keep their instructions.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/pychain_hip.h"
-#include "align.h"
+#include "call_args.h"
 #include "common.h"
 #include "device_utils.h"
 #include "num_kernels.h"
 
 namespace pychain_hip {
+
+// (outside the unnamed namespace: the kernel symbols carry its name)
+struct AlignArgs {
+  const int32_t* bwd_trans; const int32_t* bwd_idx; const float* bwd_probs;   // arcs entering each state, [G,K,3] / [G,H,2] / [G,K]
+  const float* initial; const float* final_;                                  // [G,H] log
+  const float* x;            // [B,T,D] raw   (x_half: 2-byte elements behind this pointer)
+  int x_half;                // 0 fp32; kXBf16 / kXF16 (device_utils.h): tile kernels only
+  const int64_t* lengths;    // [B]
+  double* score;             // [B]    best-path log-score, final weight included; NaN / -inf = not ok
+  int32_t* states;           // [B,T+1]
+  int64_t* pdfs;             // [B,T]
+  int32_t* bad;              // [1]    utterances not ok (+ lengths outside [1, T])
+  uint16_t* bp16;            // tile:    [B,T,Hb] offset of the winning arc inside [lo, hi) of its destination
+  int32_t* bp32;             // general: [B,T,H]
+  double* gen_sc;            // general: [B,2,H] ping-pong score vectors
+  int graph_stride;          // 1 = per-sequence graphs, 0 = shared
+  int B, T, D, H, K;
+  int Hb;                    // row stride of bp16 (H rounded up to even: rows are read back as 32-bit words)
+  int walk_bytes;            // tile: LDS bytes of the region the backtrace stages rows in (>= the score + row buffers it reuses)
+  int general;               // graphs beyond the tile kernels (num_needs_general)
+  const int32_t* windows;    // [B,H,2] {lo, hi} alignment time windows (pychain_hip_align_tw), nullptr = none
+};
+
 namespace {
 
 constexpr int kAlNT = 512;                 // threads that own states (one state per thread up to 512 states)
@@ -442,8 +466,6 @@ hipError_t launch_align_t(const AlignArgs& a, size_t lds, hipStream_t st) {
 
 size_t align_fixed_lds_bytes(int K) { return 8 * 16 + 4 * 16 + 8 * (size_t)K + 64; }     // (with the forward's region: num_fb_lds_bytes)
 
-}  // namespace
-
 // the region the forward's score vectors and rows live in, enlarged (up to kAlWalkCap, within the 160 KiB) for the backtrace
 int align_walk_bytes(int H, int K, int D) {
   const size_t Dp = (D + 3) & ~3, Hq = (H + 1) & ~1;
@@ -487,4 +509,82 @@ hipError_t launch_align(const AlignArgs& a, hipStream_t st, const char** why) {
   return launch_align_t<1, 0>(a, lds, st);
 }
 
+// ---- the entry points (include/pychain_hip.h: pychain_hip_align*) ------------------------------------------------------------
+
+struct AlignCarve { size_t bp, sc, total; };
+AlignCarve align_carve(int B, int T, int H, int K, int D) {
+  AlignCarve c;
+  c.bp = 0;
+  if (num_needs_general(H, K, D)) {                  // int32 backpointers + the two score vectors per sequence
+    c.sc = align256(4 * (size_t)B * T * H);
+    c.total = c.sc + align256(16 * (size_t)B * H) + 256;
+  } else {                                          // uint16 backpointers, rows of H rounded up to even
+    c.sc = align256(2 * (size_t)B * T * (size_t)((H + 1) & ~1));
+    c.total = c.sc + 256;
+  }
+  return c;
+}
+bool align_half_native(int H, int K, int D) { return !num_needs_general(H, K, D) && D % 4 == 0 && D <= 4 * 8 * 512; }
+}  // namespace
 }  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+extern "C" size_t pychain_hip_align_workspace_bytes(int B, int T, int H, int K, int D) {
+  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
+  return align_carve(B, T, H, K, D).total;
+}
+extern "C" int pychain_hip_align_half_native(int H, int K, int D) {
+  if (H <= 0 || K <= 0 || D <= 0) return 0;
+  return align_half_native(H, K, D) ? 1 : 0;
+}
+
+extern "C" int pychain_hip_align_tw(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K, double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
+  const char* who = "align";
+  (void)ft; (void)fi; (void)fp;                      // (the recursion gathers over the arcs entering each state only)
+  if (int rc = bad_dtype(who, nnet_output_dtype)) return rc;
+  if (!bt || !bi || !bp || !initial || !final_ || !nnet_output || !seq_lengths || !score_per_seq || !states || !pdfs ||
+      !bad_count || !workspace)
+    return null_pointer(who);
+  if (int rc = bad_sizes(who, B, T, H, K, D)) return rc;
+  if (int rc = bad_stride(who, graph_batch_stride)) return rc;
+  if (((uintptr_t)nnet_output | (uintptr_t)bi) & 15)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output and index tensors must be 16-byte aligned", who);
+  const AlignCarve c = align_carve(B, T, H, K, D);
+  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
+  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !align_half_native(H, K, D))
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_align_half_native)", who);
+  AlignArgs a;
+  memset(&a, 0, sizeof(a));
+  a.bwd_trans = bt; a.bwd_idx = bi; a.bwd_probs = bp; a.initial = initial; a.final_ = final_;
+  a.x = (const float*)nnet_output; a.x_half = nnet_output_dtype; a.lengths = seq_lengths;
+  a.score = score_per_seq; a.states = states; a.pdfs = pdfs; a.bad = bad_count;
+  a.graph_stride = graph_batch_stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
+  a.Hb = (H + 1) & ~1;
+  a.general = num_needs_general(H, K, D) ? 1 : 0;
+  a.windows = time_windows;                          // (nullptr: the kernels without the mask, exactly the call before ABI 26)
+  char* ws = ws_base(workspace);
+  if (a.general) { a.bp32 = (int32_t*)(ws + c.bp); a.gen_sc = (double*)(ws + c.sc); }
+  else { a.bp16 = (uint16_t*)(ws + c.bp); a.walk_bytes = align_walk_bytes(H, K, D); }
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(bad_count, 0, sizeof(int32_t), st) != hipSuccess)
+    return fail(PYCHAIN_HIP_ELAUNCH, "%s: hipMemsetAsync failed", who);
+  const char* why = nullptr;
+  const hipError_t e = launch_align(a, st, &why);
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed(who, e, why);
+}
+
+extern "C" int pychain_hip_align(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K, double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  return pychain_hip_align_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
+                              B, T, D, H, K, score_per_seq, states, pdfs, bad_count, workspace, workspace_bytes, stream, nullptr);
+}

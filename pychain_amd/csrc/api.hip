@@ -11,7 +11,7 @@
 #include <string>
 
 #include "../../include/pychain_hip.h"
-#include "align.h"
+#include "call_args.h"
 #include "common.h"
 #include "den_kernels.h"
 #include "den_policy.h"
@@ -242,39 +242,37 @@ extern "C" size_t pychain_hip_den_workspace_bytes(int B, int T, int H, int D) {
 
 namespace {
 int32_t* tstate_of(const void* plans_dev);
-int fill_den_args(DenArgs& a, const void* plans_dev, int64_t plan_stride_bytes, int hint, int H, int D,
-                  const void* nnet_output, int x_dtype, int input_is_exp, const int64_t* seq_lengths,
-                  int B, int T, float leaky_hmm_coefficient, float grad_scale,
-                  float* objf_per_seq, void* grad, int32_t* bad_count,
-                  void* workspace, size_t workspace_bytes, const char* who) {
-  if (x_dtype < PYCHAIN_HIP_F32 || x_dtype > PYCHAIN_HIP_F16)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, x_dtype);
-  if (!plans_dev || !nnet_output || !seq_lengths || !objf_per_seq || !grad || !bad_count || !workspace)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+// the denominator plan(s) of a call: the device blob, the bytes from one sequence's plan to the next (0: one for all), the launch
+// hint and the positions pychain_hip_den_plan_info reports
+struct DenPlan { const void* blob; int64_t stride_bytes; int hint, H; };
+int fill_den_args(DenArgs& a, const DenPlan& plan, const Rows& rows, int input_is_exp, float leaky_hmm_coefficient, float grad_scale,
+                  float* objf_per_seq, void* grad, int32_t* bad_count, const Workspace& wsp, const char* who) {
+  const int H = plan.H, B = rows.B, T = rows.T, D = rows.D;
+  if (int rc = bad_dtype(who, rows.dtype)) return rc;
+  if (!plan.blob || !rows.x || !rows.lengths || !objf_per_seq || !grad || !bad_count || !wsp.p) return null_pointer(who);
   if (B <= 0 || T <= 0 || H <= 0 || D <= 0)
     return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d D=%d", who, B, T, H, D);
-  if ((H > 65535 || D > 65535) && hint != PYCHAIN_HIP_HINT_GENERAL)
+  if ((H > 65535 || D > 65535) && plan.hint != PYCHAIN_HIP_HINT_GENERAL)
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: more than 65535 states or pdfs need a plan in the general format (build it with "
                 "pychain_hip_den_plan_build and pass the launch hint pychain_hip_den_plan_info reports)", who);
   // chain-computation.cc:68 asserts 0 < coefficient < 1 (compiled out under NDEBUG); here it is an error
   if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
-    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who,
-                (double)leaky_hmm_coefficient);
-  if (plan_stride_bytes < 0 || (plan_stride_bytes & 15))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  if (plan.stride_bytes < 0 || (plan.stride_bytes & 15))
     return fail(PYCHAIN_HIP_EINVAL, "%s: plan stride must be a non-negative multiple of 16", who);
-  if (((uintptr_t)plans_dev | (uintptr_t)nnet_output | (uintptr_t)grad | (uintptr_t)workspace) & 15)
+  if (((uintptr_t)plan.blob | (uintptr_t)rows.x | (uintptr_t)grad | (uintptr_t)wsp.p) & 15)
     return fail(PYCHAIN_HIP_EINVAL, "%s: plan, nnet_output, grad and workspace must be 16-byte aligned", who);
   const DenCarve c = den_carve(B, T, H, D);
-  if (workspace_bytes < c.min_total)
-    return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, workspace_bytes, c.min_total);
-  den_shape_args(a, plan_stride_bytes, H, D, B, T);      // (zeroes `a`: what is not set below is 0 / null)
-  a.plans = (const char*)plans_dev;
-  a.x = (const float*)nnet_output; a.x_half = x_dtype; a.lengths = seq_lengths; a.objf = objf_per_seq; a.grad = (float*)grad; a.bad = bad_count;
+  if (wsp.bytes < c.min_total)
+    return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small (%zu < %zu)", who, wsp.bytes, c.min_total);
+  den_shape_args(a, plan.stride_bytes, H, D, B, T);      // (zeroes `a`: what is not set below is 0 / null)
+  a.plans = (const char*)plan.blob;
+  a.x = (const float*)rows.x; a.x_half = rows.dtype; a.lengths = rows.lengths; a.objf = objf_per_seq; a.grad = (float*)grad; a.bad = bad_count;
   a.input_is_exp = input_is_exp ? 1 : 0;
   a.phase_mask = a.knobs.den_phase_mask;
   a.coef = leaky_hmm_coefficient; a.grad_scale = grad_scale;
   a.loss_scale = 1.f; a.bad_words = 1;
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* ws = ws_base(wsp.p);
   a.alpha_store = (float*)(ws + c.alpha); a.beta_store = (float*)(ws + c.beta);
   a.seq_progress = (int32_t*)(ws + c.seq_progress);
   a.progress = (int32_t*)(ws + c.progress);
@@ -284,9 +282,9 @@ int fill_den_args(DenArgs& a, const void* plans_dev, int64_t plan_stride_bytes, 
   a.tot_a = (float*)(ws + c.tot_a); a.tot_b = (float*)(ws + c.tot_b); a.gtot = (float*)(ws + c.gtot); a.fin_dot = (float*)(ws + c.fin_dot);
   a.splice = (float*)(ws + c.splice);
   // (behind everything else, and only in a workspace of the full size: DenArgs::ex)
-  a.ex = workspace_bytes >= c.total ? (float*)(ws + c.ex) : nullptr;
+  a.ex = wsp.bytes >= c.total ? (float*)(ws + c.ex) : nullptr;
   // (the plan's burn-in controller, unless the caller pins the cut or the burn-in with an option of its own)
-  a.tstate = (option_set("den_tseg") || option_set("den_tburn")) ? nullptr : tstate_of(plans_dev);
+  a.tstate = (option_set("den_tseg") || option_set("den_tburn")) ? nullptr : tstate_of(plan.blob);
   return PYCHAIN_HIP_OK;
 }
 }  // namespace
@@ -422,10 +420,9 @@ extern "C" int pychain_hip_den_forward_backward(
     float* objf_per_seq, void* grad, int32_t* bad_count, float* totals,
     void* workspace, size_t workspace_bytes, void* stream) {
   DenArgs a;
-  int rc = fill_den_args(a, plans_dev, plan_stride_bytes, hint, H, D, nnet_output, nnet_output_dtype, input_is_exp, seq_lengths, B, T,
-                         leaky_hmm_coefficient, grad_scale, objf_per_seq, grad, bad_count, workspace,
-                         workspace_bytes, "den_forward_backward");
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_den_args(a, DenPlan{plans_dev, plan_stride_bytes, hint, H}, Rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D},
+                             input_is_exp, leaky_hmm_coefficient, grad_scale, objf_per_seq, grad, bad_count,
+                             Workspace{workspace, workspace_bytes}, "den_forward_backward")) return rc;
   a.loss_out = totals;                                 // (sum of the per-sequence objectives, frames, bad count: den_finish_kernel)
   if (a.x_half && !den_call_half_native(a, hint))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "den_forward_backward: this shape does not take 2-byte network outputs (pychain_hip_den_half_native)");
@@ -434,10 +431,7 @@ extern "C" int pychain_hip_den_forward_backward(
     return fail(PYCHAIN_HIP_ELAUNCH, "den_forward_backward: cannot zero the counters");
   const char* why = nullptr;
   hipError_t e = run_den(a, hint, true, st, &why);
-  if (e != hipSuccess)
-    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "den_forward_backward: %s",
-                why ? why : hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed("den_forward_backward", e, why);
 }
 
 namespace {
@@ -458,43 +452,34 @@ NumCarve num_carve(int B, int T, int H, int K, int D, bool compat) {
   return c;
 }
 
-int fill_num_args(NumArgs& a, const int32_t* ft, const int32_t* fi, const float* fp,
-                  const int32_t* bt, const int32_t* bi, const float* bp,
-                  const float* initial, const float* final_, int graph_batch_stride,
-                  const void* nnet_output, int x_dtype, const int64_t* seq_lengths,
-                  int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
-                  float* objf_per_seq, void* grad, int32_t* bad_count,
-                  void* workspace, size_t workspace_bytes, const char* who, const int32_t* windows) {
-  if (x_dtype < PYCHAIN_HIP_F32 || x_dtype > PYCHAIN_HIP_F16)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, x_dtype);
-  if (!ft || !fi || !fp || !bt || !bi || !bp || !initial || !final_ || !nnet_output || !seq_lengths ||
-      !objf_per_seq || !grad || !bad_count || !workspace)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
-  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || K <= 0)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
-  if (graph_batch_stride != 0 && graph_batch_stride != 1)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+int fill_num_args(NumArgs& a, const NumGraphs& g, const Rows& rows, int grad_mode, float grad_scale,
+                  float* objf_per_seq, void* grad, int32_t* bad_count, const Workspace& wsp, const char* who, const int32_t* windows) {
+  const int B = rows.B, T = rows.T, D = rows.D, H = g.H, K = g.K;
+  if (int rc = bad_dtype(who, rows.dtype)) return rc;
+  if (g.any_null() || !rows.x || !rows.lengths || !objf_per_seq || !grad || !bad_count || !wsp.p) return null_pointer(who);
+  if (int rc = bad_sizes(who, rows, g)) return rc;
+  if (int rc = bad_stride(who, g.stride)) return rc;
   if (grad_mode < PYCHAIN_HIP_GRAD_LOG || grad_mode > PYCHAIN_HIP_GRAD_ACCUM)
     return fail(PYCHAIN_HIP_EINVAL, "%s: unknown grad_mode %d", who, grad_mode);
-  if (((uintptr_t)nnet_output | (uintptr_t)grad | (uintptr_t)fi | (uintptr_t)bi) & 15)
+  if (((uintptr_t)rows.x | (uintptr_t)grad | (uintptr_t)g.fi | (uintptr_t)g.bi) & 15)
     return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output, grad and index tensors must be 16-byte aligned", who);
   const CallKnobs knobs = call_knobs();
   const NumCarve c = num_carve(B, T, H, K, D, knobs.num_compat != 0);
-  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
+  if (wsp.bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
   if (windows && knobs.num_compat)
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: option num_compat (the reference's own arithmetic) takes no alignment time windows", who);
   memset(&a, 0, sizeof(a));
-  a.fwd_trans = ft; a.fwd_idx = fi; a.fwd_probs = fp; a.bwd_trans = bt; a.bwd_idx = bi; a.bwd_probs = bp;
-  a.initial = initial; a.final_ = final_; a.x = (const float*)nnet_output; a.x_half = x_dtype; a.lengths = seq_lengths;
+  a.fwd_trans = g.ft; a.fwd_idx = g.fi; a.fwd_probs = g.fp; a.bwd_trans = g.bt; a.bwd_idx = g.bi; a.bwd_probs = g.bp;
+  a.initial = g.initial; a.final_ = g.final_; a.x = (const float*)rows.x; a.x_half = rows.dtype; a.lengths = rows.lengths;
   a.objf = objf_per_seq; a.grad = (float*)grad; a.bad = bad_count;
-  a.graph_stride = graph_batch_stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
+  a.graph_stride = g.stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
   a.grad_mode = grad_mode; a.grad_scale = grad_scale; a.frames_per_block = 32;
   a.check_all = knobs.verbose >= 1 ? 1 : 0;
   if (knobs.corrupt_what == 2 && knobs.corrupt_b < B && knobs.corrupt_t < T) {
     a.corrupt_b = knobs.corrupt_b; a.corrupt_t = knobs.corrupt_t; a.corrupt_log = logf(knobs.corrupt_scale);
   } else a.corrupt_b = -1;
   a.watch_nan = 1;                                   // (the fused loss clears it: NumArgs::watch_nan)
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+  char* ws = ws_base(wsp.p);
   a.alpha_ws = (double*)(ws + c.alpha); a.beta_ws = (double*)(ws + c.beta); a.logp_ws = (double*)(ws + c.logp);
   a.rows_ws = (float*)(ws + c.rows); a.upd_ws = (int32_t*)(ws + c.upd); a.ucount_ws = (int32_t*)(ws + c.ucount);
   a.uidx_ws = (int32_t*)(ws + c.uidx); a.frac_ws = (float*)(ws + c.frac);
@@ -526,7 +511,7 @@ XentCarve xent_carve(int B, int T, int H, int K, int D) {
   return c;
 }
 int xent_check(const pychain_hip_xent* x, int B, int T, int H, int K, int D, const char* who, XentCall& out) {
-  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
+  if (int rc = bad_sizes(who, B, T, H, K, D)) return rc;
   if (!x->z || !x->xent_objf_per_seq || !x->workspace) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: null z, xent_objf_per_seq or workspace", who);
   if (x->z_dtype < PYCHAIN_HIP_F32 || x->z_dtype > PYCHAIN_HIP_F16) return fail(PYCHAIN_HIP_EINVAL, "%s: xent: unknown z_dtype %d", who, x->z_dtype);
   if (((uintptr_t)x->z | (uintptr_t)x->xent_grad | (uintptr_t)x->workspace) & 15)
@@ -535,7 +520,7 @@ int xent_check(const pychain_hip_xent* x, int B, int T, int H, int K, int D, con
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: option num_compat (the reference's own arithmetic) takes no cross-entropy output", who);
   const XentCarve c = xent_carve(B, T, H, K, D);
   if (x->workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: xent workspace too small (%zu < %zu)", who, x->workspace_bytes, c.total);
-  char* ws = (char*)(((uintptr_t)x->workspace + 255) & ~(uintptr_t)255);
+  char* ws = ws_base(x->workspace);
   out.z = (const char*)x->z; out.z_dtype = x->z_dtype; out.grad = (char*)x->xent_grad;
   out.grad_scale = x->grad_scale; out.grad_scale_dev = x->grad_scale_dev; out.objf = x->xent_objf_per_seq;
   out.scratch_bad = (int32_t*)(ws + c.scratch);
@@ -546,7 +531,7 @@ int xent_check(const pychain_hip_xent* x, int B, int T, int H, int K, int D, con
 // the same call over the sequences from b0 on (a slice: the workspace is reused, slice after slice in stream order)
 XentCall xent_slice(const XentCall& x, int b0, int T, int D) {
   XentCall s = x;
-  const size_t esz = x.z_dtype == PYCHAIN_HIP_F32 ? 4 : 2, off = (size_t)b0 * T * D * esz;
+  const size_t off = Rows{x.z, x.z_dtype, nullptr, 0, T, D}.offset(b0);
   s.z = x.z + off;
   if (x.grad) s.grad = x.grad + off;
   s.objf = x.objf + b0;
@@ -584,24 +569,19 @@ extern "C" size_t pychain_hip_num_workspace_bytes(int B, int T, int H, int K, in
 }
 
 extern "C" int pychain_hip_num_forward_backward_xent(
-    const int32_t* ft, const int32_t* fi, const float* fp,
-    const int32_t* bt, const int32_t* bi, const float* bp,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
-    int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
-    float* objf_per_seq, float* grad, int32_t* bad_count,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale, float* objf_per_seq, float* grad, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows, const pychain_hip_xent* xent) {
   NumArgs a;
   XentCall xc;
-  if (xent) {
-    const int xrc = xent_check(xent, B, T, H, K, D, "num_forward_backward", xc);
-    if (xrc != PYCHAIN_HIP_OK) return xrc;
-  }
+  if (xent) { if (int rc = xent_check(xent, B, T, H, K, D, "num_forward_backward", xc)) return rc; }
   const bool dense_grad = grad != nullptr || !xent;      // (with xent `grad` may be NULL: only the cross-entropy is wanted)
-  int rc = fill_num_args(a, ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
-                         B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, dense_grad ? (void*)grad : workspace, bad_count, workspace,
-                         workspace_bytes, "num_forward_backward", time_windows);
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_num_args(a, NumGraphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K},
+                             Rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D}, grad_mode, grad_scale, objf_per_seq,
+                             dense_grad ? (void*)grad : workspace, bad_count, Workspace{workspace, workspace_bytes}, "num_forward_backward",
+                             time_windows)) return rc;
   // (2-byte network outputs are READ as they are by the tile recursions; the gradient of this entry point stays fp32)
   if (a.x_half && !num_half_native(a))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "num_forward_backward: this shape does not take 2-byte network outputs (pychain_hip_num_half_native)");
@@ -629,19 +609,14 @@ extern "C" int pychain_hip_num_forward_backward_xent(
       if (e == hipSuccess && xent->xent_totals) e = launch_xent_totals(xc.objf, B, 1.f, nullptr, 0.f, xent->xent_totals, nullptr, st);
     }
   }
-  if (e != hipSuccess)
-    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "num_forward_backward: %s",
-                why ? why : hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed("num_forward_backward", e, why);
 }
 
 extern "C" int pychain_hip_num_forward_backward_tw(
-    const int32_t* ft, const int32_t* fi, const float* fp,
-    const int32_t* bt, const int32_t* bi, const float* bp,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
-    int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
-    float* objf_per_seq, float* grad, int32_t* bad_count,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale, float* objf_per_seq, float* grad, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
   return pychain_hip_num_forward_backward_xent(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype,
                                                seq_lengths, B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count,
@@ -649,136 +624,46 @@ extern "C" int pychain_hip_num_forward_backward_tw(
 }
 
 extern "C" int pychain_hip_num_forward_backward(
-    const int32_t* ft, const int32_t* fi, const float* fp,
-    const int32_t* bt, const int32_t* bi, const float* bp,
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* initial, const float* final_, int graph_batch_stride,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
-    int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
-    float* objf_per_seq, float* grad, int32_t* bad_count,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale, float* objf_per_seq, float* grad, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream) {
   return pychain_hip_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype,
                                              seq_lengths, B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count,
                                              workspace, workspace_bytes, stream, nullptr);
 }
 
-// ---- Viterbi alignment (align.hip) ------------------------------------------------------------
-
-namespace {
-struct AlignCarve { size_t bp, sc, total; };
-AlignCarve align_carve(int B, int T, int H, int K, int D) {
-  AlignCarve c;
-  c.bp = 0;
-  if (num_needs_general(H, K, D)) {                  // int32 backpointers + the two score vectors per sequence
-    c.sc = align256(4 * (size_t)B * T * H);
-    c.total = c.sc + align256(16 * (size_t)B * H) + 256;
-  } else {                                          // uint16 backpointers, rows of H rounded up to even
-    c.sc = align256(2 * (size_t)B * T * (size_t)((H + 1) & ~1));
-    c.total = c.sc + 256;
-  }
-  return c;
-}
-bool align_half_native(int H, int K, int D) { return !num_needs_general(H, K, D) && D % 4 == 0 && D <= 4 * 8 * 512; }
-}  // namespace
-
-extern "C" size_t pychain_hip_align_workspace_bytes(int B, int T, int H, int K, int D) {
-  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
-  return align_carve(B, T, H, K, D).total;
-}
-extern "C" int pychain_hip_align_half_native(int H, int K, int D) {
-  if (H <= 0 || K <= 0 || D <= 0) return 0;
-  return align_half_native(H, K, D) ? 1 : 0;
-}
-
-extern "C" int pychain_hip_align_tw(
-    const int32_t* ft, const int32_t* fi, const float* fp,
-    const int32_t* bt, const int32_t* bi, const float* bp,
-    const float* initial, const float* final_, int graph_batch_stride,
-    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
-    int B, int T, int D, int H, int K,
-    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
-  const char* who = "align";
-  (void)ft; (void)fi; (void)fp;                      // (the recursion gathers over the arcs entering each state only)
-  if (nnet_output_dtype < PYCHAIN_HIP_F32 || nnet_output_dtype > PYCHAIN_HIP_F16)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown nnet_output_dtype %d", who, nnet_output_dtype);
-  if (!bt || !bi || !bp || !initial || !final_ || !nnet_output || !seq_lengths || !score_per_seq || !states || !pdfs ||
-      !bad_count || !workspace)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
-  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || K <= 0)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
-  if (graph_batch_stride != 0 && graph_batch_stride != 1)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
-  if (((uintptr_t)nnet_output | (uintptr_t)bi) & 15)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: nnet_output and index tensors must be 16-byte aligned", who);
-  const AlignCarve c = align_carve(B, T, H, K, D);
-  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace too small", who);
-  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !align_half_native(H, K, D))
-    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_align_half_native)", who);
-  AlignArgs a;
-  memset(&a, 0, sizeof(a));
-  a.bwd_trans = bt; a.bwd_idx = bi; a.bwd_probs = bp; a.initial = initial; a.final_ = final_;
-  a.x = (const float*)nnet_output; a.x_half = nnet_output_dtype; a.lengths = seq_lengths;
-  a.score = score_per_seq; a.states = states; a.pdfs = pdfs; a.bad = bad_count;
-  a.graph_stride = graph_batch_stride; a.B = B; a.T = T; a.D = D; a.H = H; a.K = K;
-  a.Hb = (H + 1) & ~1;
-  a.general = num_needs_general(H, K, D) ? 1 : 0;
-  a.windows = time_windows;                          // (nullptr: the kernels without the mask, exactly the call before ABI 26)
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  if (a.general) { a.bp32 = (int32_t*)(ws + c.bp); a.gen_sc = (double*)(ws + c.sc); }
-  else { a.bp16 = (uint16_t*)(ws + c.bp); a.walk_bytes = align_walk_bytes(H, K, D); }
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(bad_count, 0, sizeof(int32_t), st) != hipSuccess)
-    return fail(PYCHAIN_HIP_ELAUNCH, "%s: hipMemsetAsync failed", who);
-  const char* why = nullptr;
-  hipError_t e = launch_align(a, st, &why);
-  if (e != hipSuccess)
-    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
-}
-
-extern "C" int pychain_hip_align(
-    const int32_t* ft, const int32_t* fi, const float* fp,
-    const int32_t* bt, const int32_t* bi, const float* bp,
-    const float* initial, const float* final_, int graph_batch_stride,
-    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
-    int B, int T, int D, int H, int K,
-    double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream) {
-  return pychain_hip_align_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
-                              B, T, D, H, K, score_per_seq, states, pdfs, bad_count, workspace, workspace_bytes, stream, nullptr);
-}
-
 // ---- fused ChainLoss ------------------------------------------------------------------
 
 namespace {
+// the arguments of pychain_hip_chain_loss_forward_xent (include/pychain_hip.h), packed once: of the whole call, or of one slice
+struct ChainLossCall {
+  DenPlan plan; float leaky;
+  NumGraphs graphs; Rows rows;
+  float* den_objf; float* num_objf; void* grad; float grad_scale; int32_t* bad_count;      // [B], [B], [B,T,D] as the rows or null, [2]
+  float loss_scale; const float* loss_norm_dev; float* totals;
+  Workspace den_ws, num_ws; hipStream_t stream; const int32_t* windows;
+  const XentCall* xent;                                                                    // checked (xent_check), or null
+};
 // one fused call over the B sequences it is given (pychain_hip_chain_loss_forward: all of them, or one slice of a large batch)
-int chain_loss_forward_one(
-    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H, float leaky,
-    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
-    const float* initial, const float* final_, int graph_batch_stride, int num_H, int num_K,
-    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
-    float* den_objf, float* num_objf, void* grad, float grad_scale, int32_t* bad_count,
-    float loss_scale, const float* loss_norm_dev, float* totals,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* windows,
-    const XentCall* xc) {
+int chain_loss_forward_one(const ChainLossCall& c) {
   const char* who = "chain_loss_forward";
-  if (!bad_count) return fail(PYCHAIN_HIP_EINVAL, "%s: null bad_count", who);
+  void* const grad = c.grad; const float* const loss_norm_dev = c.loss_norm_dev; const XentCall* const xc = c.xent;
+  const int hint = c.plan.hint;
+  if (!c.bad_count) return fail(PYCHAIN_HIP_EINVAL, "%s: null bad_count", who);
   DenArgs da;
   // without `grad` only the recursions run; any non-null aligned pointer then passes the checks
-  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, hint, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, leaky,
-                         grad_scale, den_objf, grad ? grad : den_ws, bad_count, den_ws, den_ws_bytes, who);
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_den_args(da, c.plan, c.rows, 0, c.leaky, c.grad_scale, c.den_objf, grad ? grad : c.den_ws.p, c.bad_count, c.den_ws, who)) return rc;
   NumArgs na;
-  rc = fill_num_args(na, ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths,
-                     B, T, D, num_H, num_K, PYCHAIN_HIP_GRAD_ACCUM, -grad_scale, num_objf,
-                     grad ? grad : num_ws, bad_count + 1, num_ws, num_ws_bytes, who, windows);
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_num_args(na, c.graphs, c.rows, PYCHAIN_HIP_GRAD_ACCUM, -c.grad_scale, c.num_objf, grad ? grad : c.num_ws.p, c.bad_count + 1,
+                             c.num_ws, who, c.windows)) return rc;
 
   da.fused = 1;
   na.watch_nan = 0;              // the denominator's alpha workgroups watch every element of every row (NumArgs::watch_nan)
   // the scalars of ChainLoss.forward from den_finish_kernel's last workgroup (DenArgs::loss_out)
-  da.loss_out = totals; da.loss_num_objf = num_objf; da.loss_scale = loss_scale; da.loss_norm_dev = loss_norm_dev; da.bad_words = 2;
-  hipStream_t st = (hipStream_t)stream;
+  da.loss_out = c.totals; da.loss_num_objf = c.num_objf; da.loss_scale = c.loss_scale; da.loss_norm_dev = loss_norm_dev; da.bad_words = 2;
+  hipStream_t st = c.stream;
   SideStream* side = side_streams_for(st);
   if (!side) return fail(PYCHAIN_HIP_ELAUNCH, "%s: cannot create the side stream", who);
   const char* why = nullptr;
@@ -787,20 +672,20 @@ int chain_loss_forward_one(
   // of both sides read it (DenArgs / NumArgs::grad_scale_dev) - not a pass over [B, T, D] behind the call
   float* inv_norm = (loss_norm_dev && grad) ? reinterpret_cast<float*>(da.progress + kCtrInvNorm) : nullptr;
   if (inv_norm) { da.grad_scale_dev = inv_norm; na.grad_scale_dev = inv_norm; }
-  hipError_t e = launch_zero_words(bad_count, 2, da.seq_progress, den_counter_words(da), st, loss_norm_dev, inv_norm);
+  hipError_t e = launch_zero_words(c.bad_count, 2, da.seq_progress, den_counter_words(da), st, loss_norm_dev, inv_norm);
   // The two-frame occupancy kernel folds the numerator in (grad = scale * (gamma_den - gamma_num), written
   // once): the numerator then also produces compact occupancy rows on its stream, and the occupancy
   // launches wait for them.  Otherwise the numerator is accumulated into the gradient afterwards.
   // (decided with the fold's own LDS rows counted in: gamma2_lds_bytes)
   da.fold_rows = na.rows_ws;
   const bool fold = grad && hint != PYCHAIN_HIP_HINT_GENERAL && !na.general && !na.compat &&
-                    den_uses_gamma2(da, (D + 63) / 64, hint);
+                    den_uses_gamma2(da, (c.rows.D + 63) / 64, hint);
   if (fold) {
-    da.fold_upd = na.upd_ws; da.fold_ucount = na.ucount_ws; da.fold_K = num_K;
-    da.fold_scale = -grad_scale;
+    da.fold_upd = na.upd_ws; da.fold_ucount = na.ucount_ws; da.fold_K = c.graphs.K;
+    da.fold_scale = -c.grad_scale;
   } else da.fold_rows = nullptr;
   // 2-byte network outputs: both sides take them and the gradient is written once, by the fold (chain_loss_half_native)
-  if (nnet_output_dtype != PYCHAIN_HIP_F32 && !(den_call_half_native(da, hint) && num_half_native(na) && (fold || !grad)))
+  if (c.rows.dtype != PYCHAIN_HIP_F32 && !(den_call_half_native(da, hint) && num_half_native(na) && (fold || !grad)))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_chain_loss_half_native)", who);
   // fork: numerator on the side stream, denominator recursion on the caller's stream
   if (e == hipSuccess) e = hipEventRecord(side->fork, st);
@@ -844,9 +729,7 @@ int chain_loss_forward_one(
     e = na.general ? launch_num_occ(na, false, st, &why) : launch_num_scatter(na, st, &why);
   if (e == hipSuccess && xjoin) e = hipStreamWaitEvent(st, xjoin, 0);
   if (e == hipSuccess && xc && na.general) e = run_xent(na, *xc, loss_norm_dev, st, &why);   // (dense posteriors: slow but complete)
-  if (e != hipSuccess)
-    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed(who, e, why);
 }
 
 // ---- a batch larger than the chip: slices (round 5).  From B = 224 on 256 CUs the recursion workgroups of ONE call (two
@@ -936,55 +819,45 @@ extern "C" int pychain_hip_chain_loss_forward_xent(
     void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, const int32_t* time_windows,
     const pychain_hip_xent* xent) {
   XentCall xcall;
-  const XentCall* xc = nullptr;
-  if (xent) {
-    const int xrc = xent_check(xent, B, T, num_H, num_K, D, "chain_loss_forward", xcall);
-    if (xrc != PYCHAIN_HIP_OK) return xrc;
-    xc = &xcall;
-  }
+  if (xent) { if (int rc = xent_check(xent, B, T, num_H, num_K, D, "chain_loss_forward", xcall)) return rc; }
+  const ChainLossCall c{{plans_dev, plan_stride_bytes, hint, den_H}, leaky,
+                        {ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, num_H, num_K},
+                        {nnet_output, nnet_output_dtype, seq_lengths, B, T, D},
+                        den_objf, num_objf, grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals,
+                        {den_ws, den_ws_bytes}, {num_ws, num_ws_bytes}, (hipStream_t)stream, time_windows, xent ? &xcall : nullptr};
   // the sums of the xent objectives and the full loss into totals[0], totals[4]: one small launch behind the call's last kernel
   auto xent_finish = [&]() -> int {
     if (!xent || (!xent->xent_totals && !totals)) return PYCHAIN_HIP_OK;
-    const hipError_t xe = launch_xent_totals(xcall.objf, B, loss_scale, loss_norm_dev, xent->loss_coef, xent->xent_totals, totals, (hipStream_t)stream);
+    const hipError_t xe = launch_xent_totals(xcall.objf, B, loss_scale, loss_norm_dev, xent->loss_coef, xent->xent_totals, totals, c.stream);
     if (xe != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "chain_loss_forward: %s", hipGetErrorString(xe));
     return PYCHAIN_HIP_OK;
   };
-  const int nsl = (B > 0 && T > 0 && D > 0 && den_ws && bad_count && den_objf && num_objf && seq_lengths && nnet_output && ft && fi && fp &&
-                   bt && bi && bp && initial && final_ && den_ws_bytes > 8192)
+  const int nsl = (B > 0 && T > 0 && D > 0 && den_ws && bad_count && den_objf && num_objf && seq_lengths && nnet_output &&
+                   !c.graphs.any_null() && den_ws_bytes > 8192)
                       ? chain_loss_slices(B, hint, plan_stride_bytes, grad != nullptr) : 1;
   note_forward_workspace(den_ws, nsl > 1);
   if (nsl <= 1) {
-    const int rc1 = chain_loss_forward_one(plans_dev, plan_stride_bytes, hint, den_H, leaky, ft, fi, fp, bt, bi, bp, initial, final_,
-                                           graph_batch_stride, num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, den_objf, num_objf,
-                                           grad, grad_scale, bad_count, loss_scale, loss_norm_dev, totals, den_ws, den_ws_bytes, num_ws, num_ws_bytes,
-                                           stream, time_windows, xc);
+    const int rc1 = chain_loss_forward_one(c);
     return rc1 != PYCHAIN_HIP_OK ? rc1 : xent_finish();
   }
   // the scratch lines: the last 4 KiB of the denominator's workspace (sized by the caller for all B sequences; a slice
   // needs about 1 / nsl of it)
   const size_t ws_bytes = (den_ws_bytes - 4096) & ~(size_t)255;
   SliceLine* lines = reinterpret_cast<SliceLine*>((char*)den_ws + ws_bytes);
-  const size_t esz = nnet_output_dtype == PYCHAIN_HIP_F32 ? 4 : 2;
   // (a multiple of 8 sequences: every slice's rows, gradient and graph tensors start 16-byte aligned whatever T and D are -
   // 2-byte rows of odd T x D included -, and the pair recursion takes its sequences two by two)
   const int per = ((B + nsl - 1) / nsl + 7) & ~7;
-  int c = 0;
+  int n = 0;
   XentCall xslice;
-  for (int b0 = 0; b0 < B; b0 += per, c++) {
-    const int nb = std::min(per, B - b0);
-    const size_t g = graph_batch_stride ? (size_t)b0 : 0;     // per-sequence numerator graphs: [G, K, 3] / [G, H, 2] / [G, K] / [G, H]
-    const int rc = chain_loss_forward_one(
-        plans_dev, plan_stride_bytes, hint, den_H, leaky,
-        ft + g * num_K * 3, fi + g * num_H * 2, fp + g * num_K, bt + g * num_K * 3, bi + g * num_H * 2, bp + g * num_K,
-        initial + g * num_H, final_ + g * num_H, graph_batch_stride, num_H, num_K,
-        (const char*)nnet_output + (size_t)b0 * T * D * esz, nnet_output_dtype, seq_lengths + b0, nb, T, D,
-        den_objf + b0, num_objf + b0, (char*)grad + (size_t)b0 * T * D * esz, grad_scale, lines[c].bad,
-        loss_scale, loss_norm_dev, lines[c].totals, den_ws, ws_bytes, num_ws, num_ws_bytes, stream,
-        time_windows ? time_windows + (size_t)b0 * num_H * 2 : nullptr,      // (one window row per sequence, shared graph or not)
-        xc ? &(xslice = xent_slice(xcall, b0, T, D)) : nullptr);
-    if (rc != PYCHAIN_HIP_OK) return rc;
+  for (int b0 = 0; b0 < B; b0 += per, n++) {
+    ChainLossCall s = c;                                     // the call over the sequences b0 .. b0 + per, reporting into its line
+    s.graphs = c.graphs.at(b0); s.rows = c.rows.slice(b0, std::min(per, B - b0)); s.windows = window_row(time_windows, b0, num_H);
+    s.den_objf = den_objf + b0; s.num_objf = num_objf + b0; s.grad = (char*)grad + c.rows.offset(b0);
+    s.bad_count = lines[n].bad; s.totals = lines[n].totals; s.den_ws.bytes = ws_bytes;
+    if (xent) { xslice = xent_slice(xcall, b0, T, D); s.xent = &xslice; }
+    if (int rc = chain_loss_forward_one(s)) return rc;
   }
-  hipLaunchKernelGGL(chain_slices_combine_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, lines, c, den_objf, num_objf, seq_lengths,
+  hipLaunchKernelGGL(chain_slices_combine_kernel, dim3(1), dim3(256), 0, c.stream, lines, n, den_objf, num_objf, seq_lengths,
                      B, T, loss_scale, loss_norm_dev, bad_count, totals);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(PYCHAIN_HIP_ELAUNCH, "chain_loss_forward: %s", hipGetErrorString(e));
@@ -1092,15 +965,15 @@ extern "C" int pychain_hip_loss_total(const float* den_objf_per_seq, const float
   return PYCHAIN_HIP_OK;
 }
 
-namespace {
-int chain_loss_backward_impl(
+extern "C" int pychain_hip_chain_loss_backward(
     const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H,
     const int32_t* ft, const int32_t* fi, const float* fp, int graph_batch_stride, int num_H, int num_K,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     float grad_scale, const float* grad_scale_dev, void* grad, int32_t* bad_count,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream, bool zero_bad) {
+    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
   const char* who = "chain_loss_backward";
-  if (!bad_count || !ft || !fi || !fp) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  const Rows rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D};
+  if (!bad_count || !ft || !fi || !fp) return null_pointer(who);
   if (workspace_was_sliced(den_ws))
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: the forward call on these workspaces wrote its gradient in slices (a batch larger than the "
                 "chip: pychain_hip_chain_loss_slices) - the workspaces hold the last slice's trajectories only.  Take the gradient "
@@ -1109,42 +982,24 @@ int chain_loss_backward_impl(
   float dummy_coef = 0.5f;       // the occupancy launch does not use the leaky coefficient
   if (nnet_output_dtype != PYCHAIN_HIP_F32)              // (the numerator's occupancy launch accumulates into an fp32 gradient)
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: 2-byte network outputs are taken by the forward call that also writes the gradient", who);
-  int rc = fill_den_args(da, plans_dev, plan_stride_bytes, hint, den_H, D, nnet_output, nnet_output_dtype, 0, seq_lengths, B, T, dummy_coef,
-                         grad_scale, (float*)den_ws, grad, bad_count, den_ws, den_ws_bytes, who);
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_den_args(da, DenPlan{plans_dev, plan_stride_bytes, hint, den_H}, rows, 0, dummy_coef, grad_scale, (float*)den_ws, grad,
+                             bad_count, Workspace{den_ws, den_ws_bytes}, who)) return rc;
   da.grad_scale_dev = grad_scale_dev;
   da.fused = 1;                                          // (the forward call that stored the rows decided as a fused call)
   den_decide_family(da, hint);                           // (what the stored rows ARE: DenArgs::lazy, DenArgs::sg)
   NumArgs na;
   // the occupancy launch reads only the forward transitions / indices / log-probs of the graphs
-  rc = fill_num_args(na, ft, fi, fp, ft, fi, fp, fp, fp,
-                     graph_batch_stride, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, num_H, num_K, PYCHAIN_HIP_GRAD_ACCUM,
-                     -grad_scale, (float*)num_ws, grad, bad_count + 1, num_ws, num_ws_bytes, who, nullptr);   // (stored rows: no windows)
-  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (int rc = fill_num_args(na, NumGraphs{ft, fi, fp, ft, fi, fp, fp, fp, graph_batch_stride, num_H, num_K}, rows, PYCHAIN_HIP_GRAD_ACCUM,
+                             -grad_scale, (float*)num_ws, grad, bad_count + 1, Workspace{num_ws, num_ws_bytes}, who, nullptr)) return rc;   // (stored rows: no windows)
   na.grad_scale_dev = grad_scale_dev;
   hipStream_t st = (hipStream_t)stream;
   const char* why = nullptr;
-  hipError_t e = zero_bad ? hipMemsetAsync(bad_count, 0, 2 * sizeof(int32_t), st) : hipSuccess;
+  hipError_t e = hipMemsetAsync(bad_count, 0, 2 * sizeof(int32_t), st);
   da.phase_mask = 2;
   if (e == hipSuccess)
     e = hint == PYCHAIN_HIP_HINT_GENERAL ? launch_den_general(da, st) : launch_den(da, (D + 63) / 64, hint, st, &why);
   if (e == hipSuccess) e = na.compat ? launch_num_compat(na, 2, st) : launch_num_occ(na, false, st, &why);
-  if (e != hipSuccess)
-    return fail(why ? PYCHAIN_HIP_EUNSUPPORTED : PYCHAIN_HIP_ELAUNCH, "%s: %s", who, why ? why : hipGetErrorString(e));
-  return PYCHAIN_HIP_OK;
-}
-
-}  // namespace
-
-extern "C" int pychain_hip_chain_loss_backward(
-    const void* plans_dev, int64_t plan_stride_bytes, int hint, int den_H,
-    const int32_t* ft, const int32_t* fi, const float* fp, int graph_batch_stride, int num_H, int num_K,
-    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
-    float grad_scale, const float* grad_scale_dev, void* grad, int32_t* bad_count,
-    void* den_ws, size_t den_ws_bytes, void* num_ws, size_t num_ws_bytes, void* stream) {
-  return chain_loss_backward_impl(plans_dev, plan_stride_bytes, hint, den_H, ft, fi, fp, graph_batch_stride,
-                                  num_H, num_K, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, grad_scale, grad_scale_dev, grad,
-                                  bad_count, den_ws, den_ws_bytes, num_ws, num_ws_bytes, stream, true);
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed(who, e, why);
 }
 
 extern "C" int pychain_hip_chain_loss_forward_backward_xent(

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/pychain_hip.h"
+#include "call_args.h"
 #include "common.h"
 
 namespace pychain_hip {
@@ -31,7 +32,10 @@ struct Csr {                       // one graph in the reference layout: arcs {s
   const int32_t* idx;
   const float* prob;
 };
+inline Csr fwd_of(const NumGraphs& g) { return Csr{g.ft, g.fi, g.fp}; }     // arcs leaving each state
+inline Csr bwd_of(const NumGraphs& g) { return Csr{g.bt, g.bi, g.bp}; }     // arcs entering each state
 inline float clamp30(float v) { return v != v ? v : (v < -30.f ? -30.f : (v > 30.f ? 30.f : v)); }
+inline int clamped_length(int64_t l, int T) { return l < 1 ? 1 : (l > T ? T : (int)l); }     // (the row passes: as on the device)
 
 template <class F>
 void for_each_sequence(int B, int num_threads, F&& body) {
@@ -267,14 +271,12 @@ bool align_one(const Csr& bwd, const float* init, const float* fin, const float*
   return true;
 }
 
-int check_common(const char* who, const void* ft, const void* fi, const void* fp, const void* bt, const void* bi, const void* bp,
-                 const void* initial, const void* final_, const void* x, const int64_t* lengths, const void* objf, const void* grad,
-                 const void* bad, int B, int T, int D, int H, int K) {
-  if (!ft || !fi || !fp || !bt || !bi || !bp || !initial || !final_ || !x || !lengths || !objf || !grad || !bad)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
-  if (B <= 0 || T <= 0 || D <= 0 || H <= 0 || K <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d H=%d K=%d D=%d", who, B, T, H, K, D);
-  for (int b = 0; b < B; b++)
-    if (lengths[b] < 1 || lengths[b] > T) return fail(PYCHAIN_HIP_EINVAL, "%s: sequence lengths must be in [1, %d]", who, T);
+// (`out0`, `out1`: the first two outputs of the call; the graph stride is checked behind whatever the call checks next)
+int check_common(const char* who, const NumGraphs& g, const Rows& rows, const void* out0, const void* out1, const void* bad) {
+  if (g.any_null() || !rows.x || !rows.lengths || !out0 || !out1 || !bad) return null_pointer(who);
+  if (int rc = bad_sizes(who, rows, g)) return rc;
+  for (int b = 0; b < rows.B; b++)
+    if (rows.lengths[b] < 1 || rows.lengths[b] > rows.T) return fail(PYCHAIN_HIP_EINVAL, "%s: sequence lengths must be in [1, %d]", who, rows.T);
   return PYCHAIN_HIP_OK;
 }
 // ---- the numerator posteriors as cross-entropy targets of z (include/pychain_hip.h: pychain_hip_xent; the device's xent.hip):
@@ -314,18 +316,19 @@ extern "C" int pychain_hip_cpu_den_forward_backward(
     const float* nnet_output, int input_is_exp, const int64_t* seq_lengths, int B, int T, int D, int H, int K,
     float leaky_hmm_coefficient, float grad_scale, float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads) {
   const char* who = "cpu_den_forward_backward";
-  int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, objf_per_seq, grad, bad_count, B, T, D, H, K);
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K};
+  int rc = check_common(who, graphs, Rows{nnet_output, PYCHAIN_HIP_F32, seq_lengths, B, T, D}, objf_per_seq, grad, bad_count);
   if (rc != PYCHAIN_HIP_OK) return rc;
   if (!leaky) return fail(PYCHAIN_HIP_EINVAL, "%s: null leaky_probs", who);
-  if (graph_batch_stride != 0 && graph_batch_stride != 1) return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+  if ((rc = bad_stride(who, graph_batch_stride)) != PYCHAIN_HIP_OK) return rc;
   if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
     return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
   g_cpu_calls++;
   std::atomic<int> bad{0};
   for_each_sequence(B, num_threads, [&](int b) {
-    const size_t g = (size_t)b * graph_batch_stride;
-    const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
-    const bool ok = den_one(fwd, bwd, leaky + g * H, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, input_is_exp,
+    const NumGraphs g = graphs.at(b);
+    const float* lk = leaky + (g.initial - initial);         // ([G,H], laid out as the initial probabilities are)
+    const bool ok = den_one(fwd_of(g), bwd_of(g), lk, g.initial, g.final_, nnet_output + (size_t)b * T * D, input_is_exp,
                             (int)seq_lengths[b], T, D, H, leaky_hmm_coefficient, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D);
     if (!ok) bad++;
   });
@@ -339,19 +342,18 @@ extern "C" int pychain_hip_cpu_num_forward_backward_tw(
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
     float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads, const int32_t* time_windows) {
   const char* who = "cpu_num_forward_backward";
-  int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, objf_per_seq, grad, bad_count, B, T, D, H, K);
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K};
+  int rc = check_common(who, graphs, Rows{nnet_output, PYCHAIN_HIP_F32, seq_lengths, B, T, D}, objf_per_seq, grad, bad_count);
   if (rc != PYCHAIN_HIP_OK) return rc;
-  if (graph_batch_stride != 0 && graph_batch_stride != 1) return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+  if ((rc = bad_stride(who, graph_batch_stride)) != PYCHAIN_HIP_OK) return rc;
   if ((grad_mode & ~PYCHAIN_HIP_CPU_NO_CLAMP) < PYCHAIN_HIP_GRAD_LOG || (grad_mode & ~PYCHAIN_HIP_CPU_NO_CLAMP) > PYCHAIN_HIP_GRAD_ACCUM)
     return fail(PYCHAIN_HIP_EINVAL, "%s: unknown grad_mode %d", who, grad_mode);
   g_cpu_calls++;
   std::atomic<int> bad{0};
   for_each_sequence(B, num_threads, [&](int b) {
-    const size_t g = (size_t)b * graph_batch_stride;
-    const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
-    const bool ok = num_one(fwd, bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
-                            grad_mode, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D,
-                            time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
+    const NumGraphs g = graphs.at(b);
+    const bool ok = num_one(fwd_of(g), bwd_of(g), g.initial, g.final_, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
+                            grad_mode, grad_scale, objf_per_seq + b, grad + (size_t)b * T * D, window_row(time_windows, b, H));
     if (!ok) bad++;
   });
   *bad_count = bad.load();
@@ -373,19 +375,17 @@ extern "C" int pychain_hip_cpu_align_tw(
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K,
     double* score_per_seq, int32_t* states, int64_t* pdfs, int32_t* bad_count, int num_threads, const int32_t* time_windows) {
   const char* who = "cpu_align";
-  int rc = check_common(who, ft, fi, fp, bt, bi, bp, initial, final_, nnet_output, seq_lengths, score_per_seq, states, bad_count,
-                        B, T, D, H, K);
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K};
+  int rc = check_common(who, graphs, Rows{nnet_output, PYCHAIN_HIP_F32, seq_lengths, B, T, D}, score_per_seq, states, bad_count);
   if (rc != PYCHAIN_HIP_OK) return rc;
-  if (!pdfs) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
-  if (graph_batch_stride != 0 && graph_batch_stride != 1) return fail(PYCHAIN_HIP_EINVAL, "%s: graph_batch_stride must be 0 or 1", who);
+  if (!pdfs) return null_pointer(who);
+  if ((rc = bad_stride(who, graph_batch_stride)) != PYCHAIN_HIP_OK) return rc;
   g_cpu_calls++;
   std::atomic<int> bad{0};
   for_each_sequence(B, num_threads, [&](int b) {
-    const size_t g = (size_t)b * graph_batch_stride;
-    const Csr bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
-    const bool ok = align_one(bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
-                              score_per_seq + b, states + (size_t)b * (T + 1), pdfs + (size_t)b * T,
-                              time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
+    const NumGraphs g = graphs.at(b);
+    const bool ok = align_one(bwd_of(g), g.initial, g.final_, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
+                              score_per_seq + b, states + (size_t)b * (T + 1), pdfs + (size_t)b * T, window_row(time_windows, b, H));
     if (!ok) bad++;
   });
   *bad_count = bad.load();
@@ -416,14 +416,13 @@ extern "C" int pychain_hip_cpu_num_forward_backward_xent(
   if (rc != PYCHAIN_HIP_OK || !xent) return rc;
   // gamma: the occupancies once more, per sequence, as a linear fp32 row buffer of the thread's own; then the rows of z
   const float sc = xent->grad_scale * (xent->grad_scale_dev ? *xent->grad_scale_dev : 1.f);
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K};
   for_each_sequence(B, num_threads, [&](int b) {
-    const size_t g = (size_t)b * graph_batch_stride;
-    const Csr fwd{ft + g * K * 3, fi + g * H * 2, fp + g * K}, bwd{bt + g * K * 3, bi + g * H * 2, bp + g * K};
+    const NumGraphs g = graphs.at(b);
     std::vector<float> gamma((size_t)T * D);
     float logp = 0.f;
-    num_one(fwd, bwd, initial + g * H, final_ + g * H, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
-            PYCHAIN_HIP_GRAD_LINEAR | (grad_mode & PYCHAIN_HIP_CPU_NO_CLAMP), 1.f, &logp, gamma.data(),
-            time_windows ? time_windows + (size_t)b * H * 2 : nullptr);
+    num_one(fwd_of(g), bwd_of(g), g.initial, g.final_, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H,
+            PYCHAIN_HIP_GRAD_LINEAR | (grad_mode & PYCHAIN_HIP_CPU_NO_CLAMP), 1.f, &logp, gamma.data(), window_row(time_windows, b, H));
     xent->xent_objf_per_seq[b] = (float)xent_one(gamma.data(), std::isfinite(logp), (const float*)xent->z + (size_t)b * T * D, (int)seq_lengths[b],
                                                  T, D, sc, xent->xent_grad ? (float*)xent->xent_grad + (size_t)b * T * D : nullptr);
   });
@@ -460,7 +459,7 @@ extern "C" int pychain_hip_cpu_output_reg(
     float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
     float* reg_per_seq, float loss_scale, float* reg_totals, float* totals, int num_threads) {
   const char* who = "cpu_output_reg";
-  if (!nnet_output || !seq_lengths || !reg_per_seq) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (!nnet_output || !seq_lengths || !reg_per_seq) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (!(l2 >= 0.f) || !(oor >= 0.f) || !(limit >= 0.f))
     return fail(PYCHAIN_HIP_EINVAL, "%s: l2, oor and limit must not be negative (got %g, %g, %g)", who, (double)l2, (double)oor, (double)limit);
@@ -474,8 +473,7 @@ extern "C" int pychain_hip_cpu_output_reg(
   const bool accum = grad_mode == PYCHAIN_HIP_GRAD_ACCUM;
   std::vector<double> pairs(2 * (size_t)B);
   for_each_sequence(B, num_threads, [&](int b) {
-    const int64_t l = seq_lengths[b];
-    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const int L = clamped_length(seq_lengths[b], T);
     const float* x = nnet_output + (size_t)b * T * D;
     float* g = grad ? grad + (size_t)b * T * D : nullptr;
     double s2 = 0.0, so = 0.0;
@@ -524,7 +522,7 @@ extern "C" int pychain_hip_cpu_weight_rows(
   if (!grad && !sums) return fail(PYCHAIN_HIP_EINVAL, "%s: nothing to do (no grad, no totals, no weighted)", who);
   if (sums && (!den_objf_per_seq || !num_objf_per_seq)) return fail(PYCHAIN_HIP_EINVAL, "%s: the sums need den_objf_per_seq and num_objf_per_seq", who);
   g_cpu_calls++;
-  auto len = [&](int b) { const int64_t l = seq_lengths[b]; return l < 1 ? 1 : (l > T ? T : (int)l); };
+  auto len = [&](int b) { return clamped_length(seq_lengths[b], T); };
   if (grad) {
     for_each_sequence(B, num_threads, [&](int b) {
       const int L = len(b);
@@ -578,8 +576,7 @@ extern "C" int pychain_hip_cpu_post_targets(
     const float* den_objf_per_seq, float* num_objf_per_seq, int32_t* bad_count,
     float loss_scale, float* totals, int num_threads) {
   const char* who = "cpu_post_targets";
-  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !num_objf_per_seq || !bad_count)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !num_objf_per_seq || !bad_count) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
   if (totals && !den_objf_per_seq) return fail(PYCHAIN_HIP_EINVAL, "%s: totals need den_objf_per_seq", who);
@@ -589,8 +586,7 @@ extern "C" int pychain_hip_cpu_post_targets(
   std::vector<double> sums((size_t)B);
   std::vector<int> bads((size_t)B);
   for_each_sequence(B, num_threads, [&](int b) {
-    const int64_t l = seq_lengths[b];
-    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const int L = clamped_length(seq_lengths[b], T);
     double seq = 0.0;
     int bad = 0;
     for (int t = 0; t < L; t++) {
@@ -648,8 +644,7 @@ extern "C" int pychain_hip_cpu_xent_targets(
     float grad_scale, const float* grad_scale_dev, const float* loss_norm_dev,
     float* xent_objf_per_seq, int32_t* bad_count, int num_threads) {
   const char* who = "cpu_xent_targets";
-  if (!z || !seq_lengths || !target_pdfs || !target_probs || !xent_objf_per_seq || !bad_count)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (!z || !seq_lengths || !target_pdfs || !target_probs || !xent_objf_per_seq || !bad_count) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
   g_cpu_calls++;
@@ -657,8 +652,7 @@ extern "C" int pychain_hip_cpu_xent_targets(
   if (loss_norm_dev) sc = sc / *loss_norm_dev;
   std::vector<int> bads((size_t)B);
   for_each_sequence(B, num_threads, [&](int b) {
-    const int64_t l = seq_lengths[b];
-    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const int L = clamped_length(seq_lengths[b], T);
     if (xent_grad) std::fill(xent_grad + (size_t)b * T * D, xent_grad + (size_t)(b + 1) * T * D, 0.f);
     std::vector<int> pdf_of((size_t)K);               // the frame's distinct live pdfs, where each occurs first, and their qd
     std::vector<float> qd_of((size_t)K);
@@ -735,16 +729,14 @@ extern "C" int pychain_hip_cpu_boost_rows(
     const int32_t* target_pdfs, const float* target_probs, int K, float boost,
     float* e, int32_t* bad_count, int num_threads) {
   const char* who = "cpu_boost_rows";
-  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !e || !bad_count)
-    return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (!nnet_output || !seq_lengths || !target_pdfs || !target_probs || !e || !bad_count) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
   if (!(boost >= 0.f) || !std::isfinite(boost)) return fail(PYCHAIN_HIP_EINVAL, "%s: boost must be finite and not negative, got %g", who, (double)boost);
   g_cpu_calls++;
   std::vector<int> bads((size_t)B);
   for_each_sequence(B, num_threads, [&](int b) {
-    const int64_t l = seq_lengths[b];
-    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const int L = clamped_length(seq_lengths[b], T);
     int bad = 0;
     for (int t = 0; t < L; t++) {
       const size_t f = (size_t)b * T + t;
@@ -779,13 +771,12 @@ extern "C" int pychain_hip_cpu_boost_rows(
 extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int D, int K, float floor,
                                          int normalize, int32_t* out_pdfs, float* out_probs, int num_threads) {
   const char* who = "cpu_topk_rows";
-  if (!rows || !seq_lengths || !out_pdfs || !out_probs) return fail(PYCHAIN_HIP_EINVAL, "%s: null pointer argument", who);
+  if (!rows || !seq_lengths || !out_pdfs || !out_probs) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1 || K > D || K > 64) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be in [1, min(D, 64)], got %d (D = %d)", who, K, D);
   g_cpu_calls++;
   for_each_sequence(B, num_threads, [&](int b) {
-    const int64_t l = seq_lengths[b];
-    const int L = l < 1 ? 1 : (l > T ? T : (int)l);
+    const int L = clamped_length(seq_lengths[b], T);
     for (int t = 0; t < T; t++) {
       const size_t f = (size_t)b * T + t;
       int32_t* op = out_pdfs + f * K;

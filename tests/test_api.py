@@ -395,3 +395,40 @@ def test_den_decisions_match_the_recorded_grid():
     assert not wrong, "%d of %d rows differ" % (len(wrong), len(want))
     sizes = {k: list(v) for k, v in got["workspace"].items()}
     assert sizes == recorded["workspace"], {k: (recorded["workspace"].get(k), v) for k, v in sizes.items() if recorded["workspace"].get(k) != v}
+
+
+def test_refusals_match_the_recorded_ones():
+    """What the device entry points and their host twins answer to calls they must refuse - one thing wrong per call, a few with
+    two things wrong (which refusal comes first), a few through the narrow entry points (the forwarding) - is the recorded
+    (return code, pychain_hip_last_error()) pair, case by case (tests/golden/make_api_refusals.py).  Every call is refused before
+    the device is touched.  A change of a refusal regenerates the file on purpose; a refactor does not."""
+    import importlib.util
+    import json
+    golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    spec = importlib.util.spec_from_file_location("make_api_refusals", os.path.join(golden, "make_api_refusals.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with open(os.path.join(golden, "api_refusals.json")) as f:
+        recorded = json.load(f)
+    got = gen.compute(_lib)
+    assert len(recorded) >= 120 and len(set(r[0] for r in recorded)) == len(recorded)
+    assert [g[0] for g in got] == [r[0] for r in recorded]
+    wrong = [(r, g) for r, g in zip(recorded, got) if r != g]
+    for r, g in wrong[:20]:
+        print(r[0], "recorded", r[1:], "got", g[1:])
+    assert not wrong, "%d of %d refusals differ" % (len(wrong), len(recorded))
+    assert all(r[1] < 0 for r in recorded)
+
+
+def test_ctypes_signatures_have_the_parameter_counts_of_the_header():
+    """Every prototype of include/pychain_hip.h has as many parameters as the argtypes `_lib` gives the symbol."""
+    hdr = open(os.path.join(REPO, "include", "pychain_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    hdr = re.sub(r"//[^\n]*", " ", hdr)
+    protos = re.findall(r"\b(pychain_hip_[a-z_0-9]+)\s*\(([^()]*)\)\s*;", hdr)
+    assert len(protos) >= 80 and len(set(n for n, _ in protos)) == len(protos)
+    assert set(n for n, _ in protos) == set(_lib.EXPORTS)
+    for name, params in protos:
+        params = " ".join(params.split())
+        count = 0 if params in ("", "void") else params.count(",") + 1
+        assert count == len(_lib._SIGNATURES[name][1]), (name, count, len(_lib._SIGNATURES[name][1]))

@@ -542,3 +542,57 @@ def test_backward_on_workspaces_a_sliced_forward_wrote_is_refused():
     torch.cuda.synchronize()
     assert int(bad2.sum()) == 0 and int(bad3.sum()) == 0
     assert (g2 - st.grad).abs().max() <= 1e-6 * st.grad.abs().max()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+def test_a_sliced_call_is_its_slices_called_by_hand(dtype):
+    """Everything a sliced fused call advances from slice to slice - the per-utterance numerator graphs, the rows, the lengths, the
+    time windows, the gradient, both per-sequence objectives, the xent output, its objectives and its gradient - at once: the
+    fused forward with gradient over B = 16 ragged sequences as two slices of 8 (option chain_slices = 2) against the same
+    entry point called by hand on sequences 0-7 and 8-15 with tensors sliced here and chain_slices = 0.  Both sides run calls of 8
+    sequences, so every output is the same bit for bit; the bad counts add up and totals[3] is the fp64 sum of den - num
+    rounded once."""
+    from pychain_amd import alignment_windows, viterbi_align
+    B, T, D, C = 16, 21, 24, 0.1
+    dev = torch.device(DEV)
+    den = syn.make_den_graph(30, 120, D, seed=3)
+    L = syn.make_lengths(B, T, "ragged", seed=6)
+    num = syn.make_num_graphs(L.tolist(), D, seed=40)
+    xh = syn.make_input(B, T, D, seed=8)
+    ali = viterbi_align(xh, L, num)
+    assert bool(ali.ok.all())
+    num.set_time_windows(alignment_windows(ali, num.num_states, 2))
+    plan = _plan.graph_plan(den, D, dev)
+    gt, w = num.device_tensors(dev), num.device_time_windows(dev)
+    x, z = xh.to(DEV).to(dtype), (syn.make_input(B, T, D, seed=9) * 1.5).to(DEV).to(dtype)
+    x[11, 3, 5] = float("nan")                                     # (the second slice has something to count)
+    lib = _lib.lib()
+    K = gt["forward_transitions"].shape[1]
+    assert lib.pychain_hip_chain_loss_slices(plan.stride, plan.slot_rows, B) == 1
+    half = [lib.pychain_hip_chain_loss_half_native(plan.stride, plan.slot_rows, plan.num_states, D, b, T, num.num_states, K) for b in (B, B // 2)]
+    assert half[0] == half[1]
+
+    def call(sl, slices):
+        g = {k: v[sl].clone() for k, v in gt.items()}
+        with _lib.option("chain_slices", slices):
+            den_objf, num_objf, bad, st, totals = native.chain_loss_forward(
+                plan, g, 1, num.num_states, x[sl].clone(), L[sl].clone(), 1e-5, with_grad=True, windows=w[sl].clone(),
+                xent=(z[sl].clone(), True, C))
+        torch.cuda.synchronize()
+        return den_objf, num_objf, st.grad, st.xent.objf, st.xent.grad, bad, totals
+    with _lib.option("chain_slices", 2):
+        assert lib.pychain_hip_chain_loss_slices(plan.stride, plan.slot_rows, B) == 2
+    whole = call(slice(0, B), 2)
+    parts = [call(slice(0, 8), 0), call(slice(8, 16), 0)]
+    assert whole[2].dtype == dtype and whole[4].dtype == dtype
+    for i, what in enumerate(("den_objf", "num_objf", "grad", "xent objf", "xent grad")):
+        by_hand = torch.cat([p[i] for p in parts])
+        assert by_hand.dtype == whole[i].dtype and by_hand.shape == whole[i].shape, what
+        assert torch.equal(torch.nan_to_num(whole[i].float(), nan=12345.0), torch.nan_to_num(by_hand.float(), nan=12345.0)), what
+    assert torch.equal(whole[5], parts[0][5] + parts[1][5])
+    assert int(parts[0][5].sum()) == 0 and int(parts[1][5].sum()) >= 1
+    x[11, 3, 5] = 0.0                                             # (finite totals)
+    whole = call(slice(0, B), 2)
+    assert int(whole[5].sum()) == 0
+    s = (whole[0].double() - whole[1].double()).sum()
+    assert float(whole[6][3]) == float(s.float())
