@@ -52,8 +52,8 @@ def needs_build():
 
 
 def build(force=False, verbose=False, extra_flags=(), lib=None):
-    """`extra_flags` / `lib`: ablation and timing builds (-DPYCHAIN_EXP_*, -DPYCHAIN_PROFILE_PHASES) into a library of
-    their own (objects are then not cached)."""
+    """`extra_flags` / `lib`: the instrumented build (-DPYCHAIN_PROFILE_PHASES) or any other one-off build into a library of
+    its own (objects are then not cached)."""
     out = lib or LIB
     variant = bool(extra_flags) or lib is not None
     if not force and not variant and not needs_build():

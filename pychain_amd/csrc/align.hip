@@ -278,21 +278,6 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
   int32_t* st = a.states + (size_t)b * (T + 1);
   if (tid == 0) st[L] = hstar;
 
-#if PYCHAIN_EXP_ALIGN_NAIVE_WALK
-  // measurement variant: one lane walks the backpointers where the forward left them (a dependent global load per frame)
-  if (tid == 0) {
-    int h = hstar;
-    for (int t = L - 1; t >= 0; t--) {
-      const size_t q = (size_t)t * a.Hb + h;
-      const uint32_t wd = fresh_u32(reinterpret_cast<const uint32_t*>(bps) + (q >> 1));
-      const int off = (q & 1) ? (int)(wd >> 16) : (int)(wd & 0xffffu);
-      const uint32_t pk = arc[idx[h].x + off].pk;
-      pd[t] = (int64_t)(pk >> 16);
-      h = (int)(pk & 0xffffu);
-      st[t] = h;
-    }
-  }
-#else
   // ---- backtrace over blocks of F frames from the end: iteration j, one barrier each:
   //   waves 1.. : backpointer rows of block j -> the winning arc's pk (src | pdf << 16) into tab[j & 1];
   //               the path of block j - 2 (path[j & 1]) out to states / pdfs, coalesced
@@ -356,7 +341,6 @@ __global__ __launch_bounds__(kAlNT + LD) void align_kernel(const AlignArgs a) {
     }
     __syncthreads();
   }
-#endif
 }
 
 // ------------------------------------------------------------------------------------

@@ -20,19 +20,11 @@ static_assert(PLAN_REC_WAVES <= 12 || (PLAN_RESIDENT_0 == 16 && PLAN_RESIDENT_1 
 // the two operands plus the arc probability (R = 0: everything is streamed from the
 // L2-resident plan).  The plan of a wave is loop-invariant over frames, so this is loaded
 // ONCE per workgroup and the per-frame inner loop touches only LDS.
-#ifndef PYCHAIN_ARC_PACKED
-#define PYCHAIN_ARC_PACKED (PLAN_REC_WAVES > 12)   // 16 waves: 128 VGPRs/lane -> 2 registers per slot-row
-#endif
+static_assert(PLAN_REC_WAVES > 12, "16 waves: 128 VGPRs/lane -> 2 registers per slot-row (the packed form below)");
 template <int R>
 struct ArcRegs {
-#if PYCHAIN_ARC_PACKED
   // 2 VGPRs per slot-row: both absolute LDS byte addresses packed 16:16, and the probability.
   uint32_t pk[R > 0 ? R : 1];
-#else
-  // 3 VGPRs per slot-row: the two absolute LDS byte addresses and the probability.
-  uint32_t o0[R > 0 ? R : 1];
-  uint32_t o1[R > 0 ? R : 1];
-#endif
   float p[R > 0 ? R : 1];
   __device__ __forceinline__ void load(const int nslot_rows, const uint2* __restrict__ wave_slots,
                                        uint32_t lds_u, uint32_t lds_v) {
@@ -41,15 +33,7 @@ struct ArcRegs {
       uint2 a = make_uint2(0u, 0u);                    // rows past the plan: p = 0, harmless addresses
       if (s < nslot_rows) a = wave_slots[s * 64];
       uint32_t a0 = lds_u + ((a.x & 0xffffu) << 2), a1 = lds_v + ((a.x >> 16) << 2);
-#ifdef PYCHAIN_EXP_NOCONFLICT      // timing experiment: lane-linear gathers (wrong results)
-      a0 = lds_u + (((threadIdx.x & 63) + 64 * (s & 7)) << 2); a1 = lds_v + (((threadIdx.x & 63) + 64 * (s & 7)) << 2);
-#endif
-#if PYCHAIN_ARC_PACKED
       pk[s] = a0 | (a1 << 16);
-#else
-      o0[s] = a0; o1[s] = a1;
-      asm volatile("" : "+v"(o0[s]), "+v"(o1[s]));    // opaque: no re-derivation from the packed word per frame
-#endif
       p[s] = __uint_as_float(a.y);
     }
   }
@@ -59,29 +43,17 @@ struct ArcRegs {
   // every inline asm costs a hazard s_nop.
   template <int N>
   __device__ __forceinline__ void opaque(int s) {
-#if PYCHAIN_ARC_PACKED
     if constexpr (N == 4) asm volatile("" : "+v"(pk[s]), "+v"(pk[s + 1]), "+v"(pk[s + 2]), "+v"(pk[s + 3]));
     else for (int k = 0; k < N; k++) asm volatile("" : "+v"(pk[s + k]));
-#endif
   }
   template <int VOFF = 0>         // VOFF: compile-time byte offset of operand V (folds into the ds_read offset field)
   __device__ __forceinline__ void gather(int s, float& u, float& v) {
-#if PYCHAIN_ARC_PACKED
     const uint32_t a0 = pk[s] & 0xffffu, a1 = pk[s] >> 16;
-#else
-    const uint32_t a0 = o0[s], a1 = o1[s];
-#endif
-#ifndef PYCHAIN_EXP_NOLDS
     u = lds_abs(a0); v = lds_abs(a1 + VOFF);
-#else
-    u = __uint_as_float(a0); v = __uint_as_float(a1);
-#endif
   }
 };
 
-#ifndef PYCHAIN_CHUNK
-#define PYCHAIN_CHUNK 4      // slot-rows gathered ahead per step of the software pipeline
-#endif
+constexpr int kChunk = 4;    // slot-rows gathered ahead per step of the software pipeline
 
 // The wave's group table lives in registers: lane i of `base` / `n` = output base and
 // slot-row count of the wave's i-th group (read back with v_readlane), `endmask` bit s =
@@ -115,10 +87,10 @@ struct GroupRegs {
       }
     }
     chunkmask = 0u;
-    for (int c = 0; c * PYCHAIN_CHUNK < 64; c++)
-      if ((endmask >> (c * PYCHAIN_CHUNK)) & ((1ull << PYCHAIN_CHUNK) - 1ull)) chunkmask |= 1u << c;
-    for (int c = 0; c * PYCHAIN_CHUNK < 32; c++)
-      if ((endmask2 >> (c * PYCHAIN_CHUNK)) & ((1u << PYCHAIN_CHUNK) - 1u)) chunkmask |= 1u << (c + 64 / PYCHAIN_CHUNK);
+    for (int c = 0; c * kChunk < 64; c++)
+      if ((endmask >> (c * kChunk)) & ((1ull << kChunk) - 1ull)) chunkmask |= 1u << c;
+    for (int c = 0; c * kChunk < 32; c++)
+      if ((endmask2 >> (c * kChunk)) & ((1u << kChunk) - 1u)) chunkmask |= 1u << (c + 64 / kChunk);
   }
 };
 
@@ -143,21 +115,10 @@ __device__ __forceinline__ void tile_store(float acc, int pos, float* __restrict
 // (measured per wave: 3000 / 4000 / 4700 / 5300 cycles; with this: recursion 4.02 -> 3.69 ms).
 template <int NC>
 __device__ __forceinline__ void wave_priority_by_progress(int c) {
-#ifndef PYCHAIN_EXP_NOPRIO
   // highest for the first half of the chunks, then stepping down to 0 on the last one (measured best of
   // four schedules: equal quarters 3.76 ms, front-loaded 3.78, this 3.69, two levels 3.84)
   constexpr int N = NC > 0 ? NC : 1;
-#if defined(PYCHAIN_PRIO_TABLE)                        /* experiments: eight hex digits, the level of each eighth of the chunks */
-  auto level = [](int cc) { return (int)((PYCHAIN_PRIO_TABLE >> (4 * (7 - cc * 8 / N))) & 0xfu); };
-#elif !defined(PYCHAIN_PRIO_SCHED) || PYCHAIN_PRIO_SCHED == 0
   auto level = [](int cc) { return cc * 2 / N == 0 ? 3 : max(0, 2 - (cc - N / 2) * 6 / N); };
-#elif PYCHAIN_PRIO_SCHED == 2                          /* experiments */
-  auto level = [](int cc) { return cc * 2 / N == 0 ? 0 : min(3, 1 + (cc - N / 2) * 6 / N); };
-#elif PYCHAIN_PRIO_SCHED == 3
-  auto level = [](int cc) { return cc * 4 / N >= 3 ? 0 : 3; };
-#else
-  auto level = [](int cc) { return 3 - cc * 4 / N; };
-#endif
   const int lvl = level(c), prev = c > 0 ? level(c - 1) : -1;
   if (NC >= 4 && lvl != prev) {
     switch (lvl) {                               // (s_setprio takes an immediate)
@@ -167,7 +128,21 @@ __device__ __forceinline__ void wave_priority_by_progress(int c) {
       default: __builtin_amdgcn_s_setprio(0); break;
     }
   }
-#endif
+}
+
+// The group-end bits of a wave's resident slot-rows as 32-bit words (GroupRegs::endmask / endmask2; loops of up to 32 or 64
+// slot-rows pass one or two).  `s` is a constant after unrolling: the word and the masks fold.
+__device__ __forceinline__ bool group_ends_at(int s, uint32_t m_lo, uint32_t m_hi = 0u, uint32_t m_2 = 0u) {
+  return (((s < 32 ? m_lo : (s < 64 ? m_hi : m_2)) >> (s & 31)) & 1u) != 0u;
+}
+// group index of slot-row s = number of group ends before it
+__device__ __forceinline__ int groups_before(int s, uint32_t m_lo, uint32_t m_hi = 0u, uint32_t m_2 = 0u) {
+  const uint32_t below = (1u << (s & 31)) - 1u;
+  const uint32_t lo_before = s < 32 ? (m_lo & below) : m_lo;
+  const uint32_t hi_before = s < 32 ? 0u : (s < 64 ? (m_hi & below) : m_hi);
+  int g = __builtin_popcount(lo_before) + __builtin_popcount(hi_before);
+  if (s >= 64) g += __builtin_popcount(m_2 & below);
+  return g;
 }
 
 // One frame of a tile plan.  The resident loop is written for instruction count (the arc phase
@@ -183,10 +158,6 @@ __device__ __forceinline__ void tile_rows(ArcRegs<R>& ar, const GroupRegs& gr,
                                           float* __restrict__ out, const int* __restrict__ row_map,
                                           const float* __restrict__ wvec, float& s0, float& s1) {
   float acc = 0.f;
-#ifndef PYCHAIN_CHUNK
-#define PYCHAIN_CHUNK 4
-#endif
-  constexpr int kChunk = PYCHAIN_CHUNK;
   static_assert(R % kChunk == 0 && 32 % kChunk == 0 && R <= 64, "whole chunks; a chunk never straddles the mask words");
   constexpr int NC = R / kChunk;
   // Opaque per call: otherwise the optimiser precomputes per-slot-row lane masks outside the
@@ -211,11 +182,9 @@ __device__ __forceinline__ void tile_rows(ArcRegs<R>& ar, const GroupRegs& gr,
 #pragma unroll
       for (int k = 0; k < kChunk; k++) ar.template gather<VOFF>((c + 1) * kChunk + k, ub[cb ^ 1][k], vb[cb ^ 1][k]);
     }
-#if !defined(PYCHAIN_EXP_NOLDS) && !defined(PYCHAIN_EXP_NOWAIT)
     __builtin_amdgcn_sched_barrier(0);
     if (c + 1 < NC) PYCHAIN_WAIT_LGKM(2 * kChunk); else PYCHAIN_WAIT_LGKM(0);
     __builtin_amdgcn_sched_barrier(0);
-#endif
     // the common case unconditionally; a chunk with a group end (a few per frame) redoes it
     float nacc = acc;
 #pragma unroll
@@ -226,12 +195,8 @@ __device__ __forceinline__ void tile_rows(ArcRegs<R>& ar, const GroupRegs& gr,
       for (int k = 0; k < kChunk; k++) {
         const int sidx = c * kChunk + k;
         nacc = fmaf(ar.p[sidx] * ub[cb][k], vb[cb][k], nacc);
-        if (((sidx < 32 ? m_lo : m_hi) >> (sidx & 31)) & 1u) {
-          // group index = number of group ends before this slot-row
-          const uint32_t lo_before = sidx < 32 ? (m_lo & ((1u << (sidx & 31)) - 1u)) : m_lo;
-          const uint32_t hi_before = sidx < 32 ? 0u : (m_hi & ((1u << (sidx & 31)) - 1u));
-          const int g = __builtin_popcount(lo_before) + __builtin_popcount(hi_before);
-          const int pos = __builtin_amdgcn_readlane(gr.base, g) + lane;
+        if (group_ends_at(sidx, m_lo, m_hi)) {
+          const int pos = __builtin_amdgcn_readlane(gr.base, groups_before(sidx, m_lo, m_hi)) + lane;
           tile_store<MODE>(nacc, pos, out, row_map);
           if constexpr (MODE == 0) {
             // row sums, updated IN PLACE (tied asm operands): a plain `s0 += nacc` makes s0/s1 loop-carried
@@ -341,7 +306,7 @@ hipError_t launch_one(K kern, const DenArgs& a, dim3 grid, size_t lds, hipStream
 // rows = slot-rows per wave the plan needs (0 = unknown: stream everything); plans larger
 // than kMaxResident keep the first kMaxResident rows in registers and stream their tail.
 inline int pick_r(const DenArgs& a, int rows, int lds_words) {
-  if (rows <= 0 || (PYCHAIN_ARC_PACKED && lds_words * 4 > 65535)) return 0;   // packed 16-bit LDS addresses
+  if (rows <= 0 || lds_words * 4 > 65535) return 0;   // packed 16-bit LDS addresses
   if (rows <= 16) return 16;
   if (rows <= 32) return 32;
   if (rows <= PLAN_RESIDENT_FIT && kMaxResident > PLAN_RESIDENT_FIT) return PLAN_RESIDENT_FIT;

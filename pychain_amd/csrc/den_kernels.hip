@@ -601,8 +601,7 @@ template <int R, typename Hook>
 __device__ __forceinline__ void tile_rows2(ArcRegs2<R>& ar, const GroupRegs& gr, const uint2* __restrict__ tail_slots,
                                            int lane, const float* __restrict__ U2, const float* __restrict__ V2,
                                            float* __restrict__ q2, const int* __restrict__ row_map, Hook hook) {
-  constexpr int kChunk = 4;
-  static_assert(R % kChunk == 0 && R <= 64 && PYCHAIN_CHUNK == 4, "chunk mask of GroupRegs is built for chunks of 4");
+  static_assert(R % kChunk == 0 && R <= 64, "whole chunks; a chunk never straddles the mask words");
   constexpr int NC = R / kChunk;
   v2f acc = {0.f, 0.f};
   uint32_t m_lo = (uint32_t)gr.endmask, m_hi = (uint32_t)(gr.endmask >> 32), cm = gr.chunkmask;
@@ -635,11 +634,8 @@ __device__ __forceinline__ void tile_rows2(ArcRegs2<R>& ar, const GroupRegs& gr,
       for (int k = 0; k < kChunk; k++) {
         const int sidx = c * kChunk + k;
         nacc = __builtin_elementwise_fma(scale2(ub[cb][k], ar.p[sidx]), vb[cb][k], nacc);
-        if (((sidx < 32 ? m_lo : m_hi) >> (sidx & 31)) & 1u) {
-          const uint32_t lo_before = sidx < 32 ? (m_lo & ((1u << (sidx & 31)) - 1u)) : m_lo;
-          const uint32_t hi_before = sidx < 32 ? 0u : (m_hi & ((1u << (sidx & 31)) - 1u));
-          const int g = __builtin_popcount(lo_before) + __builtin_popcount(hi_before);
-          tile_store2(nacc, __builtin_amdgcn_readlane(gr.base, g) + lane, q2, row_map);
+        if (group_ends_at(sidx, m_lo, m_hi)) {
+          tile_store2(nacc, __builtin_amdgcn_readlane(gr.base, groups_before(sidx, m_lo, m_hi)) + lane, q2, row_map);
           nacc = v2f{0.f, 0.f};
         }
       }

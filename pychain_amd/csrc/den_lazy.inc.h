@@ -133,24 +133,6 @@ __device__ __forceinline__ void lz_st1(uint32_t byte_addr, float v) { *(lz_lds_f
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Wint-to-pointer-cast"
 typedef __attribute__((address_space(3))) void lz_lds_void;
-#ifndef PYCHAIN_LATE_BACK
-#define PYCHAIN_LATE_BACK 2                            /* the late hook of lazy_tile runs this many chunks before the end of the arc phase */
-#endif
-#ifndef PYCHAIN_Q_REDO
-#define PYCHAIN_Q_REDO 1                                /* group ends of the one-word form: 1 row by row, 2 pair by pair (packed) */
-#endif
-#ifndef PYCHAIN_Q_ALPHA
-#define PYCHAIN_Q_ALPHA 1                               /* 0: one-word state vectors in the beta recursions only */
-#endif
-#ifndef PYCHAIN_Q_ASMLK
-#define PYCHAIN_Q_ASMLK 0                               /* the group ends' LDS operand requested with an instruction the compiler does not count */
-#endif
-#ifndef PYCHAIN_XF_EXP
-#define PYCHAIN_XF_EXP 0                               /* timing experiments on the crossing (WRONG RESULTS): 1 no adds, 2 no flush, 4 no landing rows, 8 no emission, 16 no totals */
-#endif
-#ifndef PYCHAIN_EXP_NO_ROWSTORE
-#define PYCHAIN_EXP_NO_ROWSTORE 0                      /* timing experiments (WRONG RESULTS): 1 = the rows do not leave for HBM, 2 = they do, but are not re-read from LDS first */
-#endif
 typedef float lz_v4 __attribute__((ext_vector_type(4)));
 #define PYCHAIN_WAIT_VM0() __builtin_amdgcn_s_waitcnt(0x0F70)     /* vmcnt(0) only (gfx9 encoding) */
 // row t of the sequence behind `buf` -> LDS at byte address xbase, 1 KiB chunks dealt to the NW waves; lanes past the
@@ -183,9 +165,6 @@ template <int NW, int NCH>
 __device__ __forceinline__ bool lz_dma_finish(int D, int wave, int lane, uint32_t xbase, int is_exp) {
   bool nan = false;
   PYCHAIN_WAIT_VM0();                                   // this wave's loads have landed
-#ifdef PYCHAIN_EXP_NO_FINISH                            /* timing experiment (WRONG RESULTS): the rows are gathered as they arrived */
-  return false;
-#endif
 #pragma unroll
   for (int c = 0; c < NCH; c++) {
     const int ch = wave + c * NW;
@@ -198,7 +177,6 @@ __device__ __forceinline__ bool lz_dma_finish(int D, int wave, int lane, uint32_
         const int e = ch * 256 + lane * 4;
         nan = nan || (e < D && q.x != q.x) || (e + 1 < D && q.y != q.y) || (e + 2 < D && q.z != q.z) || (e + 3 < D && q.w != q.w);
       }
-#if PYCHAIN_EXP_OPS == 2
       if (is_exp == kXExpClamp) {
         // (clamp_exp element by element, the product with log2 e as two v_pk_mul_f32: the same bits, two VALU instructions less
         // per wave and frame - each one is ~0.5 % of a frame that sits on its VALU issue)
@@ -207,9 +185,6 @@ __device__ __forceinline__ bool lz_dma_finish(int D, int wave, int lane, uint32_
         const lz_v2f t1 = lz_v2f{__builtin_amdgcn_fmed3f(q.z, -30.f, 30.f), __builtin_amdgcn_fmed3f(q.w, -30.f, 30.f)} * l2e;
         q = lz_v4{__builtin_amdgcn_exp2f(t0.x), __builtin_amdgcn_exp2f(t0.y), __builtin_amdgcn_exp2f(t1.x), __builtin_amdgcn_exp2f(t1.y)};
       }
-#else
-      if (is_exp == kXExpClamp) q = lz_v4{clamp_exp(q.x, kXExpClamp), clamp_exp(q.y, kXExpClamp), clamp_exp(q.z, kXExpClamp), clamp_exp(q.w, kXExpClamp)};
-#endif
       *(__attribute__((address_space(3))) lz_v4*)(addr) = q;
     }
   }
@@ -321,11 +296,9 @@ struct LazyArcsSplit {
   }
 };
 template <int R, typename MAP> struct LazyArcsOf { typedef LazyArcs<R, MAP> type; };
-#ifndef PYCHAIN_NO_SPLIT_ARCS
 template <typename MAP> struct LazyArcsOf<16, MAP> { typedef LazyArcsSplit<16, MAP> type; };
 template <typename MAP> struct LazyArcsOf<32, MAP> { typedef LazyArcsSplit<32, MAP> type; };
 template <typename MAP> struct LazyArcsOf<24, MAP> { typedef LazyArcsSplit<24, MAP> type; };     // (the four-wave shape: launch_small)
-#endif
 
 // One-word state vectors (MAP::kQ): the split form with a b32 state address; alpha's probabilities are q_k = p_k cl(src_k).
 template <int R, typename MAP>
@@ -415,18 +388,39 @@ __device__ __forceinline__ float lazy_group_end(const LazyWave& w, lz_v2f acc, u
   return val;
 }
 
+// The two hooks of a lazy frame, behind the gathers of a chunk: the previous frame's totals (w.inv, w.c: first needed at the
+// first group end) are reduced behind the gathers of the first two chunks, instead of between the barrier and the first
+// gather; the next frame's nnet-output row (lazy_recursion) late in the arc phase.
+constexpr int kLateBack = 2;       // the late hook runs this many chunks before the end of the arc phase
+constexpr int lazy_late_chunk(int nc) { return nc >= 4 ? nc - kLateBack : nc - 1; }
+// A group end of the two-word forms (LazyArcs, LazyArcsSplit): row `g` of the wave takes its value; returns the accumulator
+// of the next row.
+template <typename MAP, bool FWD, uint32_t UNEXT>
+__device__ __forceinline__ lz_v2f lazy_row_end(const GroupRegs& gr, LazyWave& w, int lane, int g, lz_v2f nacc, float& s0, float& s1) {
+  const uint32_t pos = (uint32_t)(__builtin_amdgcn_readlane(gr.base, g) + lane);
+  const float val = lazy_group_end<FWD>(w, nacc, UNEXT + pos * 8u);
+  s0 += val;                                           // the wave's share of the frame's totals, where the value is formed
+  // (beta's leaky probabilities in four registers instead of this LDS read: two spills, recursion +6 %: r04_p_*)
+  if constexpr (!FWD) {
+    if constexpr (MAP::kMaxPdfs <= 4096) {             // (requested one group end ahead: LazyWave::lk_next)
+      s1 = __builtin_fmaf(val, w.lk_next, s1);
+      w.lk_next = lds_abs(MAP::kLk + (uint32_t)(__builtin_amdgcn_readlane(gr.base, (g + 1) & 63) + lane) * 4u);
+    } else {
+      s1 = __builtin_fmaf(val, lds_abs(MAP::kLk + pos * 4u), s1);
+    }
+  }
+  return lz_v2f{0.f, 0.f};
+}
 // One frame of a recursion tile, lazy form: gathers from the state buffer at ds_read offset UOFF and the nnet-output
 // buffer at VOFF, writes the new values into the state buffer at absolute address UNEXT.  Same software pipeline as
 // tile_rows; up to 96 slot-rows per wave (three words of group-end bits).
 template <int R, typename MAP, bool FWD, uint32_t UOFF, uint32_t VOFF, uint32_t UNEXT, typename Hook, typename Late>
 __device__ __forceinline__ void lazy_tile(LazyArcs<R, MAP>& ar, const GroupRegs& gr, LazyWave& w, int lane, float& s0, float& s1, Hook&& after_first_gathers, Late&& late) {
-  constexpr int kChunk = 4;
-  static_assert(R % kChunk == 0 && R <= 96 && PYCHAIN_CHUNK == 4, "chunk mask of GroupRegs is built for chunks of 4");
-  constexpr int NC = R / kChunk;
-  constexpr int kLateChunk = NC >= 4 ? NC - PYCHAIN_LATE_BACK : NC - 1;
+  static_assert(R % kChunk == 0 && R <= 96, "whole chunks; three words of group-end bits");
   uint32_t m_lo = (uint32_t)gr.endmask, m_hi = (uint32_t)(gr.endmask >> 32), m_2 = gr.endmask2, cm = gr.chunkmask;
   if constexpr (R > 64) asm volatile("" : "+s"(m_lo), "+s"(m_hi), "+s"(m_2), "+s"(cm));
   else asm volatile("" : "+s"(m_lo), "+s"(m_hi), "+s"(cm));
+  constexpr int NC = R / kChunk;
   lz_v2f acc = {0.f, 0.f};
   lz_v2f ub[2][kChunk];
   float vb[2][kChunk];
@@ -442,10 +436,8 @@ __device__ __forceinline__ void lazy_tile(LazyArcs<R, MAP>& ar, const GroupRegs&
 #pragma unroll
       for (int k = 0; k < kChunk; k++) ar.template gather<UOFF, VOFF>((c + 1) * kChunk + k, ub[cb ^ 1][k], vb[cb ^ 1][k]);
     }
-    // the previous frame's totals (w.inv, w.c: first needed at the first group end) are reduced HERE, behind the
-    // gathers of the first two chunks, instead of between the barrier and the first gather
     if (c == 0) after_first_gathers();
-    if (c == kLateChunk) late();                       // (the next frame's nnet-output row: lazy_recursion)
+    if (c == lazy_late_chunk(NC)) late();
     __builtin_amdgcn_sched_barrier(0);
     if (c + 1 < NC) PYCHAIN_WAIT_LGKM(2 * kChunk); else PYCHAIN_WAIT_LGKM(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -462,29 +454,8 @@ __device__ __forceinline__ void lazy_tile(LazyArcs<R, MAP>& ar, const GroupRegs&
         const int sidx = c * kChunk + k;
         const float wk = ar.p[sidx] * vb[cb][k];
         nacc = __builtin_elementwise_fma(lz_v2f{wk, wk}, ub[cb][k], nacc);
-        const uint32_t mword = sidx < 32 ? m_lo : (sidx < 64 ? m_hi : m_2);
-        if ((mword >> (sidx & 31)) & 1u) {
-          const uint32_t below = (1u << (sidx & 31)) - 1u;
-          const uint32_t lo_before = sidx < 32 ? (m_lo & below) : m_lo;
-          const uint32_t hi_before = sidx < 32 ? 0u : (sidx < 64 ? (m_hi & below) : m_hi);
-          int g = __builtin_popcount(lo_before) + __builtin_popcount(hi_before);
-          if constexpr (R > 64) if (sidx >= 64) g += __builtin_popcount(m_2 & below);
-          const uint32_t pos = (uint32_t)(__builtin_amdgcn_readlane(gr.base, g) + lane);
-          const float val = lazy_group_end<FWD>(w, nacc, UNEXT + pos * 8u);
-          {                                              // the wave's share of the frame's totals, where the value is formed
-            s0 += val;
-            // (beta's leaky probabilities in four registers instead of this LDS read: two spills, recursion +6 %: r04_p_*)
-            if constexpr (!FWD) {
-              if constexpr (MAP::kMaxPdfs <= 4096) {                 // (requested one group end ahead: LazyWave::lk_next)
-                s1 = __builtin_fmaf(val, w.lk_next, s1);
-                w.lk_next = lds_abs(MAP::kLk + (uint32_t)(__builtin_amdgcn_readlane(gr.base, (g + 1) & 63) + lane) * 4u);
-              } else {
-                s1 = __builtin_fmaf(val, lds_abs(MAP::kLk + pos * 4u), s1);
-              }
-            }
-          }
-          nacc = lz_v2f{0.f, 0.f};
-        }
+        if (group_ends_at(sidx, m_lo, m_hi, m_2))
+          nacc = lazy_row_end<MAP, FWD, UNEXT>(gr, w, lane, groups_before(sidx, m_lo, m_hi, m_2), nacc, s0, s1);
       }
     }
     acc = nacc;
@@ -494,15 +465,12 @@ __device__ __forceinline__ void lazy_tile(LazyArcs<R, MAP>& ar, const GroupRegs&
 // ... and over arcs in the split form (LazyArcsSplit): rows in pairs
 template <int R, typename MAP, bool FWD, uint32_t UOFF, uint32_t VOFF, uint32_t UNEXT, typename Hook, typename Late>
 __device__ __forceinline__ void lazy_tile(LazyArcsSplit<R, MAP>& ar, const GroupRegs& gr, LazyWave& w, int lane, float& s0, float& s1, Hook&& after_first_gathers, Late&& late) {
-  constexpr int kChunk = 4;
-  static_assert(PYCHAIN_CHUNK == 4, "chunk mask of GroupRegs is built for chunks of 4");
-  constexpr int NC = R / kChunk;
-  constexpr int kLateChunk = NC >= 4 ? NC - PYCHAIN_LATE_BACK : NC - 1;
   uint32_t m_lo = (uint32_t)gr.endmask, cm = gr.chunkmask;
   asm volatile("" : "+s"(m_lo), "+s"(cm));
   lz_v2f acc = {0.f, 0.f};
   lz_v2f ub[2][kChunk];
   lz_v2f vb[2][kChunk / 2];
+  constexpr int NC = R / kChunk;
   ar.opaque4(0);
 #pragma unroll
   for (int k = 0; k < kChunk; k += 2) ar.template gather2<UOFF, VOFF>(k, ub[0][k], ub[0][k + 1], vb[0][k / 2]);
@@ -517,7 +485,7 @@ __device__ __forceinline__ void lazy_tile(LazyArcsSplit<R, MAP>& ar, const Group
         ar.template gather2<UOFF, VOFF>((c + 1) * kChunk + k, ub[cb ^ 1][k], ub[cb ^ 1][k + 1], vb[cb ^ 1][k / 2]);
     }
     if (c == 0) after_first_gathers();
-    if (c == kLateChunk) late();                       // (the next frame's nnet-output row: lazy_recursion)
+    if (c == lazy_late_chunk(NC)) late();
     __builtin_amdgcn_sched_barrier(0);
     if (c + 1 < NC) PYCHAIN_WAIT_LGKM(2 * kChunk); else PYCHAIN_WAIT_LGKM(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -537,24 +505,7 @@ __device__ __forceinline__ void lazy_tile(LazyArcsSplit<R, MAP>& ar, const Group
         const int sidx = c * kChunk + k;
         const float x = (k & 1) ? wk[k / 2].y : wk[k / 2].x;
         nacc = __builtin_elementwise_fma(lz_v2f{x, x}, ub[cb][k], nacc);
-        if ((m_lo >> sidx) & 1u) {
-          const int g = __builtin_popcount(m_lo & ((1u << sidx) - 1u));
-          const uint32_t pos = (uint32_t)(__builtin_amdgcn_readlane(gr.base, g) + lane);
-          const float val = lazy_group_end<FWD>(w, nacc, UNEXT + pos * 8u);
-          {                                              // the wave's share of the frame's totals, where the value is formed
-            s0 += val;
-            // (beta's leaky probabilities in four registers instead of this LDS read: two spills, recursion +6 %: r04_p_*)
-            if constexpr (!FWD) {
-              if constexpr (MAP::kMaxPdfs <= 4096) {                 // (requested one group end ahead: LazyWave::lk_next)
-                s1 = __builtin_fmaf(val, w.lk_next, s1);
-                w.lk_next = lds_abs(MAP::kLk + (uint32_t)(__builtin_amdgcn_readlane(gr.base, (g + 1) & 63) + lane) * 4u);
-              } else {
-                s1 = __builtin_fmaf(val, lds_abs(MAP::kLk + pos * 4u), s1);
-              }
-            }
-          }
-          nacc = lz_v2f{0.f, 0.f};
-        }
+        if (group_ends_at(sidx, m_lo)) nacc = lazy_row_end<MAP, FWD, UNEXT>(gr, w, lane, groups_before(sidx, m_lo), nacc, s0, s1);
       }
     }
     acc = nacc;
@@ -565,10 +516,7 @@ __device__ __forceinline__ void lazy_tile(LazyArcsSplit<R, MAP>& ar, const Group
 // {acc2.x, acc2.y} - a row's sums are the halves added up where its group ends
 template <int R, typename MAP, bool FWD, uint32_t UOFF, uint32_t VOFF, uint32_t UNEXT, typename Hook, typename Late>
 __device__ __forceinline__ void lazy_tile(LazyArcsQ<R, MAP>& ar, const GroupRegs& gr, LazyWave& w, int lane, float& s0, float& s1, Hook&& after_first_gathers, Late&& late) {
-  constexpr int kChunk = 4;
-  static_assert(PYCHAIN_CHUNK == 4, "chunk mask of GroupRegs is built for chunks of 4");
   constexpr int NC = R / kChunk;
-  constexpr int kLateChunk = NC >= 4 ? NC - PYCHAIN_LATE_BACK : NC - 1;
   uint32_t m_lo = (uint32_t)gr.endmask, cm = gr.chunkmask;
   asm volatile("" : "+s"(m_lo), "+s"(cm));
   lz_v2f acc1 = {0.f, 0.f}, acc2 = {0.f, 0.f};
@@ -588,7 +536,7 @@ __device__ __forceinline__ void lazy_tile(LazyArcsQ<R, MAP>& ar, const GroupRegs
         ar.template gather2<UOFF, VOFF>((c + 1) * kChunk + k, ub[cb ^ 1][k / 2], vb[cb ^ 1][k / 2]);
     }
     if (c == 0) after_first_gathers();
-    if (c == kLateChunk) late();                       // (the next frame's nnet-output row: lazy_recursion)
+    if (c == lazy_late_chunk(NC)) late();
     __builtin_amdgcn_sched_barrier(0);
     if (c + 1 < NC) PYCHAIN_WAIT_LGKM(2 * kChunk); else PYCHAIN_WAIT_LGKM(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -602,13 +550,9 @@ __device__ __forceinline__ void lazy_tile(LazyArcsQ<R, MAP>& ar, const GroupRegs
       n2 = n2 + wk[k];
     }
     if (__builtin_expect(((cm >> c) & 1u) != 0u, 0)) {         // a chunk with a group end (about every other chunk of a C3 wave)
-      bool lk_fresh = false;                                   // (a second group end in this chunk: its operand was requested in it)
       auto group_end = [&](int sidx, float r1, float r2) {
-        const int g = __builtin_popcount(m_lo & ((1u << sidx) - 1u));
+        const int g = groups_before(sidx, m_lo);
         const uint32_t pos = (uint32_t)(__builtin_amdgcn_readlane(gr.base, g) + lane);
-#if PYCHAIN_Q_ASMLK
-        if (lk_fresh) PYCHAIN_WAIT_LGKM(0);
-#endif
         float val;
         if constexpr (FWD) {
           val = __builtin_fmaf(r1, w.inv, r2);
@@ -622,36 +566,8 @@ __device__ __forceinline__ void lazy_tile(LazyArcsQ<R, MAP>& ar, const GroupRegs
         }
         // (alpha: 1 / cl, beta: the leaky probability - of the lane's row in the group whose end comes next)
         const uint32_t lka = MAP::kLk + (uint32_t)(__builtin_amdgcn_readlane(gr.base, (g + 1) & 63) + lane) * 4u;
-#if PYCHAIN_Q_ASMLK
-        // Requested with an instruction the compiler does not count: it would wait for EVERY LDS operation in flight - the next
-        // chunk's gathers - before the next group end reads it, although the wait at the top of that chunk's arithmetic (all but
-        // the gathers issued after this) has long covered it.  (An uncounted operation in the queue only makes the compiler's
-        // own waits wait for one more.)
-        asm volatile("ds_read_b32 %0, %1" : "=v"(w.lk_next) : "v"(lka) : "memory");
-        lk_fresh = true;
-#else
         w.lk_next = lds_abs(lka);
-        (void)lk_fresh;
-#endif
       };
-#if PYCHAIN_Q_REDO == 2
-      n1 = acc1; n2 = acc2;
-#pragma unroll
-      for (int kp = 0; kp < kChunk / 2; kp++) {
-        const int se = c * kChunk + 2 * kp;
-        const bool e0 = ((m_lo >> se) & 1u) != 0u, e1 = ((m_lo >> (se + 1)) & 1u) != 0u;   // (uniform)
-        if (!e0) {
-          n1 = __builtin_elementwise_fma(wk[kp], ub[cb][kp], n1);
-          n2 = n2 + wk[kp];
-          if (e1) { group_end(se + 1, n1.x + n1.y, n2.x + n2.y); n1 = lz_v2f{0.f, 0.f}; n2 = lz_v2f{0.f, 0.f}; }
-        } else {
-          group_end(se, __builtin_fmaf(wk[kp].x, ub[cb][kp].x, n1.x + n1.y), n2.x + n2.y + wk[kp].x);
-          const float o1 = wk[kp].y * ub[cb][kp].y, o2 = wk[kp].y;
-          if (e1) { group_end(se + 1, o1, o2); n1 = lz_v2f{0.f, 0.f}; n2 = lz_v2f{0.f, 0.f}; }
-          else { n1 = lz_v2f{0.f, o1}; n2 = lz_v2f{0.f, o2}; }
-        }
-      }
-#else
       float r1 = acc1.x + acc1.y, r2 = acc2.x + acc2.y;
 #pragma unroll
       for (int k = 0; k < kChunk; k++) {
@@ -660,28 +576,23 @@ __device__ __forceinline__ void lazy_tile(LazyArcsQ<R, MAP>& ar, const GroupRegs
         const float u = (k & 1) ? ub[cb][k / 2].y : ub[cb][k / 2].x;
         r1 = __builtin_fmaf(x, u, r1);
         r2 += x;
-        if ((m_lo >> sidx) & 1u) { group_end(sidx, r1, r2); r1 = 0.f; r2 = 0.f; }
+        if (group_ends_at(sidx, m_lo)) { group_end(sidx, r1, r2); r1 = 0.f; r2 = 0.f; }
       }
       n1 = lz_v2f{r1, 0.f}; n2 = lz_v2f{r2, 0.f};
-#endif
     }
     acc1 = n1; acc2 = n2;
   }
 }
 
-#ifndef PYCHAIN_SG_AHEAD
-#define PYCHAIN_SG_AHEAD 2                             /* chunks the gathers of the one-gather loop run ahead of its arithmetic (measured: 1, 2, 3 alike) */
-#endif
+constexpr int kSgAhead = 2;        // chunks the gathers of the one-gather loop run ahead of its arithmetic (measured: 1, 2, 3 alike)
 // ... and over arcs of a "pdf by state" plan (LazyArcsState): ONE gather per arc.  xad01 / xad23 = absolute LDS addresses (nnet-output
 // field, 16 bits each) of the pdf of this lane's row in the wave's groups 0 | 1 << 16, 2 | 3 << 16; XOFF = ds_read offset of the
 // row buffer the group ends read.
 template <int R, typename MAP, bool FWD, uint32_t UOFF, uint32_t XOFF, uint32_t UNEXT, int AHEAD, typename Hook, typename Late>
 __device__ __forceinline__ void lazy_tile_sg(LazyArcsState<R, MAP>& ar, const GroupRegs& gr, LazyWave& w, const uint32_t xad01, const uint32_t xad23, int lane,
                                              float& s0, float& s1, Hook&& after_first_gathers, Late&& late) {
-  constexpr int kChunk = 4;
-  static_assert(PYCHAIN_CHUNK == 4, "chunk mask of GroupRegs is built for chunks of 4");
   constexpr int NC = R / kChunk;
-  constexpr int kLateChunk = NC >= 4 ? NC - PYCHAIN_LATE_BACK : NC - 1;
+  constexpr int kLateChunk = lazy_late_chunk(NC);
   uint32_t m_lo = (uint32_t)gr.endmask, m_hi = (uint32_t)(gr.endmask >> 32), cm = gr.chunkmask;
   asm volatile("" : "+s"(m_lo), "+s"(m_hi), "+s"(cm));
   lz_v2f acc = {0.f, 0.f};
@@ -729,10 +640,8 @@ __device__ __forceinline__ void lazy_tile_sg(LazyArcsState<R, MAP>& ar, const Gr
         const lz_v2f pq = ar.pp[sidx / 2];
         const float p = (k & 1) ? pq.y : pq.x;
         nacc = __builtin_elementwise_fma(lz_v2f{p, p}, ub[cb][k], nacc);
-        const uint32_t mword = sidx < 32 ? m_lo : m_hi;
-        if ((mword >> (sidx & 31)) & 1u) {
-          const uint32_t below = (1u << (sidx & 31)) - 1u;
-          const int g = __builtin_popcount(sidx < 32 ? (m_lo & below) : m_lo) + (sidx < 32 ? 0 : __builtin_popcount(m_hi & below));
+        if (group_ends_at(sidx, m_lo, m_hi)) {
+          const int g = groups_before(sidx, m_lo, m_hi);
           const uint32_t pos = (uint32_t)(__builtin_amdgcn_readlane(gr.base, g) + lane);
           const float xj = w.x_next;
           float val;
@@ -778,7 +687,7 @@ template <int R, typename MAP, bool fwd, int XM, bool TS, bool NC, bool SG = fal
 __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw, const int b, const int seg_in = 0) {
   static_assert(!XF || SG, "crossing: pdf-by-state plans");
   constexpr bool PRE = XM == kLzRowsPre, XH = XM == kLzRowsHalf;
-  constexpr bool kQd = MAP::kQ && (PYCHAIN_Q_ALPHA || !fwd);   // one-word state vectors in this direction
+  constexpr bool kQd = MAP::kQ;   // one-word state vectors (alpha and beta alike)
   static_assert(!SG || (MAP::kDma && MAP::kMaxPdfs <= 4096 && !NC && !PRE), "the one-gather form: LDS-direct rows, <= 4096 pdfs, no split beta positions");
   constexpr int NW = MAP::kWaves, NT = NW * 64, MG = MAP::kMaxGroups;
   const int tid = threadIdx.x;
@@ -993,7 +902,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
     const bool emit = xf_emits(tfr), dry = fwd ? tfr == xMa - 1 : tfr == xMb;
     const int tprev = fwd ? tfr - 1 : tfr + 1;           // the row of the step before: emitted => its accumulators leave now
     const bool flush = xf_emits(tprev) && !(fwd && tprev < f0) ;
-    if (!(emit || dry || flush) || (PYCHAIN_XF_EXP & 8)) return;
+    if (!(emit || dry || flush)) return;
     XF_T0();
     const uint32_t land = par ? LzCross::kLand1 : LzCross::kLand0;
     const uint32_t acc = par ? LzCross::kA1 : LzCross::kA0, acc_prev = par ? LzCross::kA0 : LzCross::kA1;
@@ -1012,7 +921,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
     const float ot = lds_abs(LzCross::kOtot + 4u * (uint32_t)par);
     const float pred_prev = lds_abs(LzCross::kPred + 4u * (uint32_t)(par ^ 1));
     const float gscale = lds_abs(LzCross::kScale);
-    const bool fl = flush && tq_ * 4 < D && !(PYCHAIN_XF_EXP & 2);
+    const bool fl = flush && tq_ * 4 < D;
     u32x4 fv = u32x4{0u, 0u, 0u, 0u};
     if (fl) fv = *(const __attribute__((address_space(3))) u32x4*)(acc_prev + 16u * (uint32_t)tq_);
     lz_v2f ex = lz_v2f{0.f, 0.f};
@@ -1032,7 +941,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
           const float rowv = fwd ? pr[g].x : __builtin_fmaf(pr[g].x, __builtin_amdgcn_rcpf(pr[g].y), w.sprev);
           const float pq = rowv * ld[g];
           gs += pq;
-          if (emit && !(PYCHAIN_XF_EXP & 1)) xf_add(xaddr(g) + (acc - LzCross::kXField), (uint32_t)__builtin_fmaf(pq, sc, 0.5f));
+          if (emit) xf_add(xaddr(g) + (acc - LzCross::kXField), (uint32_t)__builtin_fmaf(pq, sc, 0.5f));
         }
       }
       if constexpr (!fwd) {
@@ -1042,7 +951,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
             const uint32_t e0 = __float_as_uint(ex.x), e1 = __float_as_uint(ex.y);
             const lz_v2f pe = lz_ld2(ucur + (e0 & 0xffffu));
             pq = __builtin_fmaf(pe.x, __builtin_amdgcn_rcpf(pe.y), w.sprev) * lds_abs(land + (e0 >> 16));
-            if (emit && !(PYCHAIN_XF_EXP & 1)) xf_add(acc + e1, (uint32_t)__builtin_fmaf(pq, sc, 0.5f));
+            if (emit) xf_add(acc + e1, (uint32_t)__builtin_fmaf(pq, sc, 0.5f));
           }
           gs += pq;
         }
@@ -1078,10 +987,10 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
       }
     }
     const int row = fwd ? tnx + 1 : tnx;                   // beta row / alpha-store index
-    if (!(PYCHAIN_XF_EXP & 4)) lz_dma_row<NW, ((int)LzCross::kMaxStates / 256 + NW - 1) / NW, kStoreDeviceScope>(xf_obuf, row, Hp, wave, lq_, ((j + 1) & 1) ? LzCross::kLand1 : LzCross::kLand0);
+    lz_dma_row<NW, ((int)LzCross::kMaxStates / 256 + NW - 1) / NW, kStoreDeviceScope>(xf_obuf, row, Hp, wave, lq_, ((j + 1) & 1) ? LzCross::kLand1 : LzCross::kLand0);
     // ... and its total, by the same route: a load into a REGISTER would be waited for where the compiler next touches the register -
     // at the top of the arc phase, with every row just requested in flight (measured: +1 ms per call)
-    if (!(PYCHAIN_XF_EXP & 16) && wave == 0 && lq_ == 0)
+    if (wave == 0 && lq_ == 0)
       __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xf_ototv + tnx + 1),
                                        (lz_lds_void*)(LzCross::kOtot + (((j + 1) & 1) ? 4u : 0u)), 4, 0, kStoreDeviceScope);
   };
@@ -1235,9 +1144,6 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
     /* profiles/r04_n_*; registers: live exactly as long as in the hook before) */                          \
     float pre0 = 0.f, pre1 = 0.f;                                                                           \
     if (j > 0) { pre0 = red[((PAR) ^ 1) * 128 + lq]; if (!(FWDC)) pre1 = red[((PAR) ^ 1) * 128 + 64 + lq]; } \
-    if constexpr (kQd && PYCHAIN_Q_ASMLK) {                /* (uncounted, like the group ends' own requests: lazy_tile) */ \
-      asm volatile("ds_read_b32 %0, %1" : "=v"(w.lk_next) : "v"((uint32_t)(MAP::kLk + gbase[0] * 4 + lq * 4)) : "memory"); \
-    } else                                                                                                  \
     if constexpr (MAP::kMaxPdfs <= 4096 && (!(FWDC) || kQd)) w.lk_next = lds_abs(MAP::kLk + gbase[0] * 4 + lq * 4);   \
     constexpr bool kPreRows = MAP::kMaxPdfs <= 4096 && !(XF);       /* (the map of C4 has no registers to spare: the rows are read in the hook) */ \
     lz_v2f prow[MG];                                                                                        \
@@ -1271,7 +1177,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
       if constexpr (XF) xf_totb = tot_before;                /* (the crossing's share of this row: the step's tail) */ \
       LZ_HK(6);                                                                                             \
       _Pragma("unroll") for (int g = 0; g < MG; g++) {                                                      \
-        if (g < groups.ngroups && PYCHAIN_EXP_NO_ROWSTORE != 1 && !((SG) && (FWDC) && j == 0)) {            \
+        if (g < groups.ngroups && !((SG) && (FWDC) && j == 0)) {                                            \
           const lz_v2f pr = kPreRows ? prow[g] : lz_ld2(UCUR + gbase[g] * 8 + lq * 8);                      \
           /* (SG beta: the buffer holds x {b, 1}: b + c = pr.x / pr.y + c) */                                  \
           /* (one-word states: alpha's buffer holds a / cl, the row is cl (a / cl + tot); beta's b, the row b + c) */ \
@@ -1295,7 +1201,7 @@ __device__ __forceinline__ void lazy_recursion(const DenArgs& a, char* smem_raw,
         if constexpr (XF) { if (!have_next) PYCHAIN_WAIT_VM0(); }                                           \
       }                                                                                                     \
     };                                                                                                      \
-    if constexpr (SG) lazy_tile_sg<R, MAP, (FWDC), UOFF, VOFF, UNEXT, (XF) ? 1 : PYCHAIN_SG_AHEAD>(arcs, groups, w, xad01, xad23, lq, s0, s1, hook_first, hook_late); \
+    if constexpr (SG) lazy_tile_sg<R, MAP, (FWDC), UOFF, VOFF, UNEXT, (XF) ? 1 : kSgAhead>(arcs, groups, w, xad01, xad23, lq, s0, s1, hook_first, hook_late); \
     else lazy_tile<R, MAP, (FWDC), UOFF, VOFF, UNEXT>(arcs, groups, w, lq, s0, s1, hook_first, hook_late);  \
     LZ_PH(0);                                                /* arc phase */                                 \
     /* rows through registers: the next step's nnet-output row into the other buffer (last read in the previous step) */ \

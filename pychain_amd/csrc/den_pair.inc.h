@@ -111,11 +111,8 @@ __device__ __forceinline__ void pair_tile(PairArcs<R>& ar, const GroupRegs& gr, 
           pu = lz_v2f{pp, pp} * ub[cb][k];
         }
         nacc = __builtin_elementwise_fma(pu, vb[cb][k], nacc);
-        if (((sidx < 32 ? m_lo : m_hi) >> (sidx & 31)) & 1u) {
-          const uint32_t lo_before = sidx < 32 ? (m_lo & ((1u << (sidx & 31)) - 1u)) : m_lo;
-          const uint32_t hi_before = sidx < 32 ? 0u : (m_hi & ((1u << (sidx & 31)) - 1u));
-          const int g = __builtin_popcount(lo_before) + __builtin_popcount(hi_before);
-          const int pos = __builtin_amdgcn_readlane(gr.base, g) + lane;
+        if (group_ends_at(sidx, m_lo, m_hi)) {
+          const int pos = __builtin_amdgcn_readlane(gr.base, groups_before(sidx, m_lo, m_hi)) + lane;
           lz_st2(kPrRaw + (uint32_t)pos * 8u, nacc);
           {
 #pragma clang fp contract(off)

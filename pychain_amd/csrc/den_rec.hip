@@ -35,9 +35,6 @@ __global__ __launch_bounds__(kNT) void den_recursion_kernel(const DenArgs a) {
   const int L = __builtin_amdgcn_readfirstlane(seq_len(a.lengths, b, a.T));
   const int nsteps = fwd ? L : L - 1;
   const int j_begin = 0, j_end = nsteps;             // (the whole sequence in one launch)
-#ifdef PYCHAIN_EXP_ONLY_DIR                          // timing experiment: 0 = alpha workgroups only, 1 = beta only
-  if ((int)fwd == PYCHAIN_EXP_ONLY_DIR) return;
-#endif
   const int Hp = a.Hp, H = a.H, D = a.D, Dp = (D + 3) & ~3;
   const char* plan = a.plans + (size_t)b * a.plan_stride;
   const PlanHeader* hd = reinterpret_cast<const PlanHeader*>(plan);
@@ -130,20 +127,17 @@ __global__ __launch_bounds__(kNT) void den_recursion_kernel(const DenArgs a) {
     const int tn = fwd ? j + 1 : L - 2 - j;          /* nnet-output row of the NEXT step */                \
     const bool have_next = fwd ? (tn < L) : (tn >= 1);                                                      \
     const float* xrow_next = xseq + (size_t)(have_next ? tn : 0) * D;                                       \
-    if (kWithX && have_next) {                       /* in flight during the arc work */                    \
+    if (have_next) {                                 /* in flight during the arc work */                    \
       if constexpr (VEC == 4 && XCH > 0) xq.load_row(xbuf, have_next ? tn : 0, D, tid);                      \
       else xq.load(xrow_next, D, tid);                                                                      \
     }                                                                                                       \
     float s0 = 0.f, s1 = 0.f;                                                                               \
-    if (kWithArcs)                                                                                          \
-      tile_rows<R, 0, VOFF>(arcs, groups, tail_slots, lane, cur, xr + (VOFF) / 4, raw, nullptr, fwd ? nullptr : lk, s0, s1); \
-    else { s0 = 1.f; s1 = 1.f; }                                                                            \
+    tile_rows<R, 0, VOFF>(arcs, groups, tail_slots, lane, cur, xr + (VOFF) / 4, raw, nullptr, fwd ? nullptr : lk, s0, s1); \
     /* double-buffered: the other buffer was last read in the previous step, which every wave has left */   \
-    if (DB && kWithX && have_next) {                                                                        \
+    if (DB && have_next) {                                                                                  \
       if (fwd && xq.has_nan()) bad |= 2;                                                                    \
       xq.store(xr + (kXOff - (VOFF)) / 4, xrow_next, D, tid, a.input_is_exp);                               \
     }                                                                                                       \
-    if (kArcsOnly) { if (s0 == 12345.f) raw[tid] = s0; if (kArcsOnly == 2) __syncthreads(); break; }        \
     PH_ADD(0, pt); pt = PH_T();                                                                             \
     s0 = wave_sum(s0);                                                                                      \
     if (!fwd) s1 = wave_sum(s1);                                                                            \
@@ -158,10 +152,9 @@ __global__ __launch_bounds__(kNT) void den_recursion_kernel(const DenArgs a) {
     const int tstore = fwd ? j + 1 : L - 1 - j;                                                             \
     if (tid == 0) totv[tstore] = tot;                /* the scale divided out of this frame (den_finish_kernel) */ \
     const bool do_store = fwd ? (tstore < L) : true;                                                        \
-    if (kWithNorm)                                                                                          \
-      normalise_row(fwd, raw, lk, cur, sbuf, do_store ? tstore * Hp * 4 : -1, inv, coef, coef * wtot, H, Hp, tid, true, cl0); \
+    normalise_row(fwd, raw, lk, cur, sbuf, do_store ? tstore * Hp * 4 : -1, inv, coef, coef * wtot, H, Hp, tid, true, cl0); \
     PH_ADD(3, pt); pt = PH_T();                                                                             \
-    if (!DB && kWithX && have_next) {                                                                       \
+    if (!DB && have_next) {                                                                                 \
       if (fwd && xq.has_nan()) bad |= 2;                                                                    \
       if (xq.store(xr, xrow_next, D, tid, a.input_is_exp) && fwd) bad |= 2;   /* (rows staged without registers) */ \
     }                                                                                                       \
@@ -169,27 +162,6 @@ __global__ __launch_bounds__(kNT) void den_recursion_kernel(const DenArgs a) {
     __syncthreads();                                                                                        \
     PH_ADD(5, pt);                                                                                          \
   } while (0)
-  // (PYCHAIN_EXP_*: ablation builds for timing only - results are wrong)
-#ifdef PYCHAIN_EXP_NO_X
-  constexpr bool kWithX = false;
-#else
-  constexpr bool kWithX = true;
-#endif
-#ifdef PYCHAIN_EXP_NO_ARCS
-  constexpr bool kWithArcs = false;
-#else
-  constexpr bool kWithArcs = true;
-#endif
-#ifdef PYCHAIN_EXP_NO_NORM
-  constexpr bool kWithNorm = false;
-#else
-  constexpr bool kWithNorm = true;
-#endif
-#ifdef PYCHAIN_EXP_ARCS_ONLY
-  constexpr int kArcsOnly = PYCHAIN_EXP_ARCS_ONLY;
-#else
-  constexpr int kArcsOnly = 0;
-#endif
   // Progress signal of the gated schedule: once the steps below seg_bound[s] are done, every wave waits for
   // its own row stores (device-scope write-through, normalise_row: the L2s of the XCDs are not coherent with
   // one another and the occupancy kernel runs on all of them), then one thread counts the workgroup in.

@@ -48,45 +48,25 @@ __device__ __forceinline__ float dpp_row_sum(float v) {
 // lane 63 then holds (r3 + r2) + (r1 + r0), bit for bit the (r0 + r1) + (r2 + r3) of four readlanes and three adds - and ONE
 // readlane: 7 VALU instructions instead of 13.  The recursion frames sit on their VALU issue - DESIGN.md 3.16 - and every wave
 // reduces one or two such sums per frame.)
-#ifndef PYCHAIN_WAVE_SUM_BCAST
-#define PYCHAIN_WAVE_SUM_BCAST 1
-#endif
 __device__ __forceinline__ float wave_sum(float v) {
   v = dpp_row_sum(v);
-#if PYCHAIN_WAVE_SUM_BCAST
   // (written out: from the builtin the compiler makes v_mov 0, v_mov_dpp, v_add of each step; the s_nop is the two wait states a
   // DPP read needs after the VALU write of its source, which the compiler cannot see into the asm to insert)
   asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf" : "+v"(v));   // rows 1, 3 += lane 15 of rows 0, 2
   asm volatile("s_nop 1\n\tv_add_f32_dpp %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf" : "+v"(v));   // rows 2, 3 += lane 31
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-#else
-  const float r0 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-  const float r1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 16));
-  const float r2 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 32));
-  const float r3 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 48));
-  return (r0 + r1) + (r2 + r3);
-#endif
 }
 
-// exp(c) for |c| <= 30.  PYCHAIN_EXP_OPS == 5 (rounds 1-2): v_exp_f32 on c*log2(e) with the rounding error of that product
-// fed back, exp(c) = 2^t * (1 + r ln2): relative error ~2e-7 whatever |c|.  PYCHAIN_EXP_OPS == 2 (round 3, default): v_exp_f32
-// on the rounded product alone: the error of t = c*log2(e) in fp32 is |t| * 6e-8, i.e. a relative error of |c| * 6e-8 in the
+// exp(c) for |c| <= 30.  Rounds 1-2 ran v_exp_f32 on c*log2(e) with the rounding error of that product fed back,
+// exp(c) = 2^t * (1 + r ln2): relative error ~2e-7 whatever |c|, five operations.  Since round 3 it is v_exp_f32
+// on the rounded product alone, two operations: the error of t = c*log2(e) in fp32 is |t| * 6e-8, i.e. a relative error of |c| * 6e-8 in the
 // result - 2e-7 at |c| = 3 (network outputs are O(1)), 1.8e-6 at the clamp (|c| = 30) - against a parity bar of 1e-4 and an
 // oracle whose own expf is 1 ulp.  The clamp / exp of a row sits in the serial tail of every recursion frame, where the four
 // waves of a SIMD issue it one after another: three instructions less per element are ~150 cycles per frame.
-#ifndef PYCHAIN_EXP_OPS
-#define PYCHAIN_EXP_OPS 2
-#endif
 __device__ __forceinline__ float exp_bounded(float c) {
   const float kL2E = 1.44269502162933349609375f;       // fp32(log2 e)
   const float t = c * kL2E;
-#if PYCHAIN_EXP_OPS == 2
   return __builtin_amdgcn_exp2f(t);
-#else
-  const float r = fmaf(c, kL2E, -t);
-  const float e = __builtin_amdgcn_exp2f(t);
-  return fmaf(e, r * 0.693147182464599609375f, e);
-#endif
 }
 
 // How a raw nnet-output element enters LDS (pychain/loss.py:30,43):
