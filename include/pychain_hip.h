@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 26
+#define PYCHAIN_HIP_ABI_VERSION 27
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -789,6 +789,85 @@ int pychain_hip_cpu_boost_rows(
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
     const int32_t* target_pdfs, const float* target_probs, int K, float boost,
     float* e, int32_t* bad_count, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Lattice-free sMBR (ABI 27): the expected frame accuracy of the denominator's path distribution against a reference, and its
+ * gradient (state-level minimum Bayes risk without lattices; Kanda et al., Interspeech 2018).  The reference is
+ * sparse per-frame targets (the layout and the index type of pychain_hip_post_targets: an alignment as K = 1 hard targets, or
+ * posterior targets); the accuracy of pdf n at frame t is A(t,n) = the sum of the frame's q_k with pdf_k == n (repeated pdfs
+ * add, padding adds nothing).  A path scores sum_t A(t, pdf of its arc at t); leak transitions score nothing.  Per sequence:
+ *   E          = sum_paths P(path) score(path) = sum_t e(t),   e(t) = sum_n gamma(t,n) A(t,n)
+ *   dE/dy(t,n) = gamma(t,n) (E[score | pdf n at t] - E)                       y the network output, x = exp(clamp(y, -30, 30))
+ * with gamma the denominator's occupancies under the leaky-HMM model of pychain_hip_den_forward_backward.  Neither the clamp nor
+ * the reference is differentiated.  Every live row of the gradient sums to zero over n.
+ *
+ * THE CALL HAS TWO STAGES, on one stream:
+ *   1. pychain_hip_den_forward_backward(x, ..., grad_scale = 1) as it is: its gradient IS gamma, [B,T,D] fp32 (a 2-byte network
+ *      output is up-cast for this stage).  pychain_hip_smbr_frame_accuracy then forms e(b,t) and E_b = sum_t e(b,t) (fp64).
+ *   2. pychain_hip_smbr_forward_backward: the gradient is a covariance under the path distribution and needs, beside alpha' and
+ *      beta', an accuracy-weighted pair of recursions (v' = the leak of v, the same operator for both of a pair):
+ *        abar(0) = 0   abar(t+1,j) = sum_{k: dst=j} [ abar'(t,src) + a(t,pdf_k) alpha'(t,src) ] p_k x(t,pdf_k)
+ *        bbar(L) = 0   bbar(t,i)   = sum_{k: src=i} p_k x(t,pdf_k) [ bbar'(t+1,dst) + a(t,pdf_k) beta'(t+1,dst) ]
+ *        q0(t,n) = sum_{k: pdf=n} p alpha'(t,src) beta'(t+1,dst)
+ *        q1(t,n) = sum_{k: pdf=n} p [ abar'(t,src) beta'(t+1,dst) + alpha'(t,src) bbar'(t+1,dst) ]
+ *        grad(t,n) = s x(t,n) (q1(t,n) + a(t,n) q0(t,n)) / sum_m x(t,m) q0(t,m)          s = grad_scale [* *grad_scale_dev]
+ *      with the CENTRED accuracies a(t,n) = A(t,n) - e(t): a per-frame constant changes no covariance, and it keeps every
+ *      weighted quantity near zero instead of growing like t, which is what lets fp32 carry it.  All four vectors are normalised
+ *      per frame by the totals of alpha and beta; the quotient removes the factors.  One recursion launch of 2B persistent
+ *      workgroups (sequence x direction; no workgroup waits for another), one time-parallel gradient launch.
+ *
+ * GRAPH.  One denominator graph for every sequence, in the reference layout as device pointers (fstext.cc:49-116): arcs
+ * {src, dst, pdf} in runs by source (forward_*) and by destination (backward_*), [H,2] run bounds, probabilities, and the leaky,
+ * initial and final probabilities [H]; every src, dst < H and pdf < num_pdfs (NOT checked: device memory).  pdf_arcs int32[K]:
+ * the ids of the forward_* arcs ordered by pdf, stable; pdf_index int32[num_pdfs + 1]: the run of pdf n is
+ * pdf_arcs[pdf_index[n] .. pdf_index[n+1]).
+ * frame_accuracy:    gamma dev fp32 [B,T,D]; frame_acc dev float[B,T] out (live frames only); acc_per_seq dev double[B] out;
+ *                    bad_count dev int32[2], ZEROED by this call: [1] = the live entries with pdf >= num_pdfs (skipped
+ *                    otherwise; pdf < 0 is padding).  Frames t >= L_b are neither read nor written.
+ * forward_backward:  nnet_output in its own type (fp32 / bf16 / fp16, read element by element: any element-aligned start);
+ *                    frame_acc, acc_per_seq, bad_count as the first call left them; grad dev [B,T,D] out in the network output's
+ *                    type, written once: rows t >= L_b are exact zeros, a pdf no arc carries gets an exact zero without its x
+ *                    being read.  The 2-byte forms compute what the fp32 form computes on the up-cast input and round once.
+ *                    closing dev float[B] out: sum_j abar'(L,j) final(j) / sum_j alpha'(L,j) final(j), zero up to rounding (a
+ *                    diagnostic of the recursions).  bad_count[0] += the sequences with a frame total of the recursions or a
+ *                    frame's divisor sum_m x q0 of the gradient that is not positive and finite, or a NaN in a live row of x:
+ *                    such a sequence has acc_per_seq NaN and is counted once; closing is NaN where the recursions or x were
+ *                    the cause.  The other sequences of the call are untouched.
+ * No float atomics: a call gives the same bits every time.  The recursion workgroup keeps four state vectors and four rows in
+ * LDS: (4 H + 4 num_pdfs + 128) * 4 bytes must fit the 160 KiB of a CU (3000 states and 3456 pdfs: 103 KiB), else
+ * PYCHAIN_HIP_EUNSUPPORTED with the sizes in the message - there is no slower form.  Workspace: pychain_hip_smbr_workspace_bytes
+ * (the four trajectories, 16 (T + 1) H B bytes, and the frame totals).  leaky_hmm_coefficient in (0,1); K >= 1.  The entry points
+ * are a translation unit of their own (csrc/smbr.hip): no existing entry point launches anything it did not launch before. */
+size_t pychain_hip_smbr_workspace_bytes(int B, int T, int num_states);
+int pychain_hip_smbr_frame_accuracy(
+    const float* gamma, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K,
+    float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream);
+int pychain_hip_smbr_forward_backward(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad /* nnet_output_dtype */, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream);
+/* the host twins: the same equations on host pointers, fp32 rows, state vectors and gradient, fp64 sums; host threads over the
+ * sequences; no workspace, no stream, any H and num_pdfs */
+int pychain_hip_cpu_smbr_frame_accuracy(
+    const float* gamma, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K,
+    float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads);
+int pychain_hip_cpu_smbr_forward_backward(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

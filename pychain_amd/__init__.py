@@ -30,3 +30,4 @@ from .graph import ChainGraph, ChainGraphBatch  # noqa: F401
 from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent, output_regularizer, weight_rows  # noqa: F401
 from .loss import PosteriorTargets, occupancies, posterior_numerator, posterior_targets, posterior_xent, boost_rows  # noqa: F401
 from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401
+from .smbr import SMBRFunction, SMBRLoss, expected_accuracy  # noqa: F401

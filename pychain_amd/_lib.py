@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 26
+ABI_VERSION = 27
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -46,6 +46,8 @@ _FUSED_HEAD = _DEN_PLAN + [_f] + _GRAPHS + [_i, _i] + _ROWS + [_i] * 3       # p
 _FUSED_TAIL = [_f, _vp, _vp] + _WS + _WS + [_vp]                             # loss_scale, loss_norm_dev, totals, den_ws, num_ws, stream
 _FORWARD = _FUSED_HEAD + [_vp, _vp, _vp, _f, _vp] + _FUSED_TAIL              # den_objf, num_objf, grad, grad_scale, bad_count
 _FORWARD_BACKWARD = _FUSED_HEAD + [_f] + [_vp] * 4 + _FUSED_TAIL             # grad_scale, den_objf, num_objf, grad, bad_count
+_SMBR_GRAPH = [_vp] * 11 + [_i, _i]                                          # the nine graph tensors, pdf_arcs, pdf_index, H, K
+_SMBR_TAIL = [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]            # targets, K, frame_acc, coef, grad_scale[_dev], grad, acc, closing, bad
 
 _SIGNATURES = {
     "pychain_hip_abi_version": (_i, []),
@@ -109,6 +111,12 @@ _SIGNATURES = {
     # (ABI 25: the rows of the boosted denominator - exp(clamp(x)) with the targeted elements scaled by exp(-boost * a))
     "pychain_hip_boost_rows": (_i, [_vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _vp]),
     "pychain_hip_cpu_boost_rows": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _f, _vp, _vp, _i]),
+    # (ABI 27: lattice-free sMBR - the frame accuracies under the denominator's occupancies, the accuracy-weighted recursions)
+    "pychain_hip_smbr_workspace_bytes": (_sz, [_i, _i, _i]),
+    "pychain_hip_smbr_frame_accuracy": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "pychain_hip_smbr_forward_backward": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp]),
+    "pychain_hip_cpu_smbr_frame_accuracy": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i]),
+    "pychain_hip_cpu_smbr_forward_backward": (_i, _SMBR_GRAPH + _CPU_ROWS + [_i] * 3 + _SMBR_TAIL + [_i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),

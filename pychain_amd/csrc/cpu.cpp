@@ -809,3 +809,189 @@ extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_l
   });
   return PYCHAIN_HIP_OK;
 }
+
+// ---- lattice-free sMBR (include/pychain_hip.h: pychain_hip_smbr_*; the device's smbr.hip): the same equations
+// on host pointers - fp32 state vectors and gradient, fp64 sums; the accuracies centred by the frame accuracies of the first call
+namespace pychain_hip {
+namespace {
+// the frame's accuracy of pdf d: the sum of its entries' q, in ascending k
+inline float smbr_accuracy(const int32_t* pd, const float* pr, int K, int d) {
+  float q = 0.f;
+  for (int k = 0; k < K; k++)
+    if (pd[k] == d) q = post_add(q, pr[k]);
+  return q;
+}
+
+bool smbr_one(const Csr& fwd, const Csr& bwd, const float* leaky, const float* init, const float* fin, const int32_t* parc, const int32_t* pidx,
+              int H, const float* x, int L, int D, const int32_t* pdfs, const float* probs, int K, const float* facc, float coef,
+              float gscale, float* grad, float* closing) {
+  const size_t rows = (size_t)L + 1;
+  std::vector<float> al(rows * H), ab(rows * H, 0.f), be(rows * H), bb(rows * H, 0.f), xr((size_t)D), xa((size_t)D);
+  bool ok = true, den_ok = true;                   // what the recursions find; what the gradient frames find
+  auto stage = [&](int t) {                        // x = exp(clamp(y)) and its sparse companion x A
+    const float* y = x + (size_t)t * D;
+    for (int n = 0; n < D; n++) {
+      if (y[n] != y[n]) ok = false;
+      xr[n] = std::exp(y[n] != y[n] ? -30.f : clamp30(y[n]));
+      xa[n] = 0.f;
+    }
+    for (int k = 0; k < K; k++) {
+      const int d = pdfs[(size_t)t * K + k];
+      if (d >= 0 && d < D) xa[d] = xr[d] * smbr_accuracy(pdfs + (size_t)t * K, probs + (size_t)t * K, K, d);
+    }
+  };
+  auto positive = [&](double tot) { if (!(tot > 0.0) || !std::isfinite(tot) || !std::isfinite(1.0 / tot)) ok = false; };
+  {
+    double tot = 0.0;
+    for (int i = 0; i < H; i++) tot += (double)init[i];
+    positive(tot);
+    for (int i = 0; i < H; i++) al[i] = (float)((double)init[i] / tot + (double)coef * leaky[i]);
+  }
+  std::vector<double> r0((size_t)H), r1((size_t)H);
+  for (int t = 0; t < L; t++) {
+    stage(t);
+    const float *a0 = al.data() + (size_t)t * H, *a1 = ab.data() + (size_t)t * H;
+    double tot = 0.0, s1 = 0.0;
+    for (int j = 0; j < H; j++) {
+      double acc0 = 0.0, acc1 = 0.0;
+      for (int k = bwd.idx[2 * j]; k < bwd.idx[2 * j + 1]; k++) {
+        const int src = bwd.trans[3 * k], n = bwd.trans[3 * k + 2];
+        const double wu = (double)bwd.prob[k] * a0[src];
+        acc0 += wu * xr[n];
+        acc1 += (double)bwd.prob[k] * a1[src] * xr[n] + wu * xa[n];
+      }
+      acc1 -= (double)facc[t] * acc0;
+      r0[j] = acc0; r1[j] = acc1;
+      tot += acc0; s1 += acc1;
+    }
+    positive(tot);
+    float *o0 = al.data() + (size_t)(t + 1) * H, *o1 = ab.data() + (size_t)(t + 1) * H;
+    for (int j = 0; j < H; j++) {
+      const double lk = (double)coef * leaky[j];
+      o0[j] = (float)(r0[j] / tot + lk);
+      o1[j] = (float)((r1[j] + lk * s1) / tot);
+    }
+  }
+  {
+    double tot = 0.0, w = 0.0;
+    for (int i = 0; i < H; i++) { tot += (double)fin[i]; w += (double)fin[i] * leaky[i]; }
+    positive(tot);
+    for (int i = 0; i < H; i++) be[(size_t)L * H + i] = (float)(((double)fin[i] + (double)coef * w) / tot);
+  }
+  for (int t = L - 1; t >= 0; t--) {
+    stage(t);
+    const float *b0 = be.data() + (size_t)(t + 1) * H, *b1 = bb.data() + (size_t)(t + 1) * H;
+    double tot = 0.0, s1 = 0.0, s2 = 0.0;
+    for (int i = 0; i < H; i++) {
+      double acc0 = 0.0, acc1 = 0.0;
+      for (int k = fwd.idx[2 * i]; k < fwd.idx[2 * i + 1]; k++) {
+        const int dst = fwd.trans[3 * k + 1], n = fwd.trans[3 * k + 2];
+        const double wu = (double)fwd.prob[k] * b0[dst];
+        acc0 += wu * xr[n];
+        acc1 += (double)fwd.prob[k] * b1[dst] * xr[n] + wu * xa[n];
+      }
+      acc1 -= (double)facc[t] * acc0;
+      r0[i] = acc0; r1[i] = acc1;
+      tot += acc0; s1 += acc0 * leaky[i]; s2 += acc1 * leaky[i];
+    }
+    positive(tot);
+    float *o0 = be.data() + (size_t)t * H, *o1 = bb.data() + (size_t)t * H;
+    for (int i = 0; i < H; i++) {
+      o0[i] = (float)((r0[i] + (double)coef * s1) / tot);
+      o1[i] = (float)((r1[i] + (double)coef * s2) / tot);
+    }
+    // the gradient of frame t: alpha'(t), alpha-bar'(t), beta'(t+1), beta-bar'(t+1); x and x A of frame t are staged
+    const float *a0 = al.data() + (size_t)t * H, *a1 = ab.data() + (size_t)t * H;
+    std::vector<double> v((size_t)D);
+    double den = 0.0;
+    for (int n = 0; n < D; n++) {
+      double q0 = 0.0, q1 = 0.0;
+      for (int k = pidx[n]; k < pidx[n + 1]; k++) {
+        const int id = parc[k], src = fwd.trans[3 * id], dst = fwd.trans[3 * id + 1];
+        const double wa = (double)fwd.prob[id] * a0[src];
+        q0 += wa * b0[dst];
+        q1 += (double)fwd.prob[id] * a1[src] * b0[dst] + wa * b1[dst];
+      }
+      if (pidx[n] == pidx[n + 1]) { v[n] = 0.0; continue; }
+      v[n] = (double)xr[n] * (q1 - (double)facc[t] * q0) + (double)xa[n] * q0;
+      den += (double)xr[n] * q0;
+    }
+    // the frame's divisor, as the device checks it: it decides the verdict, not `closing` (a diagnostic of the recursions)
+    if (!(den > 0.0) || !std::isfinite(den) || !std::isfinite(1.0 / den)) den_ok = false;
+    float* go = grad + (size_t)t * D;
+    for (int n = 0; n < D; n++) go[n] = pidx[n] == pidx[n + 1] ? 0.f : (float)((double)gscale * v[n] / den);
+  }
+  double c0 = 0.0, c1 = 0.0;
+  for (int i = 0; i < H; i++) { c0 += (double)al[(size_t)L * H + i] * fin[i]; c1 += (double)ab[(size_t)L * H + i] * fin[i]; }
+  if (!(c0 > 0.0)) ok = false;
+  *closing = ok ? (float)(c1 / c0) : std::numeric_limits<float>::quiet_NaN();
+  return ok && den_ok;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                                   const int32_t* target_pdfs, const float* target_probs, int K,
+                                                   float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_smbr_frame_accuracy";
+  if (!gamma || !seq_lengths || !target_pdfs || !target_probs || !frame_acc || !acc_per_seq || !bad_count) return null_pointer(who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  g_cpu_calls++;
+  std::vector<int> bads((size_t)B);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int L = clamped_length(seq_lengths[b], T);
+    double sum = 0.0;
+    int bad = 0;
+    for (int t = 0; t < L; t++) {
+      const size_t f = (size_t)b * T + t;
+      double e = 0.0;
+      for (int k = 0; k < K; k++) {
+        const int d = target_pdfs[f * K + k];
+        if (d < 0) continue;
+        if (d >= D) { bad++; continue; }
+        e += (double)target_probs[f * K + k] * (double)gamma[f * D + d];
+      }
+      frame_acc[f] = (float)e;
+      sum += e;
+    }
+    acc_per_seq[b] = sum;
+    bads[b] = bad;
+  });
+  bad_count[0] = bad_count[1] = 0;
+  for (int b = 0; b < B; b++) bad_count[1] += bads[b];
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_cpu_smbr_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_smbr_forward_backward";
+  const NumGraphs g{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
+  if (g.any_null() || !leaky || !pdf_arcs || !pdf_index || !nnet_output || !seq_lengths || !target_pdfs || !target_probs || !frame_acc ||
+      !grad || !acc_per_seq || !closing || !bad_count)
+    return null_pointer(who);
+  int rc = bad_sizes(who, B, T, H, num_arcs, D);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  g_cpu_calls++;
+  const float gscale = grad_scale * (grad_scale_dev ? *grad_scale_dev : 1.f);
+  std::atomic<int> bad{0};
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int L = clamped_length(seq_lengths[b], T);
+    const size_t f = (size_t)b * T;
+    float* gb = grad + f * D;
+    const bool ok = smbr_one(fwd_of(g), bwd_of(g), leaky, initial, final_, pdf_arcs, pdf_index, H, nnet_output + f * D, L, D,
+                             target_pdfs + f * K, target_probs + f * K, K, frame_acc + f, leaky_hmm_coefficient, gscale, gb, closing + b);
+    for (size_t i = (size_t)L * D; i < (size_t)T * D; i++) gb[i] = 0.f;
+    if (!ok) { bad++; acc_per_seq[b] = std::numeric_limits<double>::quiet_NaN(); }
+  });
+  bad_count[0] += bad.load();
+  return PYCHAIN_HIP_OK;
+}

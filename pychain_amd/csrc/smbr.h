@@ -1,0 +1,59 @@
+// smbr.h - launch interface of lattice-free sMBR (smbr.hip; include/pychain_hip.h: pychain_hip_smbr_*): the frame
+// accuracies of a reference under the denominator's occupancies, and the accuracy-weighted recursions whose products are the
+// gradient of the expected accuracy.
+#ifndef PYCHAIN_HIP_SMBR_H_
+#define PYCHAIN_HIP_SMBR_H_
+
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+namespace pychain_hip {
+
+constexpr size_t kSmbrLdsBudget = 160 * 1024;       // the LDS of one CU
+
+// the denominator graph in the reference layout (one graph for every sequence), and its arcs ordered by pdf
+struct SmbrGraph {
+  const int32_t *ft, *fi; const float* fp;          // arcs {src, dst, pdf} in runs by source, [H][2] run bounds, probabilities
+  const int32_t *bt, *bi; const float* bp;          // the same arcs in runs by destination
+  const float *leaky, *init, *fin;                  // [H]
+  const int32_t *parc, *pidx;                       // [K] ids into ft / fp, stable by pdf; [D + 1] run bounds
+  int H, K;
+};
+
+struct SmbrAccArgs {
+  const float* gamma;        // [B,T,D] the denominator's occupancies, fp32
+  const int64_t* lengths;
+  const int32_t* pdfs;       // [B,T,Kt]: < 0 padding, >= D counted
+  const float* probs;        // [B,T,Kt]
+  float* frame_acc;          // [B,T] out: e(b,t) of the live frames
+  double* acc_per_seq;       // [B] out
+  int32_t* bad_count;        // [2], zeroed on the stream before the launch; [1] += live entries with pdf >= D
+  int B, T, D, Kt;
+};
+
+struct SmbrArgs {
+  SmbrGraph g;
+  const void* x; int x_half;             // [B,T,D] raw: kXF32 / kXBf16 / kXF16 (device_utils.h)
+  const int64_t* lengths;
+  const int32_t* pdfs; const float* probs;
+  const float* frame_acc;                // [B,T] from the accuracy pass
+  float coef, grad_scale; const float* grad_scale_dev;
+  void* grad;                            // [B,T,D] out, x's type
+  double* acc_per_seq;                   // [B]: NaN for a sequence that went bad
+  float* closing;                        // [B] out
+  int32_t* bad_count;                    // [2]: [0] += the sequences that went bad
+  float *al, *ab, *be, *bb;              // workspace: [B][T+1][H] alpha', alpha-bar', beta', beta-bar', normalised per frame
+  float *tot_a, *tot_b;                  // workspace: [B][T+1] the frame totals divided out - DIAGNOSTIC ONLY: written, read by no kernel
+  int32_t* seq_bad;                      // workspace: [2][B], zeroed on the stream before the launches: what the recursions found;
+                                         // the verdict claimed (smbr.hip: smbr_condemn)
+  int B, T, D, Kt;
+};
+
+size_t smbr_recursion_lds(int H, int D);            // bytes of LDS the recursion workgroup needs
+size_t smbr_grad_lds(int H, int D);
+hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st);
+hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st);     // the recursion launch, then the gradient launch
+
+}  // namespace pychain_hip
+#endif

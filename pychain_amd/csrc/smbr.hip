@@ -1,0 +1,460 @@
+// smbr.hip - lattice-free sMBR (include/pychain_hip.h: pychain_hip_smbr_*): the expected frame accuracy of the
+// denominator's path distribution against a reference given as sparse per-frame targets, E = sum_t sum_n gamma(t,n) A(t,n), and
+// its gradient dE/dy(t,n) = gamma(t,n) (E[score | pdf n at t] - E).  The gradient is a covariance under the path distribution:
+// beside alpha' and beta' it needs the accuracy-weighted pair alpha-bar', beta-bar', which no other kernel of the library forms.
+//
+//   smbr_frame_acc_kernel    e(b,t) = sum_k q_k gamma(b,t,pdf_k) from the occupancies of the ordinary denominator call, and
+//                            E_b = sum_t e(b,t) in fp64.  One workgroup per sequence, a thread per frame.
+//   smbr_recursion_kernel    2B persistent workgroups, one per (sequence, direction), each carrying (alpha', alpha-bar') or
+//                            (beta', beta-bar') in LDS, double-buffered, with the frame's row x = exp(clamp(y)) and its sparse
+//                            companion xa(n) = x(n) A(t,n); both rows are made a frame ahead.  Arcs come from global memory in the
+//                            reference layout (by destination forwards, by source backwards); a thread owns states tid, tid + 1024,
+//                            ...  The accuracies are CENTRED, a(t,n) = A(t,n) - e(t): the source term of a frame is
+//                            sum alpha' p xa - e(t) * (the first-order sum), so that only the frame's K entries need a row.
+//                            alpha-bar and beta-bar take the per-frame normalisers of alpha and beta.  No workgroup waits for
+//                            another; every loop is bounded by L_b <= T.
+//   smbr_grad_kernel         time-parallel over (sequence, block of frames): the four state rows of a frame in LDS, a thread owns
+//                            pdfs tid, tid + 512, ... and walks that pdf's arcs through the caller's by-pdf order:
+//                              q0 = sum p alpha' beta',  q1 = sum p (alpha-bar' beta' + alpha' beta-bar')
+//                              grad = s x (q1 + a q0) / sum_m x(m) q0(m)
+//                            The frame's normalisers cancel in the quotient, as in den_general_gamma_kernel.
+// Nothing is atomic but integer counters and flags; every sum has a fixed order, so a call gives the same bits every time.  All of
+// this unit's device code, the helpers of the project's headers included, is compiled with contraction off: the 2-byte forms then compute what the fp32 form computes on the up-cast input.
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstring>
+
+#pragma clang fp contract(off)      // ahead of the project's headers: their inline helpers (clamp_exp, the row loads) are under it too
+
+#include "../../include/pychain_hip.h"
+#include "call_args.h"
+#include "common.h"
+#include "row_access.h"
+#include "smbr.h"
+
+namespace pychain_hip {
+namespace {
+
+constexpr int kSmNT = 1024;                 // recursion workgroup: 16 waves
+constexpr int kSmGNT = 512;                 // gradient workgroup
+constexpr int kSmFrames = 8;                // frames of one gradient workgroup
+constexpr int kSmAccNT = 256;
+constexpr int kSmXR = 4;                    // elements of the next row a recursion thread holds in registers across the arc loop
+constexpr int kSmRed = 64;                  // floats of reduction scratch
+constexpr size_t kSmStaticLds = 256;        // what the recursion kernel holds beside its dynamic LDS (the closing vote)
+
+// up to three sums over the workgroup, every thread gets the totals; `red` (3 x 16 floats) is free again behind the NEXT barrier
+template <int NT>
+__device__ __forceinline__ void block_sum3(float& s0, float& s1, float& s2, float* red, int tid) {
+  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
+  if ((tid & 63) == 0) { red[tid >> 6] = s0; red[16 + (tid >> 6)] = s1; red[32 + (tid >> 6)] = s2; }
+  __syncthreads();
+  s0 = s1 = s2 = 0.f;
+  for (int w = 0; w < NT / 64; w++) { s0 += red[w]; s1 += red[16 + w]; s2 += red[32 + w]; }     // (same order in every thread)
+}
+
+// Entry k of a frame (pd, pr: its Kt entries): true where this thread owns it, with (pdf, summed q).  An entry is handled where
+// its pdf occurs first in the frame, q summed in ascending k, so a repeated pdf has one owner and nothing is atomic.
+__device__ __forceinline__ bool owned_entry(const int32_t* pd, const float* pr, int k, int Kt, int D, int& d, float& q) {
+  d = pd[k];
+  if (d < 0 || d >= D) return false;
+  for (int j = 0; j < k; j++)
+    if (pd[j] == d) return false;
+  q = pr[k];
+  for (int j = k + 1; j < Kt; j++)
+    if (pd[j] == d) q += pr[j];
+  return true;
+}
+// x A of a frame over its zeroed companion row
+__device__ __forceinline__ void scatter_entries(const int32_t* pd, const float* pr, int Kt, int D, int tid, int nt, const float* xrow, float* xacc) {
+  int d;
+  float q;
+  for (int k = tid; k < Kt; k += nt)
+    if (owned_entry(pd, pr, k, Kt, D, d, q)) xacc[d] = xrow[d] * q;
+}
+
+// ---- stage 1: frame accuracies ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kSmAccNT) void smbr_frame_acc_kernel(const SmbrAccArgs a) {
+  __shared__ double red[kSmAccNT / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int L = seq_len(a.lengths, b, a.T);
+  double sum = 0.0;
+  int bad = 0;
+  for (int t = tid; t < L; t += kSmAccNT) {
+    const size_t f = (size_t)b * a.T + t;
+    const float* g = a.gamma + f * a.D;
+    double e = 0.0;
+    for (int k = 0; k < a.Kt; k++) {
+      const int d = a.pdfs[f * a.Kt + k];
+      if (d < 0) continue;
+      if (d >= a.D) { bad++; continue; }
+      e += (double)a.probs[f * a.Kt + k] * (double)g[d];
+    }
+    a.frame_acc[f] = (float)e;
+    sum += e;
+  }
+  sum = wave_sum_f64(sum);
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if ((tid & 63) == 0) {
+    red[tid >> 6] = sum;
+    if (bad) atomicAdd(a.bad_count + 1, bad);                 // (an integer sum: the same value in any order)
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < kSmAccNT / 64; w++) s += red[w];
+    a.acc_per_seq[b] = s;
+  }
+}
+
+// ---- stage 2: the recursions ----------------------------------------------------------------------------------------------------
+// row t of the sequence into LDS as exp(clamp(.)); elements tid + i * NT, i < kSmXR, come from `held` (loaded before the arc loop)
+template <int XH>
+__device__ __forceinline__ void hold_row(const void* x, size_t row, int D, int tid, float (&held)[kSmXR]) {
+#pragma unroll
+  for (int i = 0; i < kSmXR; i++) {
+    const int n = tid + i * kSmNT;
+    held[i] = n < D ? row_load1<XH>(x, row + n) : 0.f;
+  }
+}
+template <int XH>
+__device__ __forceinline__ bool put_row(const void* x, size_t row, int D, int tid, const float (&held)[kSmXR], float* lds) {
+  bool nan = false;
+#pragma unroll
+  for (int i = 0; i < kSmXR; i++) {
+    const int n = tid + i * kSmNT;
+    if (n < D) { nan = nan || held[i] != held[i]; lds[n] = clamp_exp(held[i], kXExpClamp); }
+  }
+  for (int n = tid + kSmXR * kSmNT; n < D; n += kSmNT) {       // (rows of more than 4096 pdfs)
+    const float r = row_load1<XH>(x, row + n);
+    nan = nan || r != r;
+    lds[n] = clamp_exp(r, kXExpClamp);
+  }
+  return nan;
+}
+
+template <int XH, bool FWD>
+__device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* lds) {
+  const int tid = threadIdx.x;
+  const SmbrGraph& g = a.g;
+  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
+  const int L = seq_len(a.lengths, b, T);
+  float* const vec0 = lds;                       // [2][H] alpha' / beta'
+  float* const vec1 = lds + 2 * (size_t)H;       // [2][H] alpha-bar' / beta-bar'
+  float* const xrow = vec1 + 2 * (size_t)H;      // [2][D] x
+  float* const xacc = xrow + 2 * (size_t)D;      // [2][D] x * A
+  float* const red = xacc + 2 * (size_t)D;
+  const size_t seq_rows = (size_t)b * (T + 1);
+  float* const st0 = (FWD ? a.al : a.be) + seq_rows * H;
+  float* const st1 = (FWD ? a.ab : a.bb) + seq_rows * H;
+  float* const totv = (FWD ? a.tot_a : a.tot_b) + seq_rows;
+  const int32_t* const idx = FWD ? g.bi : g.fi;                // forwards: the arcs ENTERING a state; backwards: those leaving it
+  const int32_t* const arc = FWD ? g.bt : g.ft;
+  const float* const pr = FWD ? g.bp : g.fp;
+  const float coef = a.coef;
+  const size_t xseq = (size_t)b * T * D, fseq = (size_t)b * T;
+  bool bad = false, nan = false;
+
+  // the first row: alpha'(0) from the initial, beta'(L) from the final probabilities; the weighted vector starts at zero
+  {
+    const float* start = FWD ? g.init : g.fin;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int i = tid; i < H; i += kSmNT) { s0 += start[i]; s1 += start[i] * g.leaky[i]; }
+    block_sum3<kSmNT>(s0, s1, s2, red, tid);
+    const float inv = 1.f / s0;
+    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
+    const int r0 = FWD ? 0 : L;
+    if (tid == 0) totv[r0] = s0;
+    for (int i = tid; i < H; i += kSmNT) {
+      const float v = FWD ? start[i] * inv + coef * g.leaky[i] : (start[i] + coef * s1) * inv;
+      vec0[i] = v; vec1[i] = 0.f;
+      st0[(size_t)r0 * H + i] = v; st1[(size_t)r0 * H + i] = 0.f;
+    }
+    const int t0 = FWD ? 0 : L - 1;
+    float held[kSmXR];
+    hold_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held);
+    nan = put_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held, xrow) || nan;
+    for (int n = tid; n < D; n += kSmNT) xacc[n] = 0.f;
+    __syncthreads();
+    scatter_entries(a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, xrow, xacc);
+    __syncthreads();
+  }
+  // frame j: forwards alpha'(t+1) from alpha'(t) and x(t), t = j; backwards beta'(t) from beta'(t+1) and x(t), t = L-1-j
+  for (int j = 0; j < L; j++) {
+    const int p = j & 1;
+    const int t = FWD ? j : L - 1 - j, tn = FWD ? t + 1 : t - 1;
+    const bool more = j + 1 < L;
+    const float* v0 = vec0 + (size_t)p * H;
+    const float* v1 = vec1 + (size_t)p * H;
+    float* w0 = vec0 + (size_t)(1 - p) * H;
+    float* w1 = vec1 + (size_t)(1 - p) * H;
+    const float* xr = xrow + (size_t)p * D;
+    const float* xa = xacc + (size_t)p * D;
+    float* xrn = xrow + (size_t)(1 - p) * D;
+    float* xan = xacc + (size_t)(1 - p) * D;
+    float held[kSmXR];
+    if (more) hold_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held);          // the next frame's row: in flight over the arc loop
+    for (int n = tid; n < D; n += kSmNT) xan[n] = 0.f;
+    const float e_t = a.frame_acc[fseq + t];
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int i = tid; i < H; i += kSmNT) {
+      float acc0 = 0.f, acc1 = 0.f;
+      const int k1 = idx[2 * i + 1];
+      for (int k = idx[2 * i]; k < k1; k++) {
+        const int other = arc[3 * k + (FWD ? 0 : 1)], n = arc[3 * k + 2];
+        const float w = pr[k], u0 = v0[other], u1 = v1[other], xx = xr[n], xq = xa[n];
+        const float wu = w * u0;
+        acc0 += wu * xx;
+        acc1 += (w * u1) * xx + wu * xq;
+      }
+      acc1 -= e_t * acc0;                                                      // the centring: a(t,n) = A(t,n) - e(t)
+      w0[i] = acc0; w1[i] = acc1;                                              // raw, finished below by the thread that wrote them
+      s0 += acc0;
+      if (FWD) s1 += acc1;
+      else { s1 += acc0 * g.leaky[i]; s2 += acc1 * g.leaky[i]; }
+    }
+    if (more) nan = put_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held, xrn) || nan;
+    block_sum3<kSmNT>(s0, s1, s2, red, tid);                                   // (its barrier: the next rows are whole)
+    if (more) scatter_entries(a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, xrn, xan);
+    const float inv = 1.f / s0;
+    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
+    const int r = FWD ? t + 1 : t;
+    if (tid == 0) totv[r] = s0;
+    float* o0 = st0 + (size_t)r * H;
+    float* o1 = st1 + (size_t)r * H;
+    for (int i = tid; i < H; i += kSmNT) {
+      float c0, c1;
+      if (FWD) {
+        const float lk = coef * g.leaky[i];
+        c0 = w0[i] * inv + lk;                                                 // (the normalised alpha sums to one)
+        c1 = (w1[i] + lk * s1) * inv;
+      } else {
+        c0 = (w0[i] + coef * s1) * inv;
+        c1 = (w1[i] + coef * s2) * inv;
+      }
+      w0[i] = c0; w1[i] = c1;
+      o0[i] = c0; o1[i] = c1;
+    }
+    __syncthreads();
+  }
+  // a NaN in a live row of x (the clamp turns it into exp(-30): watched here, by the forward workgroup), a total that is not
+  // positive and finite: the sequence is bad.  (Both workgroups of a sequence may store the same 1.)
+  if (__syncthreads_or((bad || (FWD && nan)) ? 1 : 0) && tid == 0) a.seq_bad[b] = 1;
+}
+
+template <int XH>
+__global__ __launch_bounds__(kSmNT) void smbr_recursion_kernel(const SmbrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true>(a, blockIdx.x, lds);
+  else smbr_recursion<XH, false>(a, blockIdx.x - a.B, lds);
+}
+
+// ---- stage 2: the gradient ------------------------------------------------------------------------------------------------------
+// The sequence went bad: its E_b becomes NaN and it is counted ONCE, by whichever workgroup of the gradient launch finds it first
+// (seq_bad[B + b]: claimed by an integer compare-and-swap; the same values whoever wins).
+__device__ __forceinline__ void smbr_condemn(const SmbrArgs& a, int b) {
+  if (atomicCAS(a.seq_bad + a.B + b, 0, 1) == 0) {
+    a.acc_per_seq[b] = __builtin_nan("");
+    atomicAdd(a.bad_count, 1);                                                 // (an integer count)
+  }
+}
+template <int XH>
+__global__ __launch_bounds__(kSmGNT) void smbr_grad_kernel(const SmbrArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const SmbrGraph& g = a.g;
+  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
+  const int L = seq_len(a.lengths, b, T);
+  float* const sa = lds;                          // alpha'(t)
+  float* const sab = sa + H;                      // alpha-bar'(t)
+  float* const sb = sab + H;                      // beta'(t+1)
+  float* const sbb = sb + H;                      // beta-bar'(t+1)
+  float* const gq = sbb + H;                      // [D] x q0
+  float* const gv = gq + D;                       // [D] x (q1 - e q0), then + A x q0 where the frame has an entry
+  float* const red = gv + D;
+  const size_t seq_rows = (size_t)b * (T + 1);
+  const float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
+  const int t_begin = blockIdx.x * kSmFrames, t_end = min(t_begin + kSmFrames, T);
+  for (int t = t_begin; t < t_end; t++) {
+    const size_t row = ((size_t)b * T + t) * D;
+    if (t >= L) {                                                              // padding: exact zeros
+      for (int n = tid; n < D; n += kSmGNT) row_store1<XH>(a.grad, row + n, 0.f);
+      continue;
+    }
+    const size_t r0 = (seq_rows + t) * H, r1 = r0 + H;
+    for (int i = tid; i < H; i += kSmGNT) { sa[i] = a.al[r0 + i]; sab[i] = a.ab[r0 + i]; sb[i] = a.be[r1 + i]; sbb[i] = a.bb[r1 + i]; }
+    __syncthreads();
+    const float e_t = a.frame_acc[(size_t)b * T + t];
+    float part = 0.f, none1 = 0.f, none2 = 0.f;
+    for (int n = tid; n < D; n += kSmGNT) {
+      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
+      float q0 = 0.f, q1 = 0.f;
+      for (int k = k0; k < k1; k++) {
+        const int id = g.parc[k];
+        const int src = g.ft[3 * id], dst = g.ft[3 * id + 1];
+        const float w = g.fp[id];
+        const float wa = w * sa[src];
+        q0 += wa * sb[dst];
+        q1 += (w * sab[src]) * sb[dst] + wa * sbb[dst];
+      }
+      float v0 = 0.f, v1 = 0.f;
+      if (k0 != k1) {                                                          // a pdf no arc carries: its x is not read
+        const float xx = clamp_exp(row_load1<XH>(a.x, row + n), kXExpClamp);
+        v0 = xx * q0;
+        v1 = xx * (q1 - e_t * q0);
+      }
+      gq[n] = v0; gv[n] = v1;
+      part += v0;
+    }
+    block_sum3<kSmGNT>(part, none1, none2, red, tid);
+    {
+      const int32_t* pd = a.pdfs + ((size_t)b * T + t) * Kt;
+      const float* pr = a.probs + ((size_t)b * T + t) * Kt;
+      int d;
+      float q;
+      for (int k = tid; k < Kt; k += kSmGNT)
+        if (owned_entry(pd, pr, k, Kt, D, d, q)) gv[d] += q * gq[d];
+    }
+    __syncthreads();
+    const float sc = gscale / part, inv = 1.f / part;
+    if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) smbr_condemn(a, b);    // (the host twin's check of the same divisor)
+    for (int n = tid; n < D; n += kSmGNT) {
+      const bool carried = g.pidx[n] != g.pidx[n + 1];
+      row_store1<XH>(a.grad, row + n, carried ? gv[n] * sc : 0.f);
+    }
+    __syncthreads();                                                           // (the rows are free for the next frame)
+  }
+  // the sequence's first workgroup closes it: the diagnostic sum_j alpha-bar'(L,j) final(j) / sum_j alpha'(L,j) final(j), and the
+  // sequence's verdict
+  if (blockIdx.x == 0) {
+    const size_t rL = (seq_rows + L) * H;
+    float c0 = 0.f, c1 = 0.f, none = 0.f;
+    for (int i = tid; i < H; i += kSmGNT) { c0 += a.al[rL + i] * g.fin[i]; c1 += a.ab[rL + i] * g.fin[i]; }
+    block_sum3<kSmGNT>(c0, c1, none, red, tid);
+    if (tid == 0) {
+      const bool bad = a.seq_bad[b] != 0 || !(c0 > 0.f);                       // what the recursions found
+      a.closing[b] = bad ? __builtin_nanf("") : c1 / c0;
+      if (bad) smbr_condemn(a, b);
+    }
+  }
+}
+
+template <int XH>
+hipError_t launch_as(const SmbrArgs& a, hipStream_t st) {
+  const size_t lds_r = smbr_recursion_lds(a.g.H, a.D), lds_g = smbr_grad_lds(a.g.H, a.D);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_grad_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((smbr_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((smbr_grad_kernel<XH>), dim3((a.T + kSmFrames - 1) / kSmFrames, a.B), dim3(kSmGNT), lds_g, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace
+
+size_t smbr_recursion_lds(int H, int D) { return (4 * (size_t)H + 4 * (size_t)D + kSmRed) * sizeof(float); }
+size_t smbr_grad_lds(int H, int D) { return (4 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
+
+hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.bad_count, 0, 2 * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(smbr_frame_acc_kernel, dim3(a.B), dim3(kSmAccNT), 0, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.seq_bad, 0, 2 * (size_t)a.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  if (a.x_half == kXF32) return launch_as<kXF32>(a, st);
+  if (a.x_half == kXBf16) return launch_as<kXBf16>(a, st);
+  return launch_as<kXF16>(a, st);
+}
+
+}  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+// ---- the entry points (include/pychain_hip.h) -----------------------------------------------------------------------------------
+namespace {
+struct SmbrCarve { size_t al, ab, be, bb, tot_a, tot_b, seq_bad, total; };
+SmbrCarve smbr_carve(int B, int T, int H) {
+  SmbrCarve c;
+  const size_t traj = align256((size_t)B * (T + 1) * H * sizeof(float)), tot = align256((size_t)B * (T + 1) * sizeof(float));
+  size_t o = 0;
+  c.al = o; o += traj; c.ab = o; o += traj; c.be = o; o += traj; c.bb = o; o += traj;
+  c.tot_a = o; o += tot; c.tot_b = o; o += tot;
+  c.seq_bad = o; o += align256(2 * (size_t)B * sizeof(int32_t));
+  c.total = o + 256;                               // (the base is aligned inside the caller's buffer)
+  return c;
+}
+}  // namespace
+
+extern "C" size_t pychain_hip_smbr_workspace_bytes(int B, int T, int H) {
+  if (B <= 0 || T <= 0 || H <= 0) return 0;
+  return smbr_carve(B, T, H).total;
+}
+
+extern "C" int pychain_hip_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                               const int32_t* target_pdfs, const float* target_probs, int K,
+                                               float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream) {
+  const char* who = "smbr_frame_accuracy";
+  if (!gamma || !seq_lengths || !target_pdfs || !target_probs || !frame_acc || !acc_per_seq || !bad_count) return null_pointer(who);
+  if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if ((size_t)B * T > (size_t)INT_MAX) return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: B * T = %zu frames", who, (size_t)B * T);
+  SmbrAccArgs a;
+  memset(&a, 0, sizeof(a));
+  a.gamma = gamma; a.lengths = seq_lengths; a.pdfs = target_pdfs; a.probs = target_probs; a.frame_acc = frame_acc;
+  a.acc_per_seq = acc_per_seq; a.bad_count = bad_count; a.B = B; a.T = T; a.D = D; a.Kt = K;
+  const hipError_t err = launch_smbr_frame_acc(a, (hipStream_t)stream);
+  if (err != hipSuccess) return launch_failed(who, err, nullptr);
+  return PYCHAIN_HIP_OK;
+}
+
+extern "C" int pychain_hip_smbr_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "smbr_forward_backward";
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
+  const Rows rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D};
+  int rc = bad_dtype(who, nnet_output_dtype);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (graphs.any_null() || !leaky || !pdf_arcs || !pdf_index || !rows.x || !rows.lengths || !target_pdfs || !target_probs || !frame_acc ||
+      !grad || !acc_per_seq || !closing || !bad_count || !workspace)
+    return null_pointer(who);
+  if ((rc = bad_sizes(who, rows, graphs)) != PYCHAIN_HIP_OK) return rc;
+  if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
+  if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  const size_t lds = smbr_recursion_lds(H, D);
+  if (lds + kSmStaticLds > kSmbrLdsBudget)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states and %d pdfs need %zu bytes of LDS (four state vectors and four rows), a CU has %zu",
+                who, H, D, lds + kSmStaticLds, kSmbrLdsBudget);
+  if ((size_t)B * (T + 1) > (size_t)INT_MAX) return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: B * (T + 1) = %zu rows", who, (size_t)B * (T + 1));
+  const SmbrCarve c = smbr_carve(B, T, H);
+  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, c.total);
+  char* base = ws_base(workspace);
+  SmbrArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = SmbrGraph{ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs};
+  a.x = nnet_output; a.x_half = nnet_output_dtype; a.lengths = seq_lengths; a.pdfs = target_pdfs; a.probs = target_probs;
+  a.frame_acc = frame_acc; a.coef = leaky_hmm_coefficient; a.grad_scale = grad_scale; a.grad_scale_dev = grad_scale_dev;
+  a.grad = grad; a.acc_per_seq = acc_per_seq; a.closing = closing; a.bad_count = bad_count;
+  a.al = (float*)(base + c.al); a.ab = (float*)(base + c.ab); a.be = (float*)(base + c.be); a.bb = (float*)(base + c.bb);
+  a.tot_a = (float*)(base + c.tot_a); a.tot_b = (float*)(base + c.tot_b); a.seq_bad = (int32_t*)(base + c.seq_bad);
+  a.B = B; a.T = T; a.D = D; a.Kt = K;
+  const hipError_t err = launch_smbr(a, (hipStream_t)stream);
+  if (err != hipSuccess) return launch_failed(who, err, nullptr);
+  return PYCHAIN_HIP_OK;
+}

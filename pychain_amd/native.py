@@ -687,6 +687,101 @@ def cpu_boost_rows(x, lengths, pdfs, probs, boost, out=None):
     return out, bad
 
 
+_SMBR_GRAPH = _GRAPH6 + ["leaky_probs", "initial_probs", "final_probs"]
+
+
+def smbr_graph(graph, D, device):
+    """The tensors of a denominator ChainGraph that the sMBR entry points read (include/pychain_hip.h: pychain_hip_smbr_*), on
+    `device`, in ABI order: the nine of the reference layout, then the arcs by pdf - pdf_arcs int32 [K], the ids of the forward
+    arcs in a stable sort by pdf, and pdf_index int32 [D + 1].  Built once per (graph tensors, D, device) and cached on the graph;
+    checked here, on the host: every state below H, every pdf below D."""
+    ts = [getattr(graph, n) for n in _SMBR_GRAPH]
+    key = ("smbr", str(device), int(D)) + tuple((t.data_ptr(), t._version) for t in ts)
+    hit = graph._plan_cache.get(key)
+    if hit is None:
+        ft = graph.forward_transitions.to(torch.int64)
+        H = int(graph.num_states)
+        if int(ft[:, :2].min()) < 0 or int(ft[:, :2].max()) >= H or int(ft[:, 2].min()) < 0:
+            raise ValueError("denominator graph: an arc names a state outside [0, %d) or a negative pdf" % H)
+        if int(ft[:, 2].max()) >= D:
+            raise ValueError("denominator graph names pdf %d, the network output has %d" % (int(ft[:, 2].max()), D))
+        order = torch.sort(ft[:, 2], stable=True)[1]
+        index = torch.zeros(D + 1, dtype=torch.int64)
+        index[1:] = torch.cumsum(torch.bincount(ft[:, 2], minlength=D), 0)
+        host = [t.to(torch.int32 if n in _GRAPH_INT else torch.float32).contiguous() for n, t in zip(_SMBR_GRAPH, ts)]
+        host += [order.to(torch.int32).contiguous(), index.to(torch.int32).contiguous()]
+        hit = [t.to(device) for t in host]
+        for k in [k for k in graph._plan_cache if k[:1] == ("smbr",) and k[1:3] == key[1:3]]:
+            del graph._plan_cache[k]
+        graph._plan_cache[key] = hit
+    return hit
+
+
+def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, grad_scale_dev=None):
+    """Lattice-free sMBR on the GPU (include/pychain_hip.h: pychain_hip_smbr_frame_accuracy, then pychain_hip_smbr_forward_backward),
+    on the current stream.  `gt`: smbr_graph(...); `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernels as it is; `gamma`: the
+    denominator's occupancies of x, float32 [B,T,D]; `pdfs` / `probs`: [B,T,K].  Returns (acc_per_seq float64 [B], grad in x's
+    dtype, bad_count int32 [2], closing float32 [B], frame_acc float32 [B,T] - beyond a length not written)."""
+    _require_device(x, "nnet_output")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
+    x = x.detach().contiguous()            # (read one element at a time, csrc/smbr.hip: any element-aligned start will do)
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    L = _lib.lib()
+    dev = x.device
+    H, K = int(num_states), int(gt[0].shape[0])
+    with torch.cuda.device(dev):
+        if gamma.dtype != torch.float32 or tuple(gamma.shape) != (B, T, D) or gamma.device != dev:
+            raise ValueError("smbr: gamma must be a float32 tensor of the network output's shape and device")
+        gamma = gamma.contiguous()
+        ld = _lengths_dev(lengths, dev)
+        pd, pr = _target_args(pdfs, probs, B, T, dev)
+        frame_acc = torch.empty(B, T, dtype=torch.float32, device=dev)
+        acc = torch.empty(B, dtype=torch.float64, device=dev)
+        closing = torch.empty(B, dtype=torch.float32, device=dev)
+        bad = torch.empty(2, dtype=torch.int32, device=dev)
+        grad = torch.empty_like(x)
+        grad_scale_dev = _dev_scalar(grad_scale_dev, dev)
+        _lib.check(L.pychain_hip_smbr_frame_accuracy(
+            gamma.data_ptr(), ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
+            acc.data_ptr(), bad.data_ptr(), _stream(dev)), "pychain_hip_smbr_frame_accuracy")
+        ws = _workspace(L.pychain_hip_smbr_workspace_bytes(B, T, H), dev, "smbr")
+        _lib.check(L.pychain_hip_smbr_forward_backward(
+            *[t.data_ptr() for t in gt], H, K, x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
+            pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale),
+            _ptr(grad_scale_dev), grad.data_ptr(), acc.data_ptr(), closing.data_ptr(), bad.data_ptr(),
+            ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_smbr_forward_backward")
+    return acc, grad, bad, closing, frame_acc
+
+
+def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0):
+    """The same on CPU tensors: the host twins (pychain_hip_cpu_smbr_*), fp32 rows and gradient."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_smbr is for CPU tensors; device tensors run on the HIP kernels")
+    xf, lc = _host_inputs(x, lengths)
+    B, T, D = xf.shape
+    H, K = int(num_states), int(gt[0].shape[0])
+    gamma = gamma.detach().to(torch.float32).contiguous()
+    if tuple(gamma.shape) != (B, T, D):
+        raise ValueError("cpu_smbr: gamma must have the network output's shape")
+    pd, pr = _target_args(pdfs, probs, B, T, torch.device("cpu"))
+    frame_acc = torch.zeros(B, T, dtype=torch.float32)
+    acc = torch.empty(B, dtype=torch.float64)
+    closing = torch.empty(B, dtype=torch.float32)
+    bad = torch.zeros(2, dtype=torch.int32)
+    grad = torch.empty(B, T, D, dtype=torch.float32)
+    L = _lib.lib()
+    _lib.check(L.pychain_hip_cpu_smbr_frame_accuracy(
+        gamma.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
+        acc.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_smbr_frame_accuracy")
+    _lib.check(L.pychain_hip_cpu_smbr_forward_backward(
+        *[t.data_ptr() for t in gt], H, K, xf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]),
+        frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale), None, grad.data_ptr(), acc.data_ptr(),
+        closing.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_smbr_forward_backward")
+    return acc, grad, bad, closing, frame_acc
+
+
 def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     """Sparse targets out of dense posterior rows on the GPU (include/pychain_hip.h: pychain_hip_topk_rows), on the current
     stream: `rows` [B,T,D] in fp32 / bf16 / fp16 as it is.  Returns (pdfs int32 [B,T,k], probs float32 [B,T,k])."""
