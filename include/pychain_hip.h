@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 27
+#define PYCHAIN_HIP_ABI_VERSION 28
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -868,6 +868,69 @@ int pychain_hip_cpu_smbr_forward_backward(
     const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
     float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
     float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Lattice-free sMBR with the accuracy by CLASS (ABI 28): phone-level frame accuracy (Kaldi's --criterion=mpfe),
+ * one class for all silence pdfs (--one-silence-class), or a reference that comes from another tree.  With a map
+ * pdf_classes int32[num_pdfs] (device pointer; host pointer for the twins), every value in [0, num_classes) - NOT checked -
+ *   Acls(t,c) = the sum, in ascending k, of the frame's q_k whose class is c       class_k = pdf_classes[id_k], or id_k itself
+ *   A(t,n)    = Acls(t, pdf_classes[n])                                            when targets_are_classes
+ * and everything else is the section above with this A: e(t), E, the centred a = A - e(t), the recursions, q0, q1, the gradient,
+ * closing and the verdicts.  A row of A is dense now - every pdf of a class takes the credit - so these are kernels of their own
+ * (csrc/smbr.hip: smbr_class_*); the pdf-level entry points launch what they launched.  The identity map gives the pdf-level
+ * quantities (not their bits: the order of the sums differs); one class gives E_b = sum_t sum_k q_k and a zero gradient.
+ * Padding (id < 0) adds nothing; an id that is out of range - >= num_pdfs for pdf targets, >= num_classes for class targets -
+ * adds nothing and is counted in bad_count[1].
+ *
+ * Each entry point takes the arguments of its counterpart above, then pdf_classes, num_classes, targets_are_classes.
+ * pdf_classes NULL is the call above, launch for launch and bit for bit (targets_are_classes must then be 0, num_classes is not
+ * looked at); otherwise num_classes >= 1.
+ * frame_accuracy_classes:   a dense pass over gamma, a wave per frame on a grid over (frames, B): 16-byte loads where num_pdfs is
+ *                           a multiple of 4 and gamma and pdf_classes start on the 16-byte grid, else one element at a time; fp64
+ *                           sums in a fixed order, no float atomics.  It takes a workspace behind the three
+ *                           (pychain_hip_smbr_frame_accuracy_classes_workspace_bytes: the fp64 frame values E_b is summed from).
+ * forward_backward_classes: the recursion workgroup keeps one table [num_classes] more in LDS, the gradient workgroup too:
+ *                           pychain_hip_smbr_lds_bytes is what the larger of the two needs, static LDS included -
+ *                           (4 H + 4 num_pdfs + num_classes + 128) * 4 bytes; num_classes = 0: the pdf-level form - and beyond the
+ *                           160 KiB of a CU the call is refused, PYCHAIN_HIP_EUNSUPPORTED with H, num_pdfs, num_classes and both
+ *                           byte counts in the message.  Workspace: pychain_hip_smbr_workspace_bytes, as above.
+ * The properties of the pdf-level form hold: the same bits on every call; the 2-byte forms compute what the fp32 form computes on
+ * the up-cast input and round once; a pdf no arc carries gets an exact zero, its x unread; rows t >= L_b are exact zeros. */
+size_t pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(int B, int T);
+size_t pychain_hip_smbr_lds_bytes(int num_states, int num_pdfs, int num_classes);
+int pychain_hip_smbr_frame_accuracy_classes(
+    const float* gamma, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K,
+    float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes,
+    void* workspace, size_t workspace_bytes);
+int pychain_hip_smbr_forward_backward_classes(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad /* nnet_output_dtype */, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes);
+/* the host twins: the same equations on host pointers (pdf_classes too), no workspace */
+int pychain_hip_cpu_smbr_frame_accuracy_classes(
+    const float* gamma, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K,
+    float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes);
+int pychain_hip_cpu_smbr_forward_backward_classes(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

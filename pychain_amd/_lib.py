@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 27
+ABI_VERSION = 28
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -47,6 +47,7 @@ _FUSED_TAIL = [_f, _vp, _vp] + _WS + _WS + [_vp]                             # l
 _FORWARD = _FUSED_HEAD + [_vp, _vp, _vp, _f, _vp] + _FUSED_TAIL              # den_objf, num_objf, grad, grad_scale, bad_count
 _FORWARD_BACKWARD = _FUSED_HEAD + [_f] + [_vp] * 4 + _FUSED_TAIL             # grad_scale, den_objf, num_objf, grad, bad_count
 _SMBR_GRAPH = [_vp] * 11 + [_i, _i]                                          # the nine graph tensors, pdf_arcs, pdf_index, H, K
+_SMBR_CLASSES = [_vp, _i, _i]                                                # pdf_classes, num_classes, targets_are_classes
 _SMBR_TAIL = [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]            # targets, K, frame_acc, coef, grad_scale[_dev], grad, acc, closing, bad
 
 _SIGNATURES = {
@@ -117,6 +118,14 @@ _SIGNATURES = {
     "pychain_hip_smbr_forward_backward": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp]),
     "pychain_hip_cpu_smbr_frame_accuracy": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_smbr_forward_backward": (_i, _SMBR_GRAPH + _CPU_ROWS + [_i] * 3 + _SMBR_TAIL + [_i]),
+    # (ABI 28: the same with the accuracy by class - pdf_classes, num_classes, targets_are_classes more, last; the accuracy pass
+    # then takes a workspace)
+    "pychain_hip_smbr_frame_accuracy_classes_workspace_bytes": (_sz, [_i, _i]),
+    "pychain_hip_smbr_lds_bytes": (_sz, [_i, _i, _i]),
+    "pychain_hip_smbr_frame_accuracy_classes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp] + _SMBR_CLASSES + _WS),
+    "pychain_hip_smbr_forward_backward_classes": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp] + _SMBR_CLASSES),
+    "pychain_hip_cpu_smbr_frame_accuracy_classes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i] + _SMBR_CLASSES),
+    "pychain_hip_cpu_smbr_forward_backward_classes": (_i, _SMBR_GRAPH + _CPU_ROWS + [_i] * 3 + _SMBR_TAIL + [_i] + _SMBR_CLASSES),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),

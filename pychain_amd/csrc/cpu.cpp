@@ -811,7 +811,9 @@ extern "C" int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_l
 }
 
 // ---- lattice-free sMBR (include/pychain_hip.h: pychain_hip_smbr_*; the device's smbr.hip): the same equations
-// on host pointers - fp32 state vectors and gradient, fp64 sums; the accuracies centred by the frame accuracies of the first call
+// on host pointers - fp32 state vectors and gradient, fp64 sums; the accuracies centred by the frame accuracies of the first call.
+// With a class map (pychain_hip_cpu_smbr_*_classes) the accuracy row is dense, A(t,n) = Acls(t, cls[n]), and the
+// gradient row is centred by its own mean, as the device's smbr_class_grad_kernel does.
 namespace pychain_hip {
 namespace {
 // the frame's accuracy of pdf d: the sum of its entries' q, in ascending k
@@ -822,18 +824,43 @@ inline float smbr_accuracy(const int32_t* pd, const float* pr, int K, int d) {
   return q;
 }
 
+// accuracy by class: the class of a target id, -1 where it adds nothing; Acls(t, .) of a frame, q summed in
+// ascending k
+struct SmbrHostClasses { const int32_t* cls; int C; bool targets_are_classes; };
+inline int smbr_entry_class(const SmbrHostClasses& c, int id, int D) {
+  if (id < 0) return -1;
+  if (c.targets_are_classes) return id < c.C ? id : -1;
+  return id < D ? c.cls[id] : -1;
+}
+inline void smbr_class_table(const SmbrHostClasses& c, const int32_t* pd, const float* pr, int K, int D, float* acl) {
+  for (int i = 0; i < c.C; i++) acl[i] = 0.f;
+  for (int k = 0; k < K; k++) {
+    const int cc = smbr_entry_class(c, pd[k], D);
+    if (cc >= 0 && cc < c.C) acl[cc] = post_add(acl[cc], pr[k]);
+  }
+}
+
 bool smbr_one(const Csr& fwd, const Csr& bwd, const float* leaky, const float* init, const float* fin, const int32_t* parc, const int32_t* pidx,
               int H, const float* x, int L, int D, const int32_t* pdfs, const float* probs, int K, const float* facc, float coef,
-              float gscale, float* grad, float* closing) {
+              float gscale, float* grad, float* closing, const SmbrHostClasses* cls = nullptr) {
   const size_t rows = (size_t)L + 1;
   std::vector<float> al(rows * H), ab(rows * H, 0.f), be(rows * H), bb(rows * H, 0.f), xr((size_t)D), xa((size_t)D);
+  std::vector<float> acl(cls ? (size_t)cls->C : 0);
   bool ok = true, den_ok = true;                   // what the recursions find; what the gradient frames find
-  auto stage = [&](int t) {                        // x = exp(clamp(y)) and its sparse companion x A
+  auto stage = [&](int t) {                        // x = exp(clamp(y)) and its companion x A: sparse, or dense by class
     const float* y = x + (size_t)t * D;
     for (int n = 0; n < D; n++) {
       if (y[n] != y[n]) ok = false;
       xr[n] = std::exp(y[n] != y[n] ? -30.f : clamp30(y[n]));
       xa[n] = 0.f;
+    }
+    if (cls) {
+      smbr_class_table(*cls, pdfs + (size_t)t * K, probs + (size_t)t * K, K, D, acl.data());
+      for (int n = 0; n < D; n++) {
+        const int cc = cls->cls[n];
+        xa[n] = cc >= 0 && cc < cls->C ? xr[n] * acl[cc] : 0.f;
+      }
+      return;
     }
     for (int k = 0; k < K; k++) {
       const int d = pdfs[(size_t)t * K + k];
@@ -902,8 +929,8 @@ bool smbr_one(const Csr& fwd, const Csr& bwd, const float* leaky, const float* i
     }
     // the gradient of frame t: alpha'(t), alpha-bar'(t), beta'(t+1), beta-bar'(t+1); x and x A of frame t are staged
     const float *a0 = al.data() + (size_t)t * H, *a1 = ab.data() + (size_t)t * H;
-    std::vector<double> v((size_t)D);
-    double den = 0.0;
+    std::vector<double> v((size_t)D), u((size_t)D, 0.0);
+    double den = 0.0, mean = 0.0;
     for (int n = 0; n < D; n++) {
       double q0 = 0.0, q1 = 0.0;
       for (int k = pidx[n]; k < pidx[n + 1]; k++) {
@@ -914,12 +941,16 @@ bool smbr_one(const Csr& fwd, const Csr& bwd, const float* leaky, const float* i
       }
       if (pidx[n] == pidx[n + 1]) { v[n] = 0.0; continue; }
       v[n] = (double)xr[n] * (q1 - (double)facc[t] * q0) + (double)xa[n] * q0;
-      den += (double)xr[n] * q0;
+      u[n] = (double)xr[n] * q0;
+      den += u[n];
+      mean += v[n];
     }
     // the frame's divisor, as the device checks it: it decides the verdict, not `closing` (a diagnostic of the recursions)
     if (!(den > 0.0) || !std::isfinite(den) || !std::isfinite(1.0 / den)) den_ok = false;
     float* go = grad + (size_t)t * D;
-    for (int n = 0; n < D; n++) go[n] = pidx[n] == pidx[n + 1] ? 0.f : (float)((double)gscale * v[n] / den);
+    // by class the row is centred by its own mean, as the device does (smbr.hip: smbr_grad): the residue of e(t)'s rounding
+    const double eps = cls ? mean / den : 0.0;
+    for (int n = 0; n < D; n++) go[n] = pidx[n] == pidx[n + 1] ? 0.f : (float)((double)gscale * (cls ? v[n] - eps * u[n] : v[n]) / den);
   }
   double c0 = 0.0, c1 = 0.0;
   for (int i = 0; i < H; i++) { c0 += (double)al[(size_t)L * H + i] * fin[i]; c1 += (double)ab[(size_t)L * H + i] * fin[i]; }
@@ -930,10 +961,10 @@ bool smbr_one(const Csr& fwd, const Csr& bwd, const float* leaky, const float* i
 }  // namespace
 }  // namespace pychain_hip
 
-extern "C" int pychain_hip_cpu_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
-                                                   const int32_t* target_pdfs, const float* target_probs, int K,
-                                                   float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads) {
-  const char* who = "cpu_smbr_frame_accuracy";
+namespace {
+int cpu_smbr_frame_accuracy(const char* who, const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                            const int32_t* target_pdfs, const float* target_probs, int K,
+                            float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads, const SmbrHostClasses* cls) {
   if (!gamma || !seq_lengths || !target_pdfs || !target_probs || !frame_acc || !acc_per_seq || !bad_count) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
@@ -943,10 +974,20 @@ extern "C" int pychain_hip_cpu_smbr_frame_accuracy(const float* gamma, const int
     const int L = clamped_length(seq_lengths[b], T);
     double sum = 0.0;
     int bad = 0;
+    std::vector<float> acl(cls ? (size_t)cls->C : 0);
     for (int t = 0; t < L; t++) {
       const size_t f = (size_t)b * T + t;
       double e = 0.0;
-      for (int k = 0; k < K; k++) {
+      if (cls) {                                   // e = sum_n gamma(n) Acls(cls[n]), ascending n
+        for (int k = 0; k < K; k++)
+          if (target_pdfs[f * K + k] >= (cls->targets_are_classes ? cls->C : D)) bad++;
+        smbr_class_table(*cls, target_pdfs + f * K, target_probs + f * K, K, D, acl.data());
+        for (int n = 0; n < D; n++) {
+          const int cc = cls->cls[n];
+          if (cc >= 0 && cc < cls->C) e += (double)gamma[f * D + n] * (double)acl[cc];
+        }
+      }
+      for (int k = 0; k < K && !cls; k++) {
         const int d = target_pdfs[f * K + k];
         if (d < 0) continue;
         if (d >= D) { bad++; continue; }
@@ -962,15 +1003,41 @@ extern "C" int pychain_hip_cpu_smbr_frame_accuracy(const float* gamma, const int
   for (int b = 0; b < B; b++) bad_count[1] += bads[b];
   return PYCHAIN_HIP_OK;
 }
+int cpu_bad_classes(const char* who, const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
+  if (!pdf_classes && targets_are_classes) return fail(PYCHAIN_HIP_EINVAL, "%s: targets_are_classes needs pdf_classes", who);
+  if (pdf_classes && num_classes < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: num_classes must be at least 1 with pdf_classes, got %d", who, num_classes);
+  return PYCHAIN_HIP_OK;
+}
+}  // namespace
 
-extern "C" int pychain_hip_cpu_smbr_forward_backward(
+extern "C" int pychain_hip_cpu_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                                   const int32_t* target_pdfs, const float* target_probs, int K,
+                                                   float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads) {
+  return cpu_smbr_frame_accuracy("cpu_smbr_frame_accuracy", gamma, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, acc_per_seq,
+                                 bad_count, num_threads, nullptr);
+}
+
+extern "C" int pychain_hip_cpu_smbr_frame_accuracy_classes(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                                           const int32_t* target_pdfs, const float* target_probs, int K,
+                                                           float* frame_acc, double* acc_per_seq, int32_t* bad_count, int num_threads,
+                                                           const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
+  const char* who = pdf_classes ? "cpu_smbr_frame_accuracy_classes" : "cpu_smbr_frame_accuracy";
+  const int rc = cpu_bad_classes("cpu_smbr_frame_accuracy_classes", pdf_classes, num_classes, targets_are_classes);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  const SmbrHostClasses c{pdf_classes, num_classes, targets_are_classes != 0};
+  return cpu_smbr_frame_accuracy(who, gamma, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, acc_per_seq, bad_count, num_threads,
+                                 pdf_classes ? &c : nullptr);
+}
+
+namespace {
+int cpu_smbr_forward_backward(
+    const char* who,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
     const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
     const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
     float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
-    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads) {
-  const char* who = "cpu_smbr_forward_backward";
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads, const SmbrHostClasses* cls) {
   const NumGraphs g{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
   if (g.any_null() || !leaky || !pdf_arcs || !pdf_index || !nnet_output || !seq_lengths || !target_pdfs || !target_probs || !frame_acc ||
       !grad || !acc_per_seq || !closing || !bad_count)
@@ -988,10 +1055,40 @@ extern "C" int pychain_hip_cpu_smbr_forward_backward(
     const size_t f = (size_t)b * T;
     float* gb = grad + f * D;
     const bool ok = smbr_one(fwd_of(g), bwd_of(g), leaky, initial, final_, pdf_arcs, pdf_index, H, nnet_output + f * D, L, D,
-                             target_pdfs + f * K, target_probs + f * K, K, frame_acc + f, leaky_hmm_coefficient, gscale, gb, closing + b);
+                             target_pdfs + f * K, target_probs + f * K, K, frame_acc + f, leaky_hmm_coefficient, gscale, gb, closing + b, cls);
     for (size_t i = (size_t)L * D; i < (size_t)T * D; i++) gb[i] = 0.f;
     if (!ok) { bad++; acc_per_seq[b] = std::numeric_limits<double>::quiet_NaN(); }
   });
   bad_count[0] += bad.load();
   return PYCHAIN_HIP_OK;
+}
+}  // namespace
+
+extern "C" int pychain_hip_cpu_smbr_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads) {
+  return cpu_smbr_forward_backward("cpu_smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs,
+                                   nnet_output, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, leaky_hmm_coefficient, grad_scale,
+                                   grad_scale_dev, grad, acc_per_seq, closing, bad_count, num_threads, nullptr);
+}
+
+extern "C" int pychain_hip_cpu_smbr_forward_backward_classes(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
+  const int rc = cpu_bad_classes("cpu_smbr_forward_backward_classes", pdf_classes, num_classes, targets_are_classes);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  const SmbrHostClasses c{pdf_classes, num_classes, targets_are_classes != 0};
+  return cpu_smbr_forward_backward(pdf_classes ? "cpu_smbr_forward_backward_classes" : "cpu_smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky,
+                                   initial, final_, pdf_arcs, pdf_index, H, num_arcs, nnet_output, seq_lengths, B, T, D, target_pdfs, target_probs,
+                                   K, frame_acc, leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing, bad_count,
+                                   num_threads, pdf_classes ? &c : nullptr);
 }

@@ -1,6 +1,6 @@
 // smbr.h - launch interface of lattice-free sMBR (smbr.hip; include/pychain_hip.h: pychain_hip_smbr_*): the frame
 // accuracies of a reference under the denominator's occupancies, and the accuracy-weighted recursions whose products are the
-// gradient of the expected accuracy.
+// gradient of the expected accuracy.  Beside the pdf-level form the same by class (§3.27: phone-level accuracy, one silence class).
 #ifndef PYCHAIN_HIP_SMBR_H_
 #define PYCHAIN_HIP_SMBR_H_
 
@@ -50,10 +50,25 @@ struct SmbrArgs {
   int B, T, D, Kt;
 };
 
+// Accuracy by CLASS: A(t,n) = Acls(t, cls[n]), Acls(t,c) = the sum of the frame's q_k whose class is c - the
+// class of entry k is cls[id_k], or id_k itself where the targets name classes.  A row of x A is then dense.  The class kernels
+// take this beside the pdf-level argument structs, which keep their layout.
+struct SmbrClasses {
+  const int32_t* cls;        // [D] pdf -> class, every value in [0, C) (NOT checked: device memory)
+  int C;
+  int targets_are_classes;   // the ids of the targets are classes: >= C counted, instead of pdfs: >= D counted
+  double* frame_e;           // workspace of the accuracy pass: [B,T] e(b,t) in fp64, live frames only
+};
+
 size_t smbr_recursion_lds(int H, int D);            // bytes of LDS the recursion workgroup needs
 size_t smbr_grad_lds(int H, int D);
+size_t smbr_recursion_lds(int H, int D, int C);     // ... the class form: one table [C] more
+size_t smbr_grad_lds(int H, int D, int C);
+size_t smbr_lds_bytes(int H, int D, int C);         // the larger of the two, static LDS included; C = 0: the pdf-level form
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st);
 hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st);     // the recursion launch, then the gradient launch
+hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hipStream_t st);   // the dense pass, then the per-sequence sums
+hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st);
 
 }  // namespace pychain_hip
 #endif

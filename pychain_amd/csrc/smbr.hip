@@ -18,6 +18,17 @@
 //                              q0 = sum p alpha' beta',  q1 = sum p (alpha-bar' beta' + alpha' beta-bar')
 //                              grad = s x (q1 + a q0) / sum_m x(m) q0(m)
 //                            The frame's normalisers cancel in the quotient, as in den_general_gamma_kernel.
+//
+// The same with the accuracy by CLASS (pychain_hip_smbr_*_classes): A(t,n) = Acls(t, cls[n]) for a map cls from
+// pdf to class, Acls(t,c) = the sum of the frame's q_k whose class is c.  A row of A is dense then, which none of the three
+// kernels above can take, so each has a counterpart; the pdf-level kernels keep their code.
+//   smbr_class_frame_acc_kernel   a dense pass over gamma: a wave per frame on a grid over (frames, B), the frame's entries merged
+//                                 into distinct classes first, fp64 sums in a fixed order; smbr_class_seq_acc_kernel sums E_b
+//   smbr_class_recursion_kernel   smbr_recursion with CLS: one table Acls(t, .) in LDS, written for the next frame before the arc
+//                                 loop; the dense companion row x A is made behind the reduction's barrier, where the pdf-level
+//                                 form scatters its K entries.  No barrier more, the arc loop unchanged.
+//   smbr_class_grad_kernel        the frame's table made beside the state rows; every carried pdf takes its class's credit; the
+//                                 row is centred by its own mean (the residue of e(t)'s rounding, which a dense A would spread)
 // Nothing is atomic but integer counters and flags; every sum has a fixed order, so a call gives the same bits every time.  All of
 // this unit's device code, the helpers of the project's headers included, is compiled with contraction off: the 2-byte forms then compute what the fp32 form computes on the up-cast input.
 #include <hip/hip_runtime.h>
@@ -74,6 +85,23 @@ __device__ __forceinline__ void scatter_entries(const int32_t* pd, const float* 
     if (owned_entry(pd, pr, k, Kt, D, d, q)) xacc[d] = xrow[d] * q;
 }
 
+// ---- accuracy by class (§3.27) ----------------------------------------------------------------------------------------------------
+// the class of a target id, -1 where it adds nothing: padding, a pdf >= D, a class >= C
+__device__ __forceinline__ int entry_class(const SmbrClasses& c, int id, int D) {
+  if (id < 0) return -1;
+  if (c.targets_are_classes) return id < c.C ? id : -1;
+  return id < D ? c.cls[id] : -1;
+}
+// Acls(t, .) of a frame into `acl` [C]: thread tid, tid + nt, ... sums the q of its class in ascending k - one owner, no atomics
+__device__ __forceinline__ void class_table(const SmbrClasses& c, const int32_t* pd, const float* pr, int Kt, int D, int tid, int nt, float* acl) {
+  for (int cc = tid; cc < c.C; cc += nt) {
+    float q = 0.f;
+    for (int k = 0; k < Kt; k++)
+      if (entry_class(c, pd[k], D) == cc) q += pr[k];
+    acl[cc] = q;
+  }
+}
+
 // ---- stage 1: frame accuracies ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSmAccNT) void smbr_frame_acc_kernel(const SmbrAccArgs a) {
   __shared__ double red[kSmAccNT / 64];
@@ -108,6 +136,91 @@ __global__ __launch_bounds__(kSmAccNT) void smbr_frame_acc_kernel(const SmbrAccA
   }
 }
 
+// The same by class: e(b,t) = sum_n gamma(b,t,n) Acls(t, cls[n]) is a dense pass over gamma, so a wave takes a frame on a grid over
+// (frames, B) - kSmAccWaves frames a workgroup, no barrier.  The frame's entries are merged first: lane k keeps (class, summed q)
+// of entry k where its class occurs first in the frame, q summed in ascending k (entries beyond 64: in chunks of a wave).  Every
+// lane then walks its elements in ascending n against the merged entries, read lane by lane; the products are summed in fp64 per
+// lane and over the wave by the butterfly.  E_b is summed from the fp64 frame values by a launch of its own.
+constexpr int kSmAccWaves = kSmAccNT / 64;
+template <int VW>
+__global__ __launch_bounds__(kSmAccNT) void smbr_class_frame_acc_kernel(const SmbrAccArgs a, const SmbrClasses c) {
+  const int lane = threadIdx.x & 63, b = blockIdx.y;
+  const int t = blockIdx.x * kSmAccWaves + (threadIdx.x >> 6);
+  if (t >= seq_len(a.lengths, b, a.T)) return;                                 // (the whole wave)
+  const size_t f = (size_t)b * a.T + t;
+  const int32_t* pd = a.pdfs + f * a.Kt;
+  const float* pr = a.probs + f * a.Kt;
+  const float* g = a.gamma + f * a.D;
+  const int D = a.D, Kt = a.Kt;
+  double e = 0.0;
+  int bad = 0;
+  for (int k0 = 0; k0 < Kt; k0 += 64) {
+    const int k = k0 + lane;
+    int mc = -1;
+    float mq = 0.f;
+    if (k < Kt) {
+      if (pd[k] >= (c.targets_are_classes ? c.C : D)) bad++;
+      mc = entry_class(c, pd[k], D);
+      for (int j = 0; j < k && mc >= 0; j++)
+        if (entry_class(c, pd[j], D) == mc) mc = -1;
+      if (mc >= 0) {
+        mq = pr[k];
+        for (int j = k + 1; j < Kt; j++)
+          if (entry_class(c, pd[j], D) == mc) mq += pr[j];
+      }
+    }
+    const int live = min(64, Kt - k0);
+    for (int base = 0; base < D; base += 64 * VW) {                            // (the same trips in every lane: the lane reads below)
+      const int n0 = base + lane * VW;
+      float v[VW], av[VW];
+      int cn[VW];
+#pragma unroll
+      for (int i = 0; i < VW; i++) { v[i] = 0.f; av[i] = 0.f; cn[i] = -2; }
+      if (n0 < D) {
+        row_load<kXF32, VW>(g, (size_t)n0, v);
+        if constexpr (VW == 4) {
+          const int4 q = *reinterpret_cast<const int4*>(c.cls + n0);
+          cn[0] = q.x; cn[1] = q.y; cn[2] = q.z; cn[3] = q.w;
+        } else {
+          cn[0] = c.cls[n0];
+        }
+      }
+      for (int j = 0; j < live; j++) {
+        const int jc = __builtin_amdgcn_readlane(mc, j);
+        const float jq = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mq), j));
+#pragma unroll
+        for (int i = 0; i < VW; i++)
+          if (cn[i] == jc) av[i] = jq;                                         // (at most one merged entry has the class)
+      }
+#pragma unroll
+      for (int i = 0; i < VW; i++) e += (double)v[i] * (double)av[i];
+    }
+  }
+  e = wave_sum_f64(e);
+  for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o);
+  if (lane == 0) {
+    a.frame_acc[f] = (float)e;
+    c.frame_e[f] = e;
+    if (bad) atomicAdd(a.bad_count + 1, bad);                                  // (an integer sum: the same value in any order)
+  }
+}
+// E_b = sum_t e(b,t) in fp64: one workgroup per sequence, a thread per frame, the order of smbr_frame_acc_kernel
+__global__ __launch_bounds__(kSmAccNT) void smbr_class_seq_acc_kernel(const SmbrAccArgs a, const SmbrClasses c) {
+  __shared__ double red[kSmAccNT / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int L = seq_len(a.lengths, b, a.T);
+  double sum = 0.0;
+  for (int t = tid; t < L; t += kSmAccNT) sum += c.frame_e[(size_t)b * a.T + t];
+  sum = wave_sum_f64(sum);
+  if ((tid & 63) == 0) red[tid >> 6] = sum;
+  __syncthreads();
+  if (tid == 0) {
+    double s = 0.0;
+    for (int w = 0; w < kSmAccNT / 64; w++) s += red[w];
+    a.acc_per_seq[b] = s;
+  }
+}
+
 // ---- stage 2: the recursions ----------------------------------------------------------------------------------------------------
 // row t of the sequence into LDS as exp(clamp(.)); elements tid + i * NT, i < kSmXR, come from `held` (loaded before the arc loop)
 template <int XH>
@@ -134,8 +247,21 @@ __device__ __forceinline__ bool put_row(const void* x, size_t row, int D, int ti
   return nan;
 }
 
-template <int XH, bool FWD>
-__device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* lds) {
+// x A of the elements put_row stored, by class: xacc[n] = xrow[n] * acl[cls[n]] - the thread reads back what it wrote itself;
+// `hc`: cls of the elements held in registers, those beyond are loaded again
+__device__ __forceinline__ void class_row(const int32_t* cls, const int (&hc)[kSmXR], int D, int tid, const float* acl, const float* xrow, float* xacc) {
+#pragma unroll
+  for (int i = 0; i < kSmXR; i++) {
+    const int n = tid + i * kSmNT;
+    if (n < D) xacc[n] = xrow[n] * acl[hc[i]];
+  }
+  for (int n = tid + kSmXR * kSmNT; n < D; n += kSmNT) xacc[n] = xrow[n] * acl[cls[n]];
+}
+
+// CLS: the accuracy by class (§3.27) - `c` is read, the table acl [C] lies behind the reduction scratch, and the companion row is
+// dense: made from the next row and the next frame's table in the slot where the pdf-level form scatters its K entries.
+template <int XH, bool FWD, bool CLS>
+__device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, const SmbrClasses& c, int b, float* lds) {
   const int tid = threadIdx.x;
   const SmbrGraph& g = a.g;
   const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
@@ -145,6 +271,12 @@ __device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* 
   float* const xrow = vec1 + 2 * (size_t)H;      // [2][D] x
   float* const xacc = xrow + 2 * (size_t)D;      // [2][D] x * A
   float* const red = xacc + 2 * (size_t)D;
+  float* const acl = red + kSmRed;               // [C] Acls of the frame whose companion row is made next (CLS)
+  int hc[kSmXR];
+  if constexpr (CLS) {
+#pragma unroll
+    for (int i = 0; i < kSmXR; i++) hc[i] = tid + i * kSmNT < D ? c.cls[tid + i * kSmNT] : 0;
+  }
   const size_t seq_rows = (size_t)b * (T + 1);
   float* const st0 = (FWD ? a.al : a.be) + seq_rows * H;
   float* const st1 = (FWD ? a.ab : a.bb) + seq_rows * H;
@@ -175,9 +307,15 @@ __device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* 
     float held[kSmXR];
     hold_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held);
     nan = put_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held, xrow) || nan;
-    for (int n = tid; n < D; n += kSmNT) xacc[n] = 0.f;
-    __syncthreads();
-    scatter_entries(a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, xrow, xacc);
+    if constexpr (CLS) {
+      class_table(c, a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, acl);
+      __syncthreads();
+      class_row(c.cls, hc, D, tid, acl, xrow, xacc);
+    } else {
+      for (int n = tid; n < D; n += kSmNT) xacc[n] = 0.f;
+      __syncthreads();
+      scatter_entries(a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, xrow, xacc);
+    }
     __syncthreads();
   }
   // frame j: forwards alpha'(t+1) from alpha'(t) and x(t), t = j; backwards beta'(t) from beta'(t+1) and x(t), t = L-1-j
@@ -195,7 +333,11 @@ __device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* 
     float* xan = xacc + (size_t)(1 - p) * D;
     float held[kSmXR];
     if (more) hold_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held);          // the next frame's row: in flight over the arc loop
-    for (int n = tid; n < D; n += kSmNT) xan[n] = 0.f;
+    if constexpr (CLS) {                                                       // (the table's readers are behind the last barrier)
+      if (more) class_table(c, a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, acl);
+    } else {
+      for (int n = tid; n < D; n += kSmNT) xan[n] = 0.f;
+    }
     const float e_t = a.frame_acc[fseq + t];
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int i = tid; i < H; i += kSmNT) {
@@ -216,7 +358,11 @@ __device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, int b, float* 
     }
     if (more) nan = put_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held, xrn) || nan;
     block_sum3<kSmNT>(s0, s1, s2, red, tid);                                   // (its barrier: the next rows are whole)
-    if (more) scatter_entries(a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, xrn, xan);
+    if constexpr (CLS) {
+      if (more) class_row(c.cls, hc, D, tid, acl, xrn, xan);
+    } else {
+      if (more) scatter_entries(a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, xrn, xan);
+    }
     const float inv = 1.f / s0;
     if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
     const int r = FWD ? t + 1 : t;
@@ -247,8 +393,15 @@ template <int XH>
 __global__ __launch_bounds__(kSmNT) void smbr_recursion_kernel(const SmbrArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* lds = reinterpret_cast<float*>(smem_raw);
-  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true>(a, blockIdx.x, lds);
-  else smbr_recursion<XH, false>(a, blockIdx.x - a.B, lds);
+  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true, false>(a, SmbrClasses{}, blockIdx.x, lds);
+  else smbr_recursion<XH, false, false>(a, SmbrClasses{}, blockIdx.x - a.B, lds);
+}
+template <int XH>
+__global__ __launch_bounds__(kSmNT) void smbr_class_recursion_kernel(const SmbrArgs a, const SmbrClasses c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true, true>(a, c, blockIdx.x, lds);
+  else smbr_recursion<XH, false, true>(a, c, blockIdx.x - a.B, lds);
 }
 
 // ---- stage 2: the gradient ------------------------------------------------------------------------------------------------------
@@ -342,6 +495,101 @@ __global__ __launch_bounds__(kSmGNT) void smbr_grad_kernel(const SmbrArgs a) {
   }
 }
 
+// The same by class (§3.27): smbr_grad_kernel with the frame's table acl [C] made beside the state rows, and every carried pdf
+// taking its class's credit in the pass that forms it, where the pdf-level form adds the K owned entries behind the reduction.
+template <int XH>
+__global__ __launch_bounds__(kSmGNT) void smbr_class_grad_kernel(const SmbrArgs a, const SmbrClasses c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const SmbrGraph& g = a.g;
+  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
+  const int L = seq_len(a.lengths, b, T);
+  float* const sa = lds;                          // alpha'(t)
+  float* const sab = sa + H;                      // alpha-bar'(t)
+  float* const sb = sab + H;                      // beta'(t+1)
+  float* const sbb = sb + H;                      // beta-bar'(t+1)
+  float* const gq = sbb + H;                      // [D] x q0
+  float* const gv = gq + D;                       // [D] x (q1 + a q0)
+  float* const red = gv + D;
+  float* const acl = red + kSmRed;                // [C] Acls of the frame
+  const size_t seq_rows = (size_t)b * (T + 1);
+  const float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
+  const int t_begin = blockIdx.x * kSmFrames, t_end = min(t_begin + kSmFrames, T);
+  for (int t = t_begin; t < t_end; t++) {
+    const size_t row = ((size_t)b * T + t) * D;
+    if (t >= L) {                                                              // padding: exact zeros
+      for (int n = tid; n < D; n += kSmGNT) row_store1<XH>(a.grad, row + n, 0.f);
+      continue;
+    }
+    const size_t r0 = (seq_rows + t) * H, r1 = r0 + H;
+    for (int i = tid; i < H; i += kSmGNT) { sa[i] = a.al[r0 + i]; sab[i] = a.ab[r0 + i]; sb[i] = a.be[r1 + i]; sbb[i] = a.bb[r1 + i]; }
+    class_table(c, a.pdfs + ((size_t)b * T + t) * Kt, a.probs + ((size_t)b * T + t) * Kt, Kt, D, tid, kSmGNT, acl);
+    __syncthreads();
+    const float e_t = a.frame_acc[(size_t)b * T + t];
+    float part = 0.f, none1 = 0.f, none2 = 0.f;
+    for (int n = tid; n < D; n += kSmGNT) {
+      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
+      float q0 = 0.f, q1 = 0.f;
+      for (int k = k0; k < k1; k++) {
+        const int id = g.parc[k];
+        const int src = g.ft[3 * id], dst = g.ft[3 * id + 1];
+        const float w = g.fp[id];
+        const float wa = w * sa[src];
+        q0 += wa * sb[dst];
+        q1 += (w * sab[src]) * sb[dst] + wa * sbb[dst];
+      }
+      float v0 = 0.f, v1 = 0.f;
+      if (k0 != k1) {                                                          // a pdf no arc carries: its x is not read
+        const float xx = clamp_exp(row_load1<XH>(a.x, row + n), kXExpClamp);
+        v0 = xx * q0;
+        v1 = xx * (q1 - e_t * q0);
+        v1 += acl[c.cls[n]] * v0;                                             // (+ A x q0: the thread's own element)
+      }
+      gq[n] = v0; gv[n] = v1;
+      part += v0;
+      none1 += v1;
+    }
+    block_sum3<kSmGNT>(part, none1, none2, red, tid);                          // (below a thread reads its own elements only)
+    const float sc = gscale / part, inv = 1.f / part;
+    if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) smbr_condemn(a, b);    // (the host twin's check of the same divisor)
+    // The row is centred by its own mean: sum_n x (q1 + a q0) is zero but for the rounding of e(t) - the occupancies are another
+    // kernel's, in fp32 -, and with a dense A of order one that residue, times gamma(t,n), is what the row would carry.
+    const float eps = none1 * inv;
+    for (int n = tid; n < D; n += kSmGNT) {
+      const bool carried = g.pidx[n] != g.pidx[n + 1];
+      row_store1<XH>(a.grad, row + n, carried ? (gv[n] - eps * gq[n]) * sc : 0.f);
+    }
+    __syncthreads();                                                           // (the rows are free for the next frame)
+  }
+  // the sequence's first workgroup closes it: the diagnostic sum_j alpha-bar'(L,j) final(j) / sum_j alpha'(L,j) final(j), and the
+  // sequence's verdict
+  if (blockIdx.x == 0) {
+    const size_t rL = (seq_rows + L) * H;
+    float c0 = 0.f, c1 = 0.f, none = 0.f;
+    for (int i = tid; i < H; i += kSmGNT) { c0 += a.al[rL + i] * g.fin[i]; c1 += a.ab[rL + i] * g.fin[i]; }
+    block_sum3<kSmGNT>(c0, c1, none, red, tid);
+    if (tid == 0) {
+      const bool bad = a.seq_bad[b] != 0 || !(c0 > 0.f);                       // what the recursions found
+      a.closing[b] = bad ? __builtin_nanf("") : c1 / c0;
+      if (bad) smbr_condemn(a, b);
+    }
+  }
+}
+template <int XH>
+hipError_t launch_classes_as(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st) {
+  const size_t lds_r = smbr_recursion_lds(a.g.H, a.D, c.C), lds_g = smbr_grad_lds(a.g.H, a.D, c.C);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_class_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_class_grad_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((smbr_class_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a, c);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((smbr_class_grad_kernel<XH>), dim3((a.T + kSmFrames - 1) / kSmFrames, a.B), dim3(kSmGNT), lds_g, st, a, c);
+  return hipGetLastError();
+}
+
 template <int XH>
 hipError_t launch_as(const SmbrArgs& a, hipStream_t st) {
   const size_t lds_r = smbr_recursion_lds(a.g.H, a.D), lds_g = smbr_grad_lds(a.g.H, a.D);
@@ -360,6 +608,12 @@ hipError_t launch_as(const SmbrArgs& a, hipStream_t st) {
 
 size_t smbr_recursion_lds(int H, int D) { return (4 * (size_t)H + 4 * (size_t)D + kSmRed) * sizeof(float); }
 size_t smbr_grad_lds(int H, int D) { return (4 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
+size_t smbr_recursion_lds(int H, int D, int C) { return smbr_recursion_lds(H, D) + (size_t)C * sizeof(float); }
+size_t smbr_grad_lds(int H, int D, int C) { return smbr_grad_lds(H, D) + (size_t)C * sizeof(float); }
+size_t smbr_lds_bytes(int H, int D, int C) {       // (the gradient kernel has no static LDS, and fewer rows)
+  const size_t r = smbr_recursion_lds(H, D, C) + kSmStaticLds, g = smbr_grad_lds(H, D, C);
+  return r > g ? r : g;
+}
 
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st) {
   hipError_t e = hipMemsetAsync(a.bad_count, 0, 2 * sizeof(int32_t), st);
@@ -374,6 +628,28 @@ hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st) {
   if (a.x_half == kXF32) return launch_as<kXF32>(a, st);
   if (a.x_half == kXBf16) return launch_as<kXBf16>(a, st);
   return launch_as<kXF16>(a, st);
+}
+
+hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.bad_count, 0, 2 * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  const dim3 grid((a.T + kSmAccWaves - 1) / kSmAccWaves, a.B);
+  // float4 / int4 loads where every row of gamma and the map start on the 16-byte grid, else one element at a time
+  const bool wide = a.D % 4 == 0 && ((uintptr_t)a.gamma | (uintptr_t)c.cls) % 16 == 0;
+  if (wide) hipLaunchKernelGGL(smbr_class_frame_acc_kernel<4>, grid, dim3(kSmAccNT), 0, st, a, c);
+  else hipLaunchKernelGGL(smbr_class_frame_acc_kernel<1>, grid, dim3(kSmAccNT), 0, st, a, c);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(smbr_class_seq_acc_kernel, dim3(a.B), dim3(kSmAccNT), 0, st, a, c);
+  return hipGetLastError();
+}
+
+hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.seq_bad, 0, 2 * (size_t)a.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  if (a.x_half == kXF32) return launch_classes_as<kXF32>(a, c, st);
+  if (a.x_half == kXBf16) return launch_classes_as<kXBf16>(a, c, st);
+  return launch_classes_as<kXF16>(a, c, st);
 }
 
 }  // namespace pychain_hip
@@ -400,10 +676,31 @@ extern "C" size_t pychain_hip_smbr_workspace_bytes(int B, int T, int H) {
   return smbr_carve(B, T, H).total;
 }
 
-extern "C" int pychain_hip_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
-                                               const int32_t* target_pdfs, const float* target_probs, int K,
-                                               float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream) {
-  const char* who = "smbr_frame_accuracy";
+extern "C" size_t pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(int B, int T) {
+  if (B <= 0 || T <= 0) return 0;
+  return align256((size_t)B * T * sizeof(double)) + 256;
+}
+
+extern "C" size_t pychain_hip_smbr_lds_bytes(int H, int D, int num_classes) {
+  if (H <= 0 || D <= 0 || num_classes < 0) return 0;
+  return smbr_lds_bytes(H, D, num_classes);
+}
+
+namespace {
+// what a class call says of its map: `cls` is the caller's, non-null
+int bad_classes(const char* who, int num_classes) {
+  if (num_classes < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: num_classes must be at least 1 with pdf_classes, got %d", who, num_classes);
+  return PYCHAIN_HIP_OK;
+}
+int classes_without_map(const char* who) {
+  return fail(PYCHAIN_HIP_EINVAL, "%s: targets_are_classes needs pdf_classes", who);
+}
+
+// both accuracy entry points; `pdf_classes` null: the pdf-level launch
+int smbr_frame_accuracy(const char* who, const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                        const int32_t* target_pdfs, const float* target_probs, int K,
+                        float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream,
+                        const int32_t* pdf_classes, int num_classes, int targets_are_classes, void* workspace, size_t workspace_bytes) {
   if (!gamma || !seq_lengths || !target_pdfs || !target_probs || !frame_acc || !acc_per_seq || !bad_count) return null_pointer(who);
   if (B <= 0 || T <= 0 || D <= 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes B=%d T=%d D=%d", who, B, T, D);
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
@@ -412,20 +709,55 @@ extern "C" int pychain_hip_smbr_frame_accuracy(const float* gamma, const int64_t
   memset(&a, 0, sizeof(a));
   a.gamma = gamma; a.lengths = seq_lengths; a.pdfs = target_pdfs; a.probs = target_probs; a.frame_acc = frame_acc;
   a.acc_per_seq = acc_per_seq; a.bad_count = bad_count; a.B = B; a.T = T; a.D = D; a.Kt = K;
-  const hipError_t err = launch_smbr_frame_acc(a, (hipStream_t)stream);
+  hipError_t err;
+  if (pdf_classes) {
+    const int rc = bad_classes(who, num_classes);
+    if (rc != PYCHAIN_HIP_OK) return rc;
+    if (!workspace) return null_pointer(who);
+    const size_t need = pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(B, T);
+    if (workspace_bytes < need) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
+    const SmbrClasses c{pdf_classes, num_classes, targets_are_classes != 0, (double*)ws_base(workspace)};
+    err = launch_smbr_frame_acc(a, c, (hipStream_t)stream);
+  } else {
+    err = launch_smbr_frame_acc(a, (hipStream_t)stream);
+  }
   if (err != hipSuccess) return launch_failed(who, err, nullptr);
   return PYCHAIN_HIP_OK;
 }
+}  // namespace
 
-extern "C" int pychain_hip_smbr_forward_backward(
+extern "C" int pychain_hip_smbr_frame_accuracy(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                               const int32_t* target_pdfs, const float* target_probs, int K,
+                                               float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream) {
+  return smbr_frame_accuracy("smbr_frame_accuracy", gamma, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, acc_per_seq, bad_count,
+                             stream, nullptr, 0, 0, nullptr, 0);
+}
+
+extern "C" int pychain_hip_smbr_frame_accuracy_classes(const float* gamma, const int64_t* seq_lengths, int B, int T, int D,
+                                                       const int32_t* target_pdfs, const float* target_probs, int K,
+                                                       float* frame_acc, double* acc_per_seq, int32_t* bad_count, void* stream,
+                                                       const int32_t* pdf_classes, int num_classes, int targets_are_classes,
+                                                       void* workspace, size_t workspace_bytes) {
+  if (!pdf_classes) {                              // the pdf-level call, launch for launch
+    if (targets_are_classes) return classes_without_map("smbr_frame_accuracy_classes");
+    return pychain_hip_smbr_frame_accuracy(gamma, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, acc_per_seq, bad_count, stream);
+  }
+  return smbr_frame_accuracy("smbr_frame_accuracy_classes", gamma, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc, acc_per_seq,
+                             bad_count, stream, pdf_classes, num_classes, targets_are_classes, workspace, workspace_bytes);
+}
+
+namespace {
+// both recursion entry points; `pdf_classes` null: the pdf-level launches
+int smbr_forward_backward(
+    const char* who,
     const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
     const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
     const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
     const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
     float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
     void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
-    void* workspace, size_t workspace_bytes, void* stream) {
-  const char* who = "smbr_forward_backward";
+    void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
   const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
   const Rows rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D};
   int rc = bad_dtype(who, nnet_output_dtype);
@@ -437,8 +769,15 @@ extern "C" int pychain_hip_smbr_forward_backward(
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
   if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
     return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  if (pdf_classes) {
+    if ((rc = bad_classes(who, num_classes)) != PYCHAIN_HIP_OK) return rc;
+    const size_t need = smbr_lds_bytes(H, D, num_classes);
+    if (need > kSmbrLdsBudget)
+      return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states, %d pdfs and %d classes need %zu bytes of LDS (four state vectors, four rows and the class table), a CU has %zu",
+                  who, H, D, num_classes, need, kSmbrLdsBudget);
+  }
   const size_t lds = smbr_recursion_lds(H, D);
-  if (lds + kSmStaticLds > kSmbrLdsBudget)
+  if (!pdf_classes && lds + kSmStaticLds > kSmbrLdsBudget)
     return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states and %d pdfs need %zu bytes of LDS (four state vectors and four rows), a CU has %zu",
                 who, H, D, lds + kSmStaticLds, kSmbrLdsBudget);
   if ((size_t)B * (T + 1) > (size_t)INT_MAX) return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: B * (T + 1) = %zu rows", who, (size_t)B * (T + 1));
@@ -454,7 +793,39 @@ extern "C" int pychain_hip_smbr_forward_backward(
   a.al = (float*)(base + c.al); a.ab = (float*)(base + c.ab); a.be = (float*)(base + c.be); a.bb = (float*)(base + c.bb);
   a.tot_a = (float*)(base + c.tot_a); a.tot_b = (float*)(base + c.tot_b); a.seq_bad = (int32_t*)(base + c.seq_bad);
   a.B = B; a.T = T; a.D = D; a.Kt = K;
-  const hipError_t err = launch_smbr(a, (hipStream_t)stream);
+  const hipError_t err = pdf_classes ? launch_smbr(a, SmbrClasses{pdf_classes, num_classes, targets_are_classes != 0, nullptr}, (hipStream_t)stream)
+                                     : launch_smbr(a, (hipStream_t)stream);
   if (err != hipSuccess) return launch_failed(who, err, nullptr);
   return PYCHAIN_HIP_OK;
+}
+}  // namespace
+
+extern "C" int pychain_hip_smbr_forward_backward(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  return smbr_forward_backward("smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs,
+                               nnet_output, nnet_output_dtype, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc,
+                               leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing, bad_count,
+                               workspace, workspace_bytes, stream, nullptr, 0, 0);
+}
+
+extern "C" int pychain_hip_smbr_forward_backward_classes(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
+  if (!pdf_classes && targets_are_classes) return classes_without_map("smbr_forward_backward_classes");
+  return smbr_forward_backward(pdf_classes ? "smbr_forward_backward_classes" : "smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky, initial,
+                               final_, pdf_arcs, pdf_index, H, num_arcs, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, target_pdfs,
+                               target_probs, K, frame_acc, leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing,
+                               bad_count, workspace, workspace_bytes, stream, pdf_classes, num_classes, targets_are_classes);
 }

@@ -585,6 +585,20 @@ class PosteriorTargets(object):
         return PosteriorTargets._of(self.pdfs.index_select(0, idx.to(self.pdfs.device)).contiguous(),
                                     self.probs.index_select(0, idx.to(self.probs.device)).contiguous())
 
+    def to_classes(self, classes):
+        """The same targets with every id mapped through `classes` (an integer tensor [D], pdf -> class): what
+        expected_accuracy(..., classes=classes, targets_are_classes=True) takes.  Padding stays padding; a pdf out of range
+        (>= D) stays out of range (>= max(classes) + 1)."""
+        classes = torch.as_tensor(classes)
+        if classes.dim() != 1 or classes.is_floating_point() or classes.dtype == torch.bool or classes.numel() < 1:
+            raise ValueError("to_classes: classes must be an integer tensor [D]")
+        cl = classes.detach().to(device=self.pdfs.device, dtype=torch.int64)
+        D, C = int(cl.numel()), int(cl.max()) + 1
+        ids = self.pdfs.to(torch.int64)
+        mapped = cl[ids.clamp(0, D - 1)]
+        out = torch.where(ids < 0, ids, torch.where(ids >= D, ids.clamp_min(C), mapped))
+        return PosteriorTargets._of(out.to(torch.int32).contiguous(), self.probs)
+
     def check(self, B, T, D):
         """Against the network output [B,T,D] of a call: the shape, and - host tensors only - every pdf below D."""
         if tuple(self.pdfs.shape[:2]) != (B, T):

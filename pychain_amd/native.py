@@ -717,11 +717,53 @@ def smbr_graph(graph, D, device):
     return hit
 
 
-def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, grad_scale_dev=None):
+_smbr_classes_cache = {}
+
+
+def smbr_classes(classes, D, device):
+    """(the map pdf -> class as a contiguous int32 tensor [D] on `device`, C = max + 1) of `classes`, an integer tensor [D] without
+    a negative entry: checked on the host and uploaded once per (tensor, D, device) - cached until the tensor is replaced or
+    edited in place, one map per device (as smbr_graph caches the graph's tensors)."""
+    if not torch.is_tensor(classes):
+        classes = torch.as_tensor(classes)
+    key = (id(classes), classes.data_ptr(), classes._version, int(D))
+    hit = _smbr_classes_cache.get(str(device))
+    if hit is None or hit[0] != key or hit[1] is not classes:
+        if classes.is_floating_point() or classes.is_complex() or classes.dtype == torch.bool:
+            raise ValueError("classes must be an integer tensor, got %s" % classes.dtype)
+        if classes.dim() != 1 or classes.numel() != D:
+            raise ValueError("classes must be [D] = [%d], one class per pdf, got %s" % (D, list(classes.shape)))
+        lo, hi = int(classes.min()), int(classes.max())
+        if lo < 0:
+            raise ValueError("classes holds a negative entry (%d)" % lo)
+        if hi >= 2 ** 31 - 1:
+            raise ValueError("classes names class %d: beyond int32" % hi)
+        hit = (key, classes, classes.detach().to(device=device, dtype=torch.int32).contiguous(), hi + 1)
+        _smbr_classes_cache[str(device)] = hit
+    return hit[2], hit[3]
+
+
+def _classes_args(classes, num_classes, targets_are_classes, D, device, who):
+    """The three trailing arguments of the *_classes entry points; `classes` None: the pdf-level call."""
+    if classes is None:
+        if targets_are_classes:
+            raise ValueError("%s: targets_are_classes needs classes" % who)
+        return None
+    if classes.dtype != torch.int32 or tuple(classes.shape) != (D,) or classes.device != device or not classes.is_contiguous():
+        raise ValueError("%s: classes must be a contiguous int32 tensor [D] on the network output's device (native.smbr_classes)" % who)
+    if int(num_classes) < 1:
+        raise ValueError("%s: num_classes must be at least 1, got %s" % (who, num_classes))
+    return classes, int(num_classes), int(bool(targets_are_classes))
+
+
+def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, grad_scale_dev=None, *,
+         classes=None, num_classes=0, targets_are_classes=False):
     """Lattice-free sMBR on the GPU (include/pychain_hip.h: pychain_hip_smbr_frame_accuracy, then pychain_hip_smbr_forward_backward),
     on the current stream.  `gt`: smbr_graph(...); `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernels as it is; `gamma`: the
     denominator's occupancies of x, float32 [B,T,D]; `pdfs` / `probs`: [B,T,K].  Returns (acc_per_seq float64 [B], grad in x's
-    dtype, bad_count int32 [2], closing float32 [B], frame_acc float32 [B,T] - beyond a length not written)."""
+    dtype, bad_count int32 [2], closing float32 [B], frame_acc float32 [B,T] - beyond a length not written).  With `classes`
+    (smbr_classes(...): int32 [D] on the device) and `num_classes` the accuracy is by class (the *_classes entry points);
+    `targets_are_classes`: the ids of `pdfs` are classes already."""
     _require_device(x, "nnet_output")
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
@@ -743,19 +785,30 @@ def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5,
         bad = torch.empty(2, dtype=torch.int32, device=dev)
         grad = torch.empty_like(x)
         grad_scale_dev = _dev_scalar(grad_scale_dev, dev)
-        _lib.check(L.pychain_hip_smbr_frame_accuracy(
-            gamma.data_ptr(), ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
-            acc.data_ptr(), bad.data_ptr(), _stream(dev)), "pychain_hip_smbr_frame_accuracy")
+        cls = _classes_args(classes, num_classes, targets_are_classes, D, dev, "smbr")
+        acc_args = (gamma.data_ptr(), ld.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
+                    acc.data_ptr(), bad.data_ptr(), _stream(dev))
+        if cls is None:
+            _lib.check(L.pychain_hip_smbr_frame_accuracy(*acc_args), "pychain_hip_smbr_frame_accuracy")
+        else:
+            wa = _workspace(L.pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(B, T), dev, "smbr_acc")
+            _lib.check(L.pychain_hip_smbr_frame_accuracy_classes(*acc_args, cls[0].data_ptr(), cls[1], cls[2], wa.data_ptr(), wa.numel()),
+                       "pychain_hip_smbr_frame_accuracy_classes")
         ws = _workspace(L.pychain_hip_smbr_workspace_bytes(B, T, H), dev, "smbr")
-        _lib.check(L.pychain_hip_smbr_forward_backward(
-            *[t.data_ptr() for t in gt], H, K, x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
-            pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale),
-            _ptr(grad_scale_dev), grad.data_ptr(), acc.data_ptr(), closing.data_ptr(), bad.data_ptr(),
-            ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_smbr_forward_backward")
+        args = (*[t.data_ptr() for t in gt], H, K, x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
+                pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale),
+                _ptr(grad_scale_dev), grad.data_ptr(), acc.data_ptr(), closing.data_ptr(), bad.data_ptr(),
+                ws.data_ptr(), ws.numel(), _stream(dev))
+        if cls is None:
+            _lib.check(L.pychain_hip_smbr_forward_backward(*args), "pychain_hip_smbr_forward_backward")
+        else:
+            _lib.check(L.pychain_hip_smbr_forward_backward_classes(*args, cls[0].data_ptr(), cls[1], cls[2]),
+                       "pychain_hip_smbr_forward_backward_classes")
     return acc, grad, bad, closing, frame_acc
 
 
-def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0):
+def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, *,
+             classes=None, num_classes=0, targets_are_classes=False):
     """The same on CPU tensors: the host twins (pychain_hip_cpu_smbr_*), fp32 rows and gradient."""
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_smbr is for CPU tensors; device tensors run on the HIP kernels")
@@ -772,13 +825,19 @@ def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1
     bad = torch.zeros(2, dtype=torch.int32)
     grad = torch.empty(B, T, D, dtype=torch.float32)
     L = _lib.lib()
-    _lib.check(L.pychain_hip_cpu_smbr_frame_accuracy(
-        gamma.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
-        acc.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_smbr_frame_accuracy")
-    _lib.check(L.pychain_hip_cpu_smbr_forward_backward(
-        *[t.data_ptr() for t in gt], H, K, xf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]),
-        frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale), None, grad.data_ptr(), acc.data_ptr(),
-        closing.data_ptr(), bad.data_ptr(), int(CPU_THREADS)), "pychain_hip_cpu_smbr_forward_backward")
+    cls = _classes_args(classes, num_classes, targets_are_classes, D, torch.device("cpu"), "cpu_smbr")
+    acc_args = (gamma.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(),
+                acc.data_ptr(), bad.data_ptr(), int(CPU_THREADS))
+    args = (*[t.data_ptr() for t in gt], H, K, xf.data_ptr(), lc.data_ptr(), B, T, D, pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]),
+            frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale), None, grad.data_ptr(), acc.data_ptr(),
+            closing.data_ptr(), bad.data_ptr(), int(CPU_THREADS))
+    if cls is None:
+        _lib.check(L.pychain_hip_cpu_smbr_frame_accuracy(*acc_args), "pychain_hip_cpu_smbr_frame_accuracy")
+        _lib.check(L.pychain_hip_cpu_smbr_forward_backward(*args), "pychain_hip_cpu_smbr_forward_backward")
+    else:
+        tail = (cls[0].data_ptr(), cls[1], cls[2])
+        _lib.check(L.pychain_hip_cpu_smbr_frame_accuracy_classes(*acc_args, *tail), "pychain_hip_cpu_smbr_frame_accuracy_classes")
+        _lib.check(L.pychain_hip_cpu_smbr_forward_backward_classes(*args, *tail), "pychain_hip_cpu_smbr_forward_backward_classes")
     return acc, grad, bad, closing, frame_acc
 
 

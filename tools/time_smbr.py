@@ -8,6 +8,9 @@ of the box falls on all of them:
   frame_acc    pychain_hip_smbr_frame_accuracy (smbr_frame_acc_kernel)
   rec_grad     pychain_hip_smbr_forward_backward: smbr_recursion_kernel, then smbr_grad_kernel
   smbr_bf16    the sMBR step on a bf16 network output
+  smbr_classes the sMBR step with the accuracy by class (DESIGN.md §3.27): a synthetic map of 40 classes, cls[n] = 40 n // D -
+               beside `smbr` it costs the dense accuracy pass over gamma and the class tables of the two stage-2 kernels
+  class_acc    pychain_hip_smbr_frame_accuracy_classes alone (smbr_class_frame_acc_kernel, smbr_class_seq_acc_kernel)
 
 The two kernels of rec_grad are told apart by a kernel trace of `--only rec_grad` (rocprofv3 --kernel-trace --stats, a run of
 its own).  Prints one JSON line of medians.
@@ -51,6 +54,9 @@ def main():
     xbf = x32.to(torch.bfloat16)
     ref = PosteriorTargets.from_alignment(viterbi_align(x32, L, num))
     mmi, smbr = ChainLoss(den, 1e-5), SMBRLoss(den, 1e-5)
+    classes = (40 * torch.arange(D, dtype=torch.int64) // D).to(torch.int32)
+    smbr_cls = SMBRLoss(den, 1e-5, classes=classes)
+    cls_dev, C = native.smbr_classes(classes, D, dev)
     plan = _plan.graph_plan(den, D, dev)
     gt = native.smbr_graph(den, D, dev)
     gamma = native.den_forward_backward(plan, x32, L, 1e-5)[1]
@@ -64,10 +70,10 @@ def main():
         xx = x32.detach().requires_grad_(True)
         mmi(xx, L, num).backward()
 
-    def leg_smbr(x):
+    def leg_smbr(x, loss=smbr):
         def run():
             xx = x.detach().requires_grad_(True)
-            smbr(xx, L, ref).backward()
+            loss(xx, L, ref).backward()
         return run
 
     def leg_den():
@@ -78,11 +84,20 @@ def main():
                                                        1, facc.data_ptr(), acc.data_ptr(), bad.data_ptr(),
                                                        torch.cuda.current_stream(dev).cuda_stream), "smbr_frame_accuracy")
 
+    ws = torch.empty(lib.pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(B, T), dtype=torch.uint8, device=dev)
+
+    def leg_class_acc():
+        _lib.check(lib.pychain_hip_smbr_frame_accuracy_classes(gamma.data_ptr(), ld.data_ptr(), B, T, D, ref.pdfs.data_ptr(), ref.probs.data_ptr(),
+                                                               1, facc.data_ptr(), acc.data_ptr(), bad.data_ptr(),
+                                                               torch.cuda.current_stream(dev).cuda_stream, cls_dev.data_ptr(), C, 0,
+                                                               ws.data_ptr(), ws.numel()), "smbr_frame_accuracy_classes")
+
     def leg_rec_grad():
         native.smbr(gt, den.num_states, x32, L, gamma, ref.pdfs, ref.probs, 1e-5)      # (the accuracy pass is in it: subtracted below)
 
     legs = {"mmi_ms": leg_mmi, "smbr_ms": leg_smbr(x32), "den_ms": leg_den, "frame_acc_ms": leg_frame_acc,
-            "acc_rec_grad_ms": leg_rec_grad, "smbr_bf16_ms": leg_smbr(xbf)}
+            "acc_rec_grad_ms": leg_rec_grad, "smbr_bf16_ms": leg_smbr(xbf), "smbr_classes_ms": leg_smbr(x32, smbr_cls),
+            "class_acc_ms": leg_class_acc}
     if only:
         legs = {only + "_ms": legs["acc_rec_grad_ms" if only == "rec_grad" else only + "_ms"]}
     acc_t = {k: [] for k in legs}
@@ -99,6 +114,7 @@ def main():
     if not only:
         out["rec_grad_ms"] = round(out["acc_rec_grad_ms"] - out["frame_acc_ms"], 4)
         out["smbr_over_mmi"] = round(out["smbr_ms"] / out["mmi_ms"], 3)
+        out["classes_over_smbr_ms"] = round(out["smbr_classes_ms"] - out["smbr_ms"], 4)
     print(json.dumps(out))
 
 
