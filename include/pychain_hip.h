@@ -810,9 +810,12 @@ int pychain_hip_cpu_boost_rows(
  *        bbar(L) = 0   bbar(t,i)   = sum_{k: src=i} p_k x(t,pdf_k) [ bbar'(t+1,dst) + a(t,pdf_k) beta'(t+1,dst) ]
  *        q0(t,n) = sum_{k: pdf=n} p alpha'(t,src) beta'(t+1,dst)
  *        q1(t,n) = sum_{k: pdf=n} p [ abar'(t,src) beta'(t+1,dst) + alpha'(t,src) bbar'(t+1,dst) ]
- *        grad(t,n) = s x(t,n) (q1(t,n) + a(t,n) q0(t,n)) / sum_m x(t,m) q0(t,m)          s = grad_scale [* *grad_scale_dev]
- *      with the CENTRED accuracies a(t,n) = A(t,n) - e(t): a per-frame constant changes no covariance, and it keeps every
- *      weighted quantity near zero instead of growing like t, which is what lets fp32 carry it.  All four vectors are normalised
+ *        v(t,n) = x(t,n) (q1(t,n) + a(t,n) q0(t,n))        eps(t) = sum_m v(t,m) / sum_m x(t,m) q0(t,m)
+ *        grad(t,n) = s (v(t,n) - eps(t) x(t,n) q0(t,n)) / sum_m x(t,m) q0(t,m)           s = grad_scale [* *grad_scale_dev]
+ *      with the CENTRED accuracies a(t,n) = A(t,n) - e(t): a per-frame constant changes no covariance, and it keeps the weighted
+ *      quantities from growing like t.  eps is zero in exact arithmetic.  In fp32 it is the rounding of e(t), which every frame
+ *      leaves in abar and bbar and the recursions carry on: every live row is centred by its own mean, or it would carry
+ *      gamma(t,n) times the residue accumulated over the whole sequence.  All four vectors are normalised
  *      per frame by the totals of alpha and beta; the quotient removes the factors.  One recursion launch of 2B persistent
  *      workgroups (sequence x direction; no workgroup waits for another), one time-parallel gradient launch.
  *
@@ -828,8 +831,9 @@ int pychain_hip_cpu_boost_rows(
  *                    frame_acc, acc_per_seq, bad_count as the first call left them; grad dev [B,T,D] out in the network output's
  *                    type, written once: rows t >= L_b are exact zeros, a pdf no arc carries gets an exact zero without its x
  *                    being read.  The 2-byte forms compute what the fp32 form computes on the up-cast input and round once.
- *                    closing dev float[B] out: sum_j abar'(L,j) final(j) / sum_j alpha'(L,j) final(j), zero up to rounding (a
- *                    diagnostic of the recursions).  bad_count[0] += the sequences with a frame total of the recursions or a
+ *                    closing dev float[B] out: sum_j abar'(L,j) final(j) / sum_j alpha'(L,j) final(j), a diagnostic of the
+ *                    recursions: zero in exact arithmetic, in fp32 the UNCENTRED residue of e(t)'s rounding summed over the
+ *                    sequence - it grows with the length (1e-6 at 1500 frames, 2e-3 from the host twin) and bounds nothing.  bad_count[0] += the sequences with a frame total of the recursions or a
  *                    frame's divisor sum_m x q0 of the gradient that is not positive and finite, or a NaN in a live row of x:
  *                    such a sequence has acc_per_seq NaN and is counted once; closing is NaN where the recursions or x were
  *                    the cause.  The other sequences of the call are untouched.

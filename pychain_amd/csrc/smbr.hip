@@ -16,7 +16,8 @@
 //   smbr_grad_kernel         time-parallel over (sequence, block of frames): the four state rows of a frame in LDS, a thread owns
 //                            pdfs tid, tid + 512, ... and walks that pdf's arcs through the caller's by-pdf order:
 //                              q0 = sum p alpha' beta',  q1 = sum p (alpha-bar' beta' + alpha' beta-bar')
-//                              grad = s x (q1 + a q0) / sum_m x(m) q0(m)
+//                              v = x (q1 + a q0),  grad = s (v - eps x q0) / sum_m x(m) q0(m),  eps = sum_m v(m) / sum_m x(m) q0(m)
+//                            (the row centred by its own mean: §3.26, "the residue")
 //                            The frame's normalisers cancel in the quotient, as in den_general_gamma_kernel.
 //
 // The same with the accuracy by CLASS (pychain_hip_smbr_*_classes): A(t,n) = Acls(t, cls[n]) for a map cls from
@@ -53,6 +54,7 @@ constexpr int kSmFrames = 8;                // frames of one gradient workgroup
 constexpr int kSmAccNT = 256;
 constexpr int kSmXR = 4;                    // elements of the next row a recursion thread holds in registers across the arc loop
 constexpr int kSmRed = 64;                  // floats of reduction scratch
+static_assert(48 + kSmGNT / 64 <= kSmRed, "smbr_grad_kernel sums the row mean over red[48 ..], behind block_sum3's 3 x 16");
 constexpr size_t kSmStaticLds = 256;        // what the recursion kernel holds beside its dynamic LDS (the closing vote)
 
 // up to three sums over the workgroup, every thread gets the totals; `red` (3 x 16 floats) is free again behind the NEXT barrier
@@ -472,11 +474,26 @@ __global__ __launch_bounds__(kSmGNT) void smbr_grad_kernel(const SmbrArgs a) {
         if (owned_entry(pd, pr, k, Kt, D, d, q)) gv[d] += q * gq[d];
     }
     __syncthreads();
+    // The row's mean: a second sum, over the FINISHED elements.  (Summing x (q1 - e q0) in the first block sum and the owners'
+    // A x q0 beside it gives the same mean in exact arithmetic, but at a pdf with gamma near one the two halves are each as large
+    // as the divisor and cancel: the mean must carry the rounding its elements carry, or it spreads 1e-7 of gamma over the row.)
+    // Its scratch is red[48 ..], which block_sum3 leaves alone - slower waves may still read red[0 .. 47].
+    float mean = 0.f;
+    for (int n = tid; n < D; n += kSmGNT) mean += gv[n];
+    mean = wave_sum(mean);
+    if ((tid & 63) == 0) red[48 + (tid >> 6)] = mean;
+    __syncthreads();
+    mean = 0.f;
+    for (int w = 0; w < kSmGNT / 64; w++) mean += red[48 + w];                   // (same order in every thread)
     const float sc = gscale / part, inv = 1.f / part;
     if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) smbr_condemn(a, b);    // (the host twin's check of the same divisor)
+    // The row is centred by its own mean, as smbr_class_grad_kernel's: sum_n x (q1 + a q0) is zero but for the rounding of e(t),
+    // and that residue enters alpha-bar and beta-bar at every frame and stays - uncentred, the row carries gamma(t,n) times the
+    // residue accumulated over the sequence (`closing` is that sum; DESIGN.md §3.26, "The residue").
+    const float eps = mean * inv;
     for (int n = tid; n < D; n += kSmGNT) {
       const bool carried = g.pidx[n] != g.pidx[n + 1];
-      row_store1<XH>(a.grad, row + n, carried ? gv[n] * sc : 0.f);
+      row_store1<XH>(a.grad, row + n, carried ? (gv[n] - eps * gq[n]) * sc : 0.f);
     }
     __syncthreads();                                                           // (the rows are free for the next frame)
   }

@@ -96,8 +96,9 @@ def expected_accuracy(x, lengths, den_graph, targets, leaky_coefficient=1e-5, *,
     PosteriorTargets.from_alignment, or posterior targets), as a 0-dim tensor differentiable in x (neither the clamp nor the
     reference is differentiated).  `den_graph`: a probability-domain ChainGraph, or a ChainGraphBatch made of one.  Of the
     result: `.per_seq` float64 [B] (NaN for a sequence that went bad), `.bad_count` int32 [2] (the sequences that went bad; the
-    target entries that name a pdf the network output does not have), `.closing` float32 [B] (a diagnostic of the recursions,
-    zero up to rounding).
+    target entries that name a pdf the network output does not have), `.closing` float32 [B] (a diagnostic of the recursions:
+    zero in exact arithmetic, in fp32 the uncentred residue of the frame accuracies' rounding summed over the sequence - it grows
+    with the length and bounds nothing).
 
     `classes`: an integer tensor [D], the class of every pdf (C = max + 1) - the accuracy of pdf n at a frame is then the sum of
     the frame's q_k whose pdf has n's class, so a path is credited on any pdf of the right class.  `targets_are_classes`: the ids
