@@ -360,6 +360,8 @@ int pychain_hip_num_half_native(int num_states, int num_transitions, int num_pdf
  * The device and the host twin give the same bits.  Graphs the tile kernels take (pychain_hip_num_half_native's shapes) keep
  * uint16 backpointers (2 B T H bytes of workspace); larger ones run on a global-memory kernel with int32 backpointers.
  * 2-byte network outputs: pychain_hip_align_half_native says where the kernels read them as they are (else up-cast first).
+ * nnet_output and the transition index tensors must be 16-byte aligned, else PYCHAIN_HIP_EINVAL (the device entry point; the
+ * time windows of pychain_hip_align_tw are read one element at a time: any element-aligned start).
  * pychain_hip_cpu_align: fp32 input, host threads as the other host twins. */
 size_t pychain_hip_align_workspace_bytes(int B, int T, int num_states, int num_transitions, int num_pdfs);
 int pychain_hip_align(
@@ -700,7 +702,9 @@ int pychain_hip_cpu_post_targets(
  * (exact); with `normalize` each is divided by the fp32 sum of the selected values taken in slot order (IEEE division).  A frame
  * with nothing selected stays all -1 / 0.  Frames t >= L_b are WRITTEN -1 / 0 and their rows never read.  out_pdfs int32
  * [B,T,K], out_probs float [B,T,K].  1 <= K <= min(num_pdfs, 64), else PYCHAIN_HIP_EINVAL.  Rows of up to 9216 elements are
- * read from memory once and held on chip; longer rows are re-read. */
+ * read from memory once and held on chip; longer rows are re-read.  `rows` may start at any element-aligned address: 16-byte
+ * loads where it starts on the 16-byte grid and num_pdfs is a multiple of the load's width, else one element at a time - the
+ * selection is exact either way, and the outputs do not depend on which (tests/test_gpu_layouts.py holds them to the bit). */
 int pychain_hip_topk_rows(const void* rows, int rows_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
                           int K, float floor, int normalize, int32_t* out_pdfs, float* out_probs, void* stream);
 int pychain_hip_cpu_topk_rows(const float* rows, const int64_t* seq_lengths, int B, int T, int num_pdfs,

@@ -144,8 +144,9 @@ def _dev_scalar(t, device):
 
 
 def _kernel_tensor(t):
-    """`t` as a device entry point takes it: contiguous and starting on a 16-byte boundary (every HIP entry point refuses any
-    other pointer - include/pychain_hip.h: its kernels read and write the rows 16 bytes at a time).  An aligned contiguous tensor
+    """`t` as a device entry point takes it: contiguous and starting on a 16-byte boundary (the entry points whose kernels read
+    and write the rows 16 bytes at a time refuse any other pointer - include/pychain_hip.h; pychain_hip_smbr_forward_backward,
+    pychain_hip_topk_rows and the time windows take any element-aligned start and do not come through here).  An aligned contiguous tensor
     comes back as it is, without a launch; a strided view, or a contiguous one whose offset into its buffer is no multiple of
     16 bytes (`y[1:]` at an odd T * D, one half of a wider layer's output), costs one copy of that tensor."""
     t = t.contiguous()
@@ -738,7 +739,10 @@ def smbr_classes(classes, D, device):
             raise ValueError("classes holds a negative entry (%d)" % lo)
         if hi >= 2 ** 31 - 1:
             raise ValueError("classes names class %d: beyond int32" % hi)
-        hit = (key, classes, classes.detach().to(device=device, dtype=torch.int32).contiguous(), hi + 1)
+        # (an aligned copy, 4 D bytes once per map: an int32 map already on `device` that is a contiguous view off the 16-byte grid
+        # would come back as that view, and the accuracy pass picks its 16-byte or its element form - other fp64 sum orders, other
+        # last bits - by the map's start.  One form serves a (D, gamma) whatever view the caller passed; the key stays the caller's.)
+        hit = (key, classes, _kernel_tensor(classes.detach().to(device=device, dtype=torch.int32)), hi + 1)
         _smbr_classes_cache[str(device)] = hit
     return hit[2], hit[3]
 
@@ -767,7 +771,10 @@ def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5,
     _require_device(x, "nnet_output")
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
-    x = x.detach().contiguous()            # (read one element at a time, csrc/smbr.hip: any element-aligned start will do)
+    # (x is read one element at a time - include/pychain_hip.h: pychain_hip_smbr_forward_backward, "any element-aligned start";
+    # csrc/smbr.hip: row_load1 - so a contiguous view off the 16-byte grid goes to the kernels as it is, 2-byte rows at a 2-byte
+    # offset included: no copy.  tests/test_gpu_layouts.py sends such views.  gamma and grad are this package's own, aligned.)
+    x = x.detach().contiguous()
     B, T, D = x.shape
     _check_lengths(lengths, B, T)
     L = _lib.lib()

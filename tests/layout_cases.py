@@ -20,10 +20,27 @@ bits.  The control itself is held to the float64 reference its own feature test 
   weight_rows                 weights_reference.np_weight_rows, bit for bit
   from_dense, posterior_targets   post_reference.np_topk, the same pdfs, values within TOPK_REL
   viterbi_align               num_reference.np_viterbi, bit for bit
+  viterbi_align under windows align_tw_reference.np_viterbi_tw, bit for bit (the batch's own windows, explicit int32 windows, explicit
+                              int64 windows): the windows lie around the alignment of `x`, the input aligned is `z`, so the constraint
+                              binds - asserted - and every sequence stays feasible
+  expected_accuracy, SMBRLoss smbr_reference.batch(recursions) on the up-cast input: per_seq, the gradient, its row sums and `closing`
+                              within smbr_reference.bound - 1e-5, or twice the fp32 numpy recursions' own distance where that is
+                              beyond F32_SLACK; the loss of SMBRLoss is -sum E_b / sum L_b, an upstream gradient scales the gradient
+  ... with `classes`          smbr_class_reference.batch(recursions) under the map `phones`, the same rule with the class-level rows;
+                              class-id targets (to_classes) give the bits of the pdf-level targets' control as well
 A gradient stored in bf16 / fp16 is rounded once or more per pass that touched it; the float64 comparison of GRADIENTS is made
 for float32 network outputs (the 2-byte stores have their derived bounds in tests/test_gpu_half.py, test_gpu_post_targets.py,
 test_gpu_weights.py, test_gpu_outreg.py), the loss of a 2-byte control is held to the bar like any other, and every 2-byte
 layout case is held to its control to the bit.
+
+THE sMBR INPUTS.  `x` has 5 % of its elements beyond the clamp; the fp32 reference's own distance from fp64 on exactly these
+inputs is computed here, on the CPU, and recorded with every measured distance (`f32_reference`, `bound`).  A bound beyond 1e-4
+would mean an input on which fp32 itself is poor: SEED_X is then to be changed, not the bound accepted (`smbr_bound` asserts it).
+SEED_X = 5 (the seed the matrix has had from the start) keeps every config's fp32 distance below F32_SLACK, so every bound is 1e-5.
+
+THE int64 WINDOWS.  `windows64` holds the windows of `windows` with every bound that cannot bind written beyond int32 - a lower
+bound of 0 as -2^40, an upper bound at the sequence's length as 2^40: saturated to int32 they admit exactly what `windows` admits
+(the reference reads them as int64), wrapped they would not.  The buffer around a view of them is poison beyond int32 too.
 """
 import contextlib
 import copy
@@ -31,17 +48,20 @@ import copy
 import numpy as np
 import torch
 
+import align_tw_reference as atr
 import boost_reference as br
 import layouts as ly
 import num_reference as nr
 import outreg_reference as orf
 import post_reference as pr
+import smbr_class_reference as scr
+import smbr_reference as sr
 import weights_reference as wr
 import xent_reference as xr
 import xent_targets_reference as xtr
-from pychain_amd import (ChainFunction, ChainGraphBatch, ChainLoss, ChainLossFunction, PosteriorTargets, alignment_windows,
-                         boost_rows, numerator_xent, occupancies, output_regularizer, posterior_numerator, posterior_targets,
-                         posterior_xent, viterbi_align, weight_rows, synthetic as syn)
+from pychain_amd import (ChainFunction, ChainGraphBatch, ChainLoss, ChainLossFunction, PosteriorTargets, SMBRLoss, alignment_windows,
+                         boost_rows, expected_accuracy, native, numerator_xent, occupancies, output_regularizer, posterior_numerator,
+                         posterior_targets, posterior_xent, viterbi_align, weight_rows, synthetic as syn)
 
 B, T = 4, 23
 LENGTHS = [23, 17, 9, 1]
@@ -51,6 +71,9 @@ CONFIGS = [(41, "float32"), (42, "float32"), (40, "float32"), (40, "bfloat16"), 
 DTYPES = pr.DTYPES
 L2, OOR, XENT_C, BOOST, TOPK = 5e-4, 1e-2, 0.2, 1.0, 3
 UPSTREAM = 0.37
+COEF = 1e-5                     # the leaky-HMM coefficient of the sMBR entries (and, written out, of every other entry)
+SEED_X = 5                      # (the module's docstring: THE sMBR INPUTS)
+BEYOND_INT32 = 2 ** 40
 _CACHE = {}
 
 
@@ -62,7 +85,7 @@ class Inputs(object):
         self.lengths = torch.tensor(LENGTHS, dtype=torch.int64)
         self.den = syn.make_den_graph(20, 60, D, seed=0)
         self.num = syn.make_num_graphs(LENGTHS, D, seed=100)
-        x = syn.make_input(B, T, D, seed=5)
+        x = syn.make_input(B, T, D, seed=SEED_X)
         far = torch.rand(x.shape, generator=torch.Generator().manual_seed(9)) < 0.05        # some elements beyond the clamp
         x = torch.where(far, torch.rand(x.shape, generator=torch.Generator().manual_seed(10)) * 80.0 - 40.0, x)
         v = dict(x=x.to(self.dtype), z=syn.make_input(B, T, D, seed=77).to(self.dtype),
@@ -81,6 +104,17 @@ class Inputs(object):
         v["bt_pdfs"], v["bt_probs"] = bt.pdfs, bt.probs
         v["windows"] = alignment_windows(ali, self.num.num_states, tolerance=2)
         v["lengths"] = self.lengths
+        # the same windows, every bound that cannot bind beyond int32 (the module's docstring: THE int64 WINDOWS)
+        w64 = v["windows"].to(torch.int64)
+        length = self.lengths.view(B, 1)
+        w64[..., 0] = torch.where(w64[..., 0] <= 0, torch.full_like(w64[..., 0], -BEYOND_INT32), w64[..., 0])
+        w64[..., 1] = torch.where(w64[..., 1] >= length, torch.full_like(w64[..., 1], BEYOND_INT32), w64[..., 1])
+        assert int((w64.abs() == BEYOND_INT32).sum()) >= 2 * B
+        v["windows64"] = w64
+        v["classes64"] = torch.from_numpy(scr.class_map("phones", D))
+        v["classes"] = v["classes64"].to(torch.int32)
+        v["cls_pdfs"] = PosteriorTargets(tg.pdfs, tg.probs).to_classes(v["classes"]).pdfs
+        assert v["cls_pdfs"].dtype == torch.int32 and v["cls_pdfs"].dim() == 3
         self.v = v
         self.xf, self.zf = v["x"].float(), v["z"].float()
 
@@ -104,8 +138,11 @@ ARGS = {"x": (3, False, True, False), "z": (3, False, True, False), "x_in": (3, 
         "post": (3, False, False, False), "u": (1, True, False, False), "f": (2, True, False, False),
         "pdfs": (3, False, False, False), "probs": (3, False, False, False), "bt_pdfs": (3, False, False, False),
         "bt_probs": (3, False, False, False), "hpdfs": (3, False, False, True), "hprobs": (3, False, False, True),
-        "windows": (3, False, False, False), "lengths": (1, False, False, False), "g0": (0, False, False, False)}
-_VALUE_OF = {"x_in": "x", "hpdfs": "pdfs", "hprobs": "probs"}
+        "windows": (3, False, False, False), "lengths": (1, False, False, False), "g0": (0, False, False, False),
+        "windows64": (3, False, False, False), "cls_pdfs": (3, False, False, False), "classes": (1, False, False, False),
+        "classes64": (1, False, False, False), "hclasses": (1, False, False, True)}
+_VALUE_OF = {"x_in": "x", "hpdfs": "pdfs", "hprobs": "probs", "hclasses": "classes64"}
+CLASS_MAPS = ("classes", "classes64", "hclasses")
 NON_FRESH = [n for n in ly.LAYOUTS if n != "fresh"]
 
 
@@ -119,14 +156,15 @@ def arg_layouts(arg):
 class Case(object):
     """One call: `t(name)` is the argument `name` on the call's device in the layout this case gives it."""
 
-    def __init__(self, inp, dev, mode, lay, eq):
+    def __init__(self, inp, dev, mode, lay, eq, values=None):
         self.inp, self.dev, self.mode, self.lay, self.eq = inp, dev, mode, dict(lay), tuple(eq)
+        self.values = dict(_VALUE_OF, **(values or {}))       # (an entry may give an argument another of the inputs' values)
         self.views, self.leaves = {}, {}
 
     def t(self, name):
         if name not in self.views:
             dim, _, leaf, host = ARGS[name]
-            val = self.inp.value(_VALUE_OF.get(name, name), self.eq)
+            val = self.inp.value(self.values.get(name, name), self.eq)
             val = val if host else val.to(self.dev)
             view = ly.LAYOUTS[self.lay.get(name, "fresh")](val, leaf=leaf)
             self.views[name] = view
@@ -239,10 +277,31 @@ def _viterbi(c):
     return dict(pdfs=ali.pdfs, states=ali.states, score=ali.score, ok=ali.ok)
 
 
+def _smbr(c, p="pdfs", q="probs", classes=None, targets_are_classes=False):
+    kw = {} if classes is None else dict(classes=c.t(classes), targets_are_classes=targets_are_classes)
+    return expected_accuracy(c.t("x"), c.lengths(False), c.inp.den, c.targets(p, q), COEF, **kw)
+
+
+def _smbr_loss(c):
+    return SMBRLoss(ChainGraphBatch(c.inp.den, B), COEF, avg=True)(c.t("x"), c.lengths(True), c.targets())
+
+
+def _viterbi_windows(c, windows="windows", own=False):
+    if own:                                          # (a batch of its own, as _windows makes it)
+        num = copy.copy(c.inp.num)
+        num._device_cache = dict(c.inp.num._device_cache)
+        num.__dict__.pop("_tw_device", None)
+        num.set_time_windows(c.t(windows))
+        ali = viterbi_align(c.t("x_in"), c.lengths(False), num, time_windows=True)
+    else:
+        ali = viterbi_align(c.t("x_in"), c.lengths(False), c.num(), time_windows=c.t(windows))
+    return dict(pdfs=ali.pdfs, states=ali.states, score=ali.score, ok=ali.ok)
+
+
 class Entry(object):
-    def __init__(self, name, fn, args, ref, modes=(None,), gpu_only=False, gradient=None, kw=None):
+    def __init__(self, name, fn, args, ref, modes=(None,), gpu_only=False, gradient=None, kw=None, values=None):
         self.name, self.fn, self.args, self.ref, self.modes, self.gpu_only = name, fn, tuple(args), ref, tuple(modes), gpu_only
-        self.gradient, self.kw = gradient, dict(kw or {})
+        self.gradient, self.kw, self.values = gradient, dict(kw or {}), dict(values or {})
 
 
 GRAPH_MODES = ("fused", "no_overlap", "unfused")
@@ -275,7 +334,23 @@ ENTRIES = [
     # an upstream gradient other than 1, a 0-dim view at an element offset: read on the device by native.rescale_
     Entry("upstream_graph", _loss_plain, ["g0"], "loss_plain", ("fused", "no_overlap"), gradient="g0"),
     Entry("upstream_post", _post_plain, ["g0"], "post_plain", ("fused",), gradient="g0"),
+    # lattice-free sMBR: x goes to its kernels as it is, 2-byte rows at 2 / 4 / 6-byte offsets included (native.smbr)
+    Entry("smbr_pdf", _smbr, ["x", "pdfs", "probs"], "smbr_pdf"),
+    Entry("smbr_pdf_host_targets", _smbr, ["x", "hpdfs", "hprobs"], "smbr_pdf", gpu_only=True, kw=dict(p="hpdfs", q="hprobs")),
+    Entry("smbr_loss_devlen", _smbr_loss, ["x", "lengths"], "smbr_loss"),
+    Entry("smbr_classes", _smbr, ["x", "pdfs", "probs", "classes"], "smbr_classes", kw=dict(classes="classes")),
+    Entry("smbr_classes_int64", _smbr, ["classes64"], "smbr_classes", kw=dict(classes="classes64")),
+    Entry("smbr_classes_host_map", _smbr, ["x", "hclasses"], "smbr_classes", gpu_only=True, kw=dict(classes="hclasses")),
+    Entry("smbr_class_targets", _smbr, ["x", "cls_pdfs", "probs", "classes"], "smbr_class_targets",
+          kw=dict(p="cls_pdfs", classes="classes", targets_are_classes=True)),
+    # constrained re-alignment: `z` aligned inside the windows around the alignment of `x`
+    Entry("viterbi_windows_own", _viterbi_windows, ["x_in", "windows"], "viterbi_windows", kw=dict(own=True), values=dict(x_in="z")),
+    Entry("viterbi_windows_explicit", _viterbi_windows, ["x_in", "windows"], "viterbi_windows", values=dict(x_in="z")),
+    Entry("viterbi_windows_explicit_int64", _viterbi_windows, ["windows64"], "viterbi_windows64", kw=dict(windows="windows64"),
+          values=dict(x_in="z")),
+    Entry("upstream_smbr", _smbr, ["g0"], "smbr_pdf", gradient="g0"),
 ]
+SMBR_REFS = ("smbr_pdf", "smbr_loss", "smbr_classes", "smbr_class_targets")
 BY_NAME = {e.name: e for e in ENTRIES}
 
 
@@ -313,7 +388,7 @@ def variants(entry, layout):
 
 # ---- running a case -----------------------------------------------------------------------------------------------------------------
 REPORTS = ("totals", "totals_all", "bad_count", "xent_objf", "xent_objf_per_seq", "l2_term", "out_of_range_term", "weighted_frames",
-           "objf_per_seq")
+           "objf_per_seq", "per_seq", "closing")          # (the last two: of the sMBR entries only - test_layouts.py asserts it)
 
 
 @contextlib.contextmanager
@@ -339,11 +414,16 @@ class Result(object):
 
 def run(entry, dev, D, dname, mode=None, lay=None, eq=()):
     inp = inputs(D, dname)
-    c = Case(inp, torch.device(dev), mode, lay or {}, eq)
+    c = Case(inp, torch.device(dev), mode, lay or {}, eq, entry.values)
     res = Result()
     res.values, res.grads = {}, {}
     with _route(mode):
         out = entry.fn(c, **entry.kw)
+        for a in CLASS_MAPS:
+            if a in c.views:
+                # the map was uploaded for THIS view - the cache of native.smbr_classes holds its source tensor -, not taken from
+                # what the control, or the case before, left there
+                assert native._smbr_classes_cache[str(c.t("x").device)][1] is c.views[a], (entry.name, a, "a cached class map was used")
         if isinstance(out, dict):
             res.values = {k: _host(v) for k, v in out.items()}
             return res
@@ -458,6 +538,44 @@ def _want_loss(inp, ref, eq):
     raise KeyError(ref)
 
 
+def smbr_bound(d32):
+    """smbr_reference.bound's rule on the fp32 reference's own distance `d32`; beyond 1e-4 the inputs are at fault (SEED_X)"""
+    bound = 2.0 * d32 if d32 > sr.F32_SLACK else sr.BAR
+    assert bound <= 1e-4, ("the fp32 reference itself is %g from fp64 on these inputs: choose another SEED_X" % d32)
+    return bound
+
+
+def _smbr_ref(inp, ref):
+    """((E [B], dE/dx [B,T,D], closing [B]) by the float64 recursions on the up-cast input, the bound, the fp32 recursions' own
+    distance, what gradient distances are relative to) of the sMBR entries: pdf-level, by class, by class with class-id targets"""
+    def make():
+        probs = inp.v["probs"].numpy()
+        if ref in ("smbr_pdf", "smbr_loss"):
+            args = (inp.den, inp.xf, LENGTHS, inp.v["pdfs"].numpy(), probs, COEF)
+            want, w32 = sr.batch(sr.recursions, *args), sr.batch(sr.recursions, *args, dtype=np.float32)
+        else:
+            tac = ref == "smbr_class_targets"
+            args = (inp.den, inp.xf, LENGTHS, inp.v["cls_pdfs" if tac else "pdfs"].numpy(), probs, inp.v["classes64"].numpy(), COEF)
+            want = scr.batch(sr.recursions, *args, targets_are_classes=tac)
+            w32 = scr.batch(sr.recursions, *args, targets_are_classes=tac, dtype=np.float32)
+        scale = float(np.abs(want[1]).max())
+        assert scale > 0 and int((want[0] > 0).sum()) >= 3, "the reference has nothing to compare"
+        d32 = max(scr.grad_dist(w32[1], want[1], scale), sr.value_dist(w32[0], want[0]))
+        return want, smbr_bound(d32), d32, scale
+    return _cached(("smbr_ref", ref if ref != "smbr_loss" else "smbr_pdf", inp.D, inp.dname), make)
+
+
+def _tw_ref(inp, ref):
+    """(np_viterbi_tw of `z` inside the windows around the alignment of `x`, the free alignment of `z`)"""
+    def make():
+        w = inp.v["windows64" if ref == "viterbi_windows64" else "windows"]
+        want, free = atr.np_viterbi_tw(inp.num, inp.zf, LENGTHS, w), nr.np_viterbi(inp.num, inp.zf, LENGTHS)
+        assert bool(np.isfinite(want[0]).all()) and all(atr.admits(inp.v["windows"], want, LENGTHS)), "a sequence is infeasible"
+        assert sum(atr.frames_differing(want, free, LENGTHS)) >= 1, "the windows do not bind: the free path lies inside them"
+        return want, free
+    return _cached(("tw_ref", ref, inp.D, inp.dname), make)
+
+
 def _dist(got, want):
     return float(np.abs(np.asarray(got, dtype=np.float64) - want).max() / np.abs(want).max())
 
@@ -538,6 +656,28 @@ def check_reference(entry, ctl, dev, D, dname, mode=None, eq=(), record=None):
     elif ref == "viterbi_align":
         want = nr.np_viterbi(inp.num, inp.xf, LENGTHS)
         nr.check_alignment(ctl.values["score"], ctl.values["states"], ctl.values["pdfs"], ctl.values["ok"], 0, want, LENGTHS)
+    elif ref in ("viterbi_windows", "viterbi_windows64"):
+        want, _ = _tw_ref(inp, ref)
+        if ref == "viterbi_windows64":                                   # (saturated, the int64 windows admit what the int32 ones do)
+            same = _tw_ref(inp, "viterbi_windows")[0]
+            assert all(np.array_equal(a, b) for a, b in zip(want[:3], same[:3]))
+        nr.check_alignment(ctl.values["score"], ctl.values["states"], ctl.values["pdfs"], ctl.values["ok"], 0, want, LENGTHS)
+    elif ref in SMBR_REFS:
+        (E, G, _), bound, d32, scale = _smbr_ref(inp, ref)
+        s = -1.0 / float(sum(LENGTHS)) if ref == "smbr_loss" else 1.0   # SMBRLoss, avg: -sum_b E_b / sum_b L_b
+        d["value"] = sr.value_dist(v["per_seq"], E)
+        d["loss"] = abs(float(v["loss"]) - s * E.sum()) / abs(s * E.sum())
+        d["closing"] = float(np.abs(v["closing"]).max())
+        if f32:
+            d["grad"] = scr.grad_dist(gx, up * s * G, abs(up * s) * scale)
+            d["rows"] = float(np.abs(gx.astype(np.float64).sum(-1)).max() / (abs(up * s) * scale))
+        assert ctl.values["per_seq"].dtype == torch.float64 and ctl.values["bad_count"].tolist() == [0, 0]
+        assert max(d.values()) <= bound, (entry.name, d, bound)
+        d.update(f32_reference=d32, bound=bound)                         # (recorded beside every measured distance)
+        if ref == "smbr_class_targets":                                  # class ids in place of pdfs: the bits of the pdf targets' call
+            other = control(BY_NAME["smbr_classes"], dev, D, dname, mode)
+            assert all(same_bits(ctl.values[k], other.values[k]) for k in ("per_seq", "closing", "bad_count"))
+            assert same_bits(ctl.grads["x"]["inside"], other.grads["x"]["inside"])
     else:
         raise KeyError(ref)
     if record is not None and d:

@@ -6,8 +6,11 @@ import torch
 
 import layout_cases as lc
 import layouts as ly
+from helpers import record_parity
 
 DEV = "cpu"
+NEW = ("smbr_pdf", "smbr_pdf_host_targets", "smbr_loss_devlen", "smbr_classes", "smbr_classes_int64", "smbr_classes_host_map",
+       "smbr_class_targets", "viterbi_windows_own", "viterbi_windows_explicit", "viterbi_windows_explicit_int64", "upstream_smbr")
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16, torch.int32, torch.int64])
@@ -64,6 +67,27 @@ def test_the_matrix_covers_every_entry_and_layout():
             assert lc.variants(e, layout), (e.name, layout)
     lay, eq = lc.variants(lc.BY_NAME["loss_all"], "everything")[0]
     assert len(set(lay.values())) == len(lay) == 4 and "fresh" not in lay.values()
+    # sMBR, the class maps and windowed alignment: every listed argument in every layout of its dimensionality, one at a time,
+    # and all of an entry's arguments at once, each in a layout of its own
+    one_dim = ["offset_1", "offset_2", "offset_3", "offset_4", "batch_slice", "batch_step", "head_lo", "head_hi"]
+    for a in lc.CLASS_MAPS + ("lengths",):
+        assert lc.arg_layouts(a) == one_dim, a                         # (a map is never `expanded`)
+    for a in ("x", "x_in", "pdfs", "probs", "cls_pdfs", "hpdfs", "hprobs", "windows", "windows64"):
+        assert lc.arg_layouts(a) == lc.NON_FRESH[:-1] and lc.NON_FRESH[-1] == "expanded", a
+    assert set(NEW) <= {e.name for e in lc.ENTRIES}
+    for name in NEW:
+        e = lc.BY_NAME[name]
+        for a in e.args:
+            for layout in lc.arg_layouts(a):
+                assert [lay for lay, _ in lc.variants(e, layout) if lay == {a: layout}], (name, a, layout)
+        if len(e.args) > 1:
+            (lay, eq), = lc.variants(e, "everything")
+            assert sorted(lay) == sorted(e.args) and len(set(lay.values())) == len(lay) and "fresh" not in lay.values() and not eq
+            assert (name, e.modes[0], "everything") in lc.matrix(DEV) or e.gpu_only
+
+
+def _record(name, **d):
+    record_parity(name.replace("layouts_", "layouts_cpu_", 1), **d)
 
 
 def _controls(dev):
@@ -75,7 +99,9 @@ def _controls(dev):
 def test_control_is_stable_and_meets_its_float64_reference(name, mode, D, dname):
     e = lc.BY_NAME[name]
     lc.fresh_is_stable(e, DEV, D, dname, mode)
-    d = lc.check_reference(e, lc.control(e, DEV, D, dname, mode), DEV, D, dname, mode)
+    ctl = lc.control(e, DEV, D, dname, mode)
+    assert ("per_seq" in ctl.values) == ("closing" in ctl.values) == (e.ref in lc.SMBR_REFS)       # (no other result carries the names)
+    d = lc.check_reference(e, ctl, DEV, D, dname, mode, record=_record if name in NEW else None)
     print(name, mode, D, dname, d)
 
 
