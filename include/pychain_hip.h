@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 28
+#define PYCHAIN_HIP_ABI_VERSION 29
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -843,7 +843,8 @@ int pychain_hip_cpu_boost_rows(
  *                    the cause.  The other sequences of the call are untouched.
  * No float atomics: a call gives the same bits every time.  The recursion workgroup keeps four state vectors and four rows in
  * LDS: (4 H + 4 num_pdfs + 128) * 4 bytes must fit the 160 KiB of a CU (3000 states and 3456 pdfs: 103 KiB), else
- * PYCHAIN_HIP_EUNSUPPORTED with the sizes in the message - there is no slower form.  Workspace: pychain_hip_smbr_workspace_bytes
+ * PYCHAIN_HIP_EUNSUPPORTED with the sizes in the message - these two entry points have no slower form; the general kernels are
+ * asked for by name (pychain_hip_smbr_forward_backward_general, below).  Workspace: pychain_hip_smbr_workspace_bytes
  * (the four trajectories, 16 (T + 1) H B bytes, and the frame totals).  leaky_hmm_coefficient in (0,1); K >= 1.  The entry points
  * are a translation unit of their own (csrc/smbr.hip): no existing entry point launches anything it did not launch before. */
 size_t pychain_hip_smbr_workspace_bytes(int B, int T, int num_states);
@@ -939,6 +940,51 @@ int pychain_hip_cpu_smbr_forward_backward_classes(
     float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
     float* grad, double* acc_per_seq, float* closing, int32_t* bad_count, int num_threads,
     const int32_t* pdf_classes, int num_classes, int targets_are_classes);
+
+/* ------------------------------------------------------------------------
+ * Lattice-free sMBR on graphs and trees beyond the LDS of a CU (ABI 29; csrc/smbr_general.hip).  The two
+ * forward_backward entry points above keep four state vectors and four rows of a frame in LDS and refuse what does not fit:
+ * 3000 states with more than about 7 200 pdfs (the 8408 pdfs of a 2000-frame tree among them), identity classes sooner, more
+ * than about 10 000 states at any num_pdfs.  The general kernels take any num_states, num_pdfs, num_classes and K the int32
+ * layout holds, with the same equations, row centring, checks and workspace layout; they are slower - what does not fit LDS is
+ * gathered from global memory - and are asked for by name, through an entry point of their own:
+ *   PYCHAIN_HIP_SMBR_LDS     the kernels of the entry points above, launch for launch
+ *   PYCHAIN_HIP_SMBR_ROWS    the state vectors stay in LDS (pychain_hip_smbr_general_lds_bytes(num_states) within 160 KiB:
+ *                            (4 H + 64) * 4 + 256 bytes); the frame's row x, its companion x A and the class table lie in
+ *                            scratch rows of the workspace, one set per workgroup, made a frame ahead
+ *   PYCHAIN_HIP_SMBR_GLOBAL  the state vectors too are read back from the trajectories in the workspace: always runs
+ *   PYCHAIN_HIP_SMBR_AUTO    LDS where pychain_hip_smbr_lds_bytes is within 160 KiB, else ROWS where the state vectors fit, else
+ *                            GLOBAL
+ * SAME BITS: thread-to-state and thread-to-pdf ownership, the arc order and the order of every sum are those of the LDS kernels,
+ * so on a shape two forms take they give the same gradient, acc_per_seq, closing and bad_count, bit for bit.  No float atomics;
+ * a call gives the same bits every time.
+ * pychain_hip_smbr_form: host only; the form a call with `requested` would run, or PYCHAIN_HIP_EUNSUPPORTED (LDS or ROWS asked
+ *   for on a shape it cannot hold: the sizes are in the message) or PYCHAIN_HIP_EINVAL (sizes, an unknown form).  num_classes 0:
+ *   the pdf-level call.
+ * pychain_hip_smbr_general_workspace_bytes: the trajectories of pychain_hip_smbr_workspace_bytes, then per recursion workgroup
+ *   (2 B of them) 4 num_pdfs + num_classes floats and per gradient workgroup (at most 512, persistent over the (sequence, 8-frame
+ *   block) items) 2 num_pdfs + num_classes floats, each rounded up to 256 bytes; 0 for bad sizes.  A call whose form resolves to
+ *   LDS needs pychain_hip_smbr_workspace_bytes only.
+ * pychain_hip_smbr_forward_backward_general: the arguments of pychain_hip_smbr_forward_backward_classes (pdf_classes NULL: the
+ *   pdf-level call), then `form`; the same argument checks and messages. */
+#define PYCHAIN_HIP_SMBR_AUTO   0
+#define PYCHAIN_HIP_SMBR_LDS    1
+#define PYCHAIN_HIP_SMBR_ROWS   2
+#define PYCHAIN_HIP_SMBR_GLOBAL 3
+int pychain_hip_smbr_form(int num_states, int num_pdfs, int num_classes, int requested);
+size_t pychain_hip_smbr_general_lds_bytes(int num_states);
+size_t pychain_hip_smbr_general_workspace_bytes(int B, int T, int num_states, int num_pdfs, int num_classes);
+int pychain_hip_smbr_forward_backward_general(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad /* nnet_output_dtype */, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes, int form);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -10,12 +10,13 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 28
+ABI_VERSION = 29
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
 CPU_NO_CLAMP = 0x100     # (host twin of the numerator only: include/pychain_hip.h)
 F32, BF16, F16 = 0, 1, 2        # include/pychain_hip.h: PYCHAIN_HIP_F32 / _BF16 / _F16
+SMBR_AUTO, SMBR_LDS, SMBR_ROWS, SMBR_GLOBAL = 0, 1, 2, 3     # include/pychain_hip.h: PYCHAIN_HIP_SMBR_*
 
 _lib = None
 
@@ -126,6 +127,10 @@ _SIGNATURES = {
     "pychain_hip_smbr_forward_backward_classes": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp] + _SMBR_CLASSES),
     "pychain_hip_cpu_smbr_frame_accuracy_classes": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i] + _SMBR_CLASSES),
     "pychain_hip_cpu_smbr_forward_backward_classes": (_i, _SMBR_GRAPH + _CPU_ROWS + [_i] * 3 + _SMBR_TAIL + [_i] + _SMBR_CLASSES),
+    "pychain_hip_smbr_form": (_i, [_i, _i, _i, _i]),
+    "pychain_hip_smbr_general_lds_bytes": (_sz, [_i]),
+    "pychain_hip_smbr_general_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pychain_hip_smbr_forward_backward_general": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp] + _SMBR_CLASSES + [_i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),

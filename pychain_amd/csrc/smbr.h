@@ -70,5 +70,23 @@ hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st);     // the recursion 
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hipStream_t st);   // the dense pass, then the per-sequence sums
 hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st);
 
+// The general kernels (smbr_general.hip): any H, D, C.  What the LDS kernels keep in LDS beside the state vectors
+// - the frame's row x, its companion x A, the class table; the two D-rows of the gradient - lies in scratch rows of the workspace,
+// one set per workgroup, behind the trajectories.
+struct SmbrGeneral {
+  float* rec;                // [2 B][rec_stride]: x [2][D], x A [2][D], Acls [C] of a recursion workgroup
+  float* grad;               // [grad_wgs][grad_stride]: x q0 [D], x (q1 + a q0) [D], Acls [C] of a gradient workgroup
+  size_t rec_stride, grad_stride;       // floats, multiples of 64
+  int grad_wgs;              // workgroups of the gradient launch, persistent over the (sequence, frame-block) items
+  int state_lds;             // 1: the state vectors double-buffered in LDS ("rows"); 0: read back from the trajectories ("global")
+};
+constexpr int kSmbrGradMaxWgs = 512;                // two gradient workgroups a CU: bounds the scratch
+size_t smbr_general_lds(int H);                     // bytes of LDS of the rows form, static LDS included
+size_t smbr_general_rec_stride(int D, int C);       // floats
+size_t smbr_general_grad_stride(int D, int C);
+int smbr_general_grad_wgs(int B, int T);
+// the recursion launch, then the gradient launch; c.cls null: the pdf-level form
+hipError_t launch_smbr_general(const SmbrArgs& a, const SmbrClasses& c, const SmbrGeneral& s, hipStream_t st);
+
 }  // namespace pychain_hip
 #endif

@@ -32,6 +32,11 @@
 //                                 row is centred by its own mean (the residue of e(t)'s rounding, which a dense A would spread)
 // Nothing is atomic but integer counters and flags; every sum has a fixed order, so a call gives the same bits every time.  All of
 // this unit's device code, the helpers of the project's headers included, is compiled with contraction off: the 2-byte forms then compute what the fp32 form computes on the up-cast input.
+//
+// These kernels keep a frame in LDS and the two entry points that launch only them refuse what does not fit.  The general kernels
+// (smbr_general.hip) take any graph and tree with the same bits; they share this unit's argument checks, workspace
+// layout and entry-point code (pychain_hip_smbr_forward_backward_general, pychain_hip_smbr_form, below) and the device helpers of
+// smbr_device.h.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -44,65 +49,14 @@
 #include "common.h"
 #include "row_access.h"
 #include "smbr.h"
+#include "smbr_device.h"
 
 namespace pychain_hip {
 namespace {
 
-constexpr int kSmNT = 1024;                 // recursion workgroup: 16 waves
-constexpr int kSmGNT = 512;                 // gradient workgroup
-constexpr int kSmFrames = 8;                // frames of one gradient workgroup
+// (the workgroup shapes, block_sum3, owned_entry, scatter_entries, entry_class, class_table, hold_row, put_row and smbr_condemn:
+// smbr_device.h, shared with the general kernels of smbr_general.hip)
 constexpr int kSmAccNT = 256;
-constexpr int kSmXR = 4;                    // elements of the next row a recursion thread holds in registers across the arc loop
-constexpr int kSmRed = 64;                  // floats of reduction scratch
-static_assert(48 + kSmGNT / 64 <= kSmRed, "smbr_grad_kernel sums the row mean over red[48 ..], behind block_sum3's 3 x 16");
-constexpr size_t kSmStaticLds = 256;        // what the recursion kernel holds beside its dynamic LDS (the closing vote)
-
-// up to three sums over the workgroup, every thread gets the totals; `red` (3 x 16 floats) is free again behind the NEXT barrier
-template <int NT>
-__device__ __forceinline__ void block_sum3(float& s0, float& s1, float& s2, float* red, int tid) {
-  s0 = wave_sum(s0); s1 = wave_sum(s1); s2 = wave_sum(s2);
-  if ((tid & 63) == 0) { red[tid >> 6] = s0; red[16 + (tid >> 6)] = s1; red[32 + (tid >> 6)] = s2; }
-  __syncthreads();
-  s0 = s1 = s2 = 0.f;
-  for (int w = 0; w < NT / 64; w++) { s0 += red[w]; s1 += red[16 + w]; s2 += red[32 + w]; }     // (same order in every thread)
-}
-
-// Entry k of a frame (pd, pr: its Kt entries): true where this thread owns it, with (pdf, summed q).  An entry is handled where
-// its pdf occurs first in the frame, q summed in ascending k, so a repeated pdf has one owner and nothing is atomic.
-__device__ __forceinline__ bool owned_entry(const int32_t* pd, const float* pr, int k, int Kt, int D, int& d, float& q) {
-  d = pd[k];
-  if (d < 0 || d >= D) return false;
-  for (int j = 0; j < k; j++)
-    if (pd[j] == d) return false;
-  q = pr[k];
-  for (int j = k + 1; j < Kt; j++)
-    if (pd[j] == d) q += pr[j];
-  return true;
-}
-// x A of a frame over its zeroed companion row
-__device__ __forceinline__ void scatter_entries(const int32_t* pd, const float* pr, int Kt, int D, int tid, int nt, const float* xrow, float* xacc) {
-  int d;
-  float q;
-  for (int k = tid; k < Kt; k += nt)
-    if (owned_entry(pd, pr, k, Kt, D, d, q)) xacc[d] = xrow[d] * q;
-}
-
-// ---- accuracy by class (§3.27) ----------------------------------------------------------------------------------------------------
-// the class of a target id, -1 where it adds nothing: padding, a pdf >= D, a class >= C
-__device__ __forceinline__ int entry_class(const SmbrClasses& c, int id, int D) {
-  if (id < 0) return -1;
-  if (c.targets_are_classes) return id < c.C ? id : -1;
-  return id < D ? c.cls[id] : -1;
-}
-// Acls(t, .) of a frame into `acl` [C]: thread tid, tid + nt, ... sums the q of its class in ascending k - one owner, no atomics
-__device__ __forceinline__ void class_table(const SmbrClasses& c, const int32_t* pd, const float* pr, int Kt, int D, int tid, int nt, float* acl) {
-  for (int cc = tid; cc < c.C; cc += nt) {
-    float q = 0.f;
-    for (int k = 0; k < Kt; k++)
-      if (entry_class(c, pd[k], D) == cc) q += pr[k];
-    acl[cc] = q;
-  }
-}
 
 // ---- stage 1: frame accuracies ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSmAccNT) void smbr_frame_acc_kernel(const SmbrAccArgs a) {
@@ -224,31 +178,7 @@ __global__ __launch_bounds__(kSmAccNT) void smbr_class_seq_acc_kernel(const Smbr
 }
 
 // ---- stage 2: the recursions ----------------------------------------------------------------------------------------------------
-// row t of the sequence into LDS as exp(clamp(.)); elements tid + i * NT, i < kSmXR, come from `held` (loaded before the arc loop)
-template <int XH>
-__device__ __forceinline__ void hold_row(const void* x, size_t row, int D, int tid, float (&held)[kSmXR]) {
-#pragma unroll
-  for (int i = 0; i < kSmXR; i++) {
-    const int n = tid + i * kSmNT;
-    held[i] = n < D ? row_load1<XH>(x, row + n) : 0.f;
-  }
-}
-template <int XH>
-__device__ __forceinline__ bool put_row(const void* x, size_t row, int D, int tid, const float (&held)[kSmXR], float* lds) {
-  bool nan = false;
-#pragma unroll
-  for (int i = 0; i < kSmXR; i++) {
-    const int n = tid + i * kSmNT;
-    if (n < D) { nan = nan || held[i] != held[i]; lds[n] = clamp_exp(held[i], kXExpClamp); }
-  }
-  for (int n = tid + kSmXR * kSmNT; n < D; n += kSmNT) {       // (rows of more than 4096 pdfs)
-    const float r = row_load1<XH>(x, row + n);
-    nan = nan || r != r;
-    lds[n] = clamp_exp(r, kXExpClamp);
-  }
-  return nan;
-}
-
+// (hold_row / put_row - row t of the sequence into LDS as exp(clamp(.)) -: smbr_device.h)
 // x A of the elements put_row stored, by class: xacc[n] = xrow[n] * acl[cls[n]] - the thread reads back what it wrote itself;
 // `hc`: cls of the elements held in registers, those beyond are loaded again
 __device__ __forceinline__ void class_row(const int32_t* cls, const int (&hc)[kSmXR], int D, int tid, const float* acl, const float* xrow, float* xacc) {
@@ -407,14 +337,7 @@ __global__ __launch_bounds__(kSmNT) void smbr_class_recursion_kernel(const SmbrA
 }
 
 // ---- stage 2: the gradient ------------------------------------------------------------------------------------------------------
-// The sequence went bad: its E_b becomes NaN and it is counted ONCE, by whichever workgroup of the gradient launch finds it first
-// (seq_bad[B + b]: claimed by an integer compare-and-swap; the same values whoever wins).
-__device__ __forceinline__ void smbr_condemn(const SmbrArgs& a, int b) {
-  if (atomicCAS(a.seq_bad + a.B + b, 0, 1) == 0) {
-    a.acc_per_seq[b] = __builtin_nan("");
-    atomicAdd(a.bad_count, 1);                                                 // (an integer count)
-  }
-}
+// (smbr_condemn - a sequence that went bad is counted once, its E_b NaN -: smbr_device.h)
 template <int XH>
 __global__ __launch_bounds__(kSmGNT) void smbr_grad_kernel(const SmbrArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -675,7 +598,7 @@ using namespace pychain_hip;
 
 // ---- the entry points (include/pychain_hip.h) -----------------------------------------------------------------------------------
 namespace {
-struct SmbrCarve { size_t al, ab, be, bb, tot_a, tot_b, seq_bad, total; };
+struct SmbrCarve { size_t al, ab, be, bb, tot_a, tot_b, seq_bad, end, total; };
 SmbrCarve smbr_carve(int B, int T, int H) {
   SmbrCarve c;
   const size_t traj = align256((size_t)B * (T + 1) * H * sizeof(float)), tot = align256((size_t)B * (T + 1) * sizeof(float));
@@ -683,10 +606,57 @@ SmbrCarve smbr_carve(int B, int T, int H) {
   c.al = o; o += traj; c.ab = o; o += traj; c.be = o; o += traj; c.bb = o; o += traj;
   c.tot_a = o; o += tot; c.tot_b = o; o += tot;
   c.seq_bad = o; o += align256(2 * (size_t)B * sizeof(int32_t));
+  c.end = o;
   c.total = o + 256;                               // (the base is aligned inside the caller's buffer)
   return c;
 }
+// the general kernels' scratch rows (smbr.h: SmbrGeneral) behind the layout above, which they keep
+struct SmbrGeneralCarve { size_t rec, grad, total; SmbrGeneral s; };
+SmbrGeneralCarve smbr_general_carve(const SmbrCarve& c, int B, int T, int D, int C) {
+  SmbrGeneralCarve v;
+  memset(&v, 0, sizeof(v));
+  v.s.rec_stride = smbr_general_rec_stride(D, C);
+  v.s.grad_stride = smbr_general_grad_stride(D, C);
+  v.s.grad_wgs = smbr_general_grad_wgs(B, T);
+  size_t o = c.end;
+  v.rec = o; o += align256(2 * (size_t)B * v.s.rec_stride * sizeof(float));
+  v.grad = o; o += align256((size_t)v.s.grad_wgs * v.s.grad_stride * sizeof(float));
+  v.total = o + 256;
+  return v;
+}
+
+// The form a call of the general entry point runs (include/pychain_hip.h: PYCHAIN_HIP_SMBR_*), or a negative code with the
+// message set.  C = 0: the pdf-level call.
+int smbr_resolve_form(const char* who, int H, int D, int C, int requested) {
+  if (H <= 0 || D <= 0 || C < 0) return fail(PYCHAIN_HIP_EINVAL, "%s: bad sizes H=%d D=%d num_classes=%d", who, H, D, C);
+  if (requested < PYCHAIN_HIP_SMBR_AUTO || requested > PYCHAIN_HIP_SMBR_GLOBAL)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: unknown form %d (PYCHAIN_HIP_SMBR_AUTO .. _GLOBAL)", who, requested);
+  const size_t lds = smbr_lds_bytes(H, D, C), rows = smbr_general_lds(H);
+  if (requested == PYCHAIN_HIP_SMBR_LDS && lds > kSmbrLdsBudget)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: the LDS form needs %zu bytes of LDS for %d states, %d pdfs and %d classes (four state vectors, four rows and the class table), a CU has %zu",
+                who, lds, H, D, C, kSmbrLdsBudget);
+  if (requested == PYCHAIN_HIP_SMBR_ROWS && rows > kSmbrLdsBudget)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: the rows form needs %zu bytes of LDS for %d states (four state vectors), a CU has %zu",
+                who, rows, H, kSmbrLdsBudget);
+  if (requested != PYCHAIN_HIP_SMBR_AUTO) return requested;
+  return lds <= kSmbrLdsBudget ? PYCHAIN_HIP_SMBR_LDS : rows <= kSmbrLdsBudget ? PYCHAIN_HIP_SMBR_ROWS : PYCHAIN_HIP_SMBR_GLOBAL;
+}
+constexpr int kSmbrFormOfOld = -1;                 // the two entry points from before the general kernels: LDS or refused, their messages
 }  // namespace
+
+extern "C" int pychain_hip_smbr_form(int H, int D, int num_classes, int requested) {
+  return smbr_resolve_form("smbr_form", H, D, num_classes, requested);
+}
+
+extern "C" size_t pychain_hip_smbr_general_lds_bytes(int H) {
+  if (H <= 0) return 0;
+  return smbr_general_lds(H);
+}
+
+extern "C" size_t pychain_hip_smbr_general_workspace_bytes(int B, int T, int H, int D, int num_classes) {
+  if (B <= 0 || T <= 0 || H <= 0 || D <= 0 || num_classes < 0) return 0;
+  return smbr_general_carve(smbr_carve(B, T, H), B, T, D, num_classes).total;
+}
 
 extern "C" size_t pychain_hip_smbr_workspace_bytes(int B, int T, int H) {
   if (B <= 0 || T <= 0 || H <= 0) return 0;
@@ -774,7 +744,7 @@ int smbr_forward_backward(
     float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
     void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream,
-    const int32_t* pdf_classes, int num_classes, int targets_are_classes) {
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes, int form) {
   const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
   const Rows rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D};
   int rc = bad_dtype(who, nnet_output_dtype);
@@ -786,20 +756,28 @@ int smbr_forward_backward(
   if (K < 1) return fail(PYCHAIN_HIP_EINVAL, "%s: K must be at least 1, got %d", who, K);
   if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
     return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
-  if (pdf_classes) {
-    if ((rc = bad_classes(who, num_classes)) != PYCHAIN_HIP_OK) return rc;
-    const size_t need = smbr_lds_bytes(H, D, num_classes);
-    if (need > kSmbrLdsBudget)
-      return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states, %d pdfs and %d classes need %zu bytes of LDS (four state vectors, four rows and the class table), a CU has %zu",
-                  who, H, D, num_classes, need, kSmbrLdsBudget);
+  if (pdf_classes && (rc = bad_classes(who, num_classes)) != PYCHAIN_HIP_OK) return rc;
+  const int C = pdf_classes ? num_classes : 0;
+  int run = PYCHAIN_HIP_SMBR_LDS;
+  if (form == kSmbrFormOfOld) {
+    if (pdf_classes) {
+      const size_t need = smbr_lds_bytes(H, D, num_classes);
+      if (need > kSmbrLdsBudget)
+        return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states, %d pdfs and %d classes need %zu bytes of LDS (four state vectors, four rows and the class table), a CU has %zu",
+                    who, H, D, num_classes, need, kSmbrLdsBudget);
+    }
+    const size_t lds = smbr_recursion_lds(H, D);
+    if (!pdf_classes && lds + kSmStaticLds > kSmbrLdsBudget)
+      return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states and %d pdfs need %zu bytes of LDS (four state vectors and four rows), a CU has %zu",
+                  who, H, D, lds + kSmStaticLds, kSmbrLdsBudget);
+  } else if ((run = smbr_resolve_form(who, H, D, C, form)) < 0) {
+    return run;
   }
-  const size_t lds = smbr_recursion_lds(H, D);
-  if (!pdf_classes && lds + kSmStaticLds > kSmbrLdsBudget)
-    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states and %d pdfs need %zu bytes of LDS (four state vectors and four rows), a CU has %zu",
-                who, H, D, lds + kSmStaticLds, kSmbrLdsBudget);
   if ((size_t)B * (T + 1) > (size_t)INT_MAX) return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: B * (T + 1) = %zu rows", who, (size_t)B * (T + 1));
   const SmbrCarve c = smbr_carve(B, T, H);
-  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, c.total);
+  SmbrGeneralCarve gc = smbr_general_carve(c, B, T, D, C);
+  const size_t ws_need = run == PYCHAIN_HIP_SMBR_LDS ? c.total : gc.total;     // (the LDS form takes the trajectories alone)
+  if (workspace_bytes < ws_need) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, ws_need);
   char* base = ws_base(workspace);
   SmbrArgs a;
   memset(&a, 0, sizeof(a));
@@ -810,8 +788,15 @@ int smbr_forward_backward(
   a.al = (float*)(base + c.al); a.ab = (float*)(base + c.ab); a.be = (float*)(base + c.be); a.bb = (float*)(base + c.bb);
   a.tot_a = (float*)(base + c.tot_a); a.tot_b = (float*)(base + c.tot_b); a.seq_bad = (int32_t*)(base + c.seq_bad);
   a.B = B; a.T = T; a.D = D; a.Kt = K;
-  const hipError_t err = pdf_classes ? launch_smbr(a, SmbrClasses{pdf_classes, num_classes, targets_are_classes != 0, nullptr}, (hipStream_t)stream)
-                                     : launch_smbr(a, (hipStream_t)stream);
+  const SmbrClasses cl{pdf_classes, C, targets_are_classes != 0, nullptr};
+  hipError_t err;
+  if (run == PYCHAIN_HIP_SMBR_LDS) {
+    err = pdf_classes ? launch_smbr(a, cl, (hipStream_t)stream) : launch_smbr(a, (hipStream_t)stream);
+  } else {
+    gc.s.rec = (float*)(base + gc.rec); gc.s.grad = (float*)(base + gc.grad);
+    gc.s.state_lds = run == PYCHAIN_HIP_SMBR_ROWS;
+    err = launch_smbr_general(a, cl, gc.s, (hipStream_t)stream);
+  }
   if (err != hipSuccess) return launch_failed(who, err, nullptr);
   return PYCHAIN_HIP_OK;
 }
@@ -828,7 +813,7 @@ extern "C" int pychain_hip_smbr_forward_backward(
   return smbr_forward_backward("smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs,
                                nnet_output, nnet_output_dtype, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc,
                                leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing, bad_count,
-                               workspace, workspace_bytes, stream, nullptr, 0, 0);
+                               workspace, workspace_bytes, stream, nullptr, 0, 0, kSmbrFormOfOld);
 }
 
 extern "C" int pychain_hip_smbr_forward_backward_classes(
@@ -844,5 +829,24 @@ extern "C" int pychain_hip_smbr_forward_backward_classes(
   return smbr_forward_backward(pdf_classes ? "smbr_forward_backward_classes" : "smbr_forward_backward", ft, fi, fp, bt, bi, bp, leaky, initial,
                                final_, pdf_arcs, pdf_index, H, num_arcs, nnet_output, nnet_output_dtype, seq_lengths, B, T, D, target_pdfs,
                                target_probs, K, frame_acc, leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing,
-                               bad_count, workspace, workspace_bytes, stream, pdf_classes, num_classes, targets_are_classes);
+                               bad_count, workspace, workspace_bytes, stream, pdf_classes, num_classes, targets_are_classes, kSmbrFormOfOld);
+}
+
+// any H, num_pdfs, num_classes: `form` picks the kernels, PYCHAIN_HIP_SMBR_LDS today's launches
+extern "C" int pychain_hip_smbr_forward_backward_general(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    const int32_t* target_pdfs, const float* target_probs, int K, const float* frame_acc,
+    float leaky_hmm_coefficient, float grad_scale, const float* grad_scale_dev,
+    void* grad, double* acc_per_seq, float* closing, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream,
+    const int32_t* pdf_classes, int num_classes, int targets_are_classes, int form) {
+  if (!pdf_classes && targets_are_classes) return classes_without_map("smbr_forward_backward_general");
+  if (form < PYCHAIN_HIP_SMBR_AUTO || form > PYCHAIN_HIP_SMBR_GLOBAL)
+    return fail(PYCHAIN_HIP_EINVAL, "smbr_forward_backward_general: unknown form %d (PYCHAIN_HIP_SMBR_AUTO .. _GLOBAL)", form);
+  return smbr_forward_backward("smbr_forward_backward_general", ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs,
+                               nnet_output, nnet_output_dtype, seq_lengths, B, T, D, target_pdfs, target_probs, K, frame_acc,
+                               leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing, bad_count,
+                               workspace, workspace_bytes, stream, pdf_classes, num_classes, targets_are_classes, form);
 }

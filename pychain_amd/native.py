@@ -760,15 +760,28 @@ def _classes_args(classes, num_classes, targets_are_classes, D, device, who):
     return classes, int(num_classes), int(bool(targets_are_classes))
 
 
+SMBR_FORMS = {"lds": _lib.SMBR_LDS, "auto": _lib.SMBR_AUTO, "rows": _lib.SMBR_ROWS, "global": _lib.SMBR_GLOBAL}
+
+
+def smbr_form_code(form, who="smbr"):
+    """PYCHAIN_HIP_SMBR_* of `form` ("lds", "auto", "rows", "global"); ValueError for anything else."""
+    if not isinstance(form, str) or form not in SMBR_FORMS:
+        raise ValueError("%s: the kernels must be one of %s, got %r" % (who, ", ".join(repr(k) for k in SMBR_FORMS), form))
+    return SMBR_FORMS[form]
+
+
 def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, grad_scale_dev=None, *,
-         classes=None, num_classes=0, targets_are_classes=False):
+         classes=None, num_classes=0, targets_are_classes=False, form="lds"):
     """Lattice-free sMBR on the GPU (include/pychain_hip.h: pychain_hip_smbr_frame_accuracy, then pychain_hip_smbr_forward_backward),
     on the current stream.  `gt`: smbr_graph(...); `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernels as it is; `gamma`: the
     denominator's occupancies of x, float32 [B,T,D]; `pdfs` / `probs`: [B,T,K].  Returns (acc_per_seq float64 [B], grad in x's
     dtype, bad_count int32 [2], closing float32 [B], frame_acc float32 [B,T] - beyond a length not written).  With `classes`
     (smbr_classes(...): int32 [D] on the device) and `num_classes` the accuracy is by class (the *_classes entry points);
-    `targets_are_classes`: the ids of `pdfs` are classes already."""
+    `targets_are_classes`: the ids of `pdfs` are classes already.  `form`: "lds" - the two entry points above, which refuse a
+    graph and tree beyond the LDS of a CU -, or "auto", "rows", "global": pychain_hip_smbr_forward_backward_general with that
+    form (any H, D, C; the bits of "lds" wherever both run)."""
     _require_device(x, "nnet_output")
+    form_code = smbr_form_code(form)
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
     # (x is read one element at a time - include/pychain_hip.h: pychain_hip_smbr_forward_backward, "any element-aligned start";
@@ -801,12 +814,18 @@ def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5,
             wa = _workspace(L.pychain_hip_smbr_frame_accuracy_classes_workspace_bytes(B, T), dev, "smbr_acc")
             _lib.check(L.pychain_hip_smbr_frame_accuracy_classes(*acc_args, cls[0].data_ptr(), cls[1], cls[2], wa.data_ptr(), wa.numel()),
                        "pychain_hip_smbr_frame_accuracy_classes")
-        ws = _workspace(L.pychain_hip_smbr_workspace_bytes(B, T, H), dev, "smbr")
+        if form == "lds":
+            ws = _workspace(L.pychain_hip_smbr_workspace_bytes(B, T, H), dev, "smbr")
+        else:
+            ws = _workspace(L.pychain_hip_smbr_general_workspace_bytes(B, T, H, D, cls[1] if cls else 0), dev, "smbr")
         args = (*[t.data_ptr() for t in gt], H, K, x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
                 pd.data_ptr(), pr.data_ptr(), int(pd.shape[2]), frame_acc.data_ptr(), float(leaky_coefficient), float(grad_scale),
                 _ptr(grad_scale_dev), grad.data_ptr(), acc.data_ptr(), closing.data_ptr(), bad.data_ptr(),
                 ws.data_ptr(), ws.numel(), _stream(dev))
-        if cls is None:
+        if form != "lds":
+            tail = (cls[0].data_ptr(), cls[1], cls[2]) if cls else (None, 0, 0)
+            _lib.check(L.pychain_hip_smbr_forward_backward_general(*args, *tail, form_code), "pychain_hip_smbr_forward_backward_general")
+        elif cls is None:
             _lib.check(L.pychain_hip_smbr_forward_backward(*args), "pychain_hip_smbr_forward_backward")
         else:
             _lib.check(L.pychain_hip_smbr_forward_backward_classes(*args, cls[0].data_ptr(), cls[1], cls[2]),
@@ -815,8 +834,10 @@ def smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5,
 
 
 def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1e-5, grad_scale=1.0, *,
-             classes=None, num_classes=0, targets_are_classes=False):
-    """The same on CPU tensors: the host twins (pychain_hip_cpu_smbr_*), fp32 rows and gradient."""
+             classes=None, num_classes=0, targets_are_classes=False, form="lds"):
+    """The same on CPU tensors: the host twins (pychain_hip_cpu_smbr_*), fp32 rows and gradient.  `form` is checked and changes
+    nothing: the one host twin has no size limit."""
+    smbr_form_code(form, "cpu_smbr")
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_smbr is for CPU tensors; device tensors run on the HIP kernels")
     xf, lc = _host_inputs(x, lengths)

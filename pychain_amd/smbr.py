@@ -44,8 +44,9 @@ class SMBRFunction(torch.autograd.Function):
     the forward call for an upstream gradient of 1; backward rescales it (as PosteriorNumeratorFunction does)."""
 
     @staticmethod
-    def forward(ctx, input, lengths, den_graph, targets, leaky_coefficient, classes=None, targets_are_classes=False):
+    def forward(ctx, input, lengths, den_graph, targets, leaky_coefficient, classes=None, targets_are_classes=False, kernels="lds"):
         x = input.detach()
+        native.smbr_form_code(kernels, "expected_accuracy")                     # (ValueError, on CPU tensors too)
         if x.dim() != 3:
             raise ValueError("the network output must be [B, T, D], got %s" % list(x.shape))
         if not isinstance(targets, PosteriorTargets):
@@ -60,7 +61,7 @@ class SMBRFunction(torch.autograd.Function):
         else:
             cls = native.smbr_classes(classes, D, x.device) + (bool(targets_are_classes),)       # (checked, uploaded once)
             targets.check(B, T, cls[1] if targets_are_classes else D)
-        evaluate = lambda: SMBRFunction._evaluate(x, lengths, graph, targets, float(leaky_coefficient), cls)
+        evaluate = lambda: SMBRFunction._evaluate(x, lengths, graph, targets, float(leaky_coefficient), cls, kernels)
         acc, grad, bad, closing = evaluate()
         ctx.grad_buf = grad
         ctx.again = _recompute(x, evaluate, lambda r: r[1])
@@ -70,10 +71,11 @@ class SMBRFunction(torch.autograd.Function):
         return out
 
     @staticmethod
-    def _evaluate(x, lengths, graph, targets, coef, cls=None):
+    def _evaluate(x, lengths, graph, targets, coef, cls=None, kernels="lds"):
         """(E_b float64 [B], the gradient for an upstream gradient of 1, bad_count int32 [2], closing float32 [B]); `cls`: (the
-        class map on x's device, C, targets_are_classes) or None"""
+        class map on x's device, C, targets_are_classes) or None; `kernels`: native.smbr's `form`"""
         kw = {} if cls is None else dict(classes=cls[0], num_classes=cls[1], targets_are_classes=cls[2])
+        kw["form"] = kernels
         tg = targets.to(x.device)
         D = x.size(2)
         gt = native.smbr_graph(graph, D, x.device)                              # (checks the graph against D before anything runs)
@@ -88,10 +90,10 @@ class SMBRFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        return _grad_written_in_forward(ctx, g), None, None, None, None, None, None
+        return _grad_written_in_forward(ctx, g), None, None, None, None, None, None, None
 
 
-def expected_accuracy(x, lengths, den_graph, targets, leaky_coefficient=1e-5, *, classes=None, targets_are_classes=False):
+def expected_accuracy(x, lengths, den_graph, targets, leaky_coefficient=1e-5, *, classes=None, targets_are_classes=False, kernels="lds"):
     """The expected frame accuracy sum_b E_b of the denominator's paths against `targets` (PosteriorTargets: an alignment through
     PosteriorTargets.from_alignment, or posterior targets), as a 0-dim tensor differentiable in x (neither the clamp nor the
     reference is differentiated).  `den_graph`: a probability-domain ChainGraph, or a ChainGraphBatch made of one.  Of the
@@ -105,24 +107,33 @@ def expected_accuracy(x, lengths, den_graph, targets, leaky_coefficient=1e-5, *,
     of `targets` are classes already (PosteriorTargets.to_classes, or a reference from another tree) and are held against C.
     `bad_count[1]` then counts the entries out of range of what they name.  The int32 device copy of `classes` is cached until
     the tensor is replaced or edited in place; making it reads the tensor on the host (one synchronisation for a device tensor).
-    ValueError for a map of the wrong length or dtype, a negative entry, or targets_are_classes without classes."""
-    return SMBRFunction.apply(x, lengths, den_graph, targets, leaky_coefficient, classes, targets_are_classes)
+    ValueError for a map of the wrong length or dtype, a negative entry, or targets_are_classes without classes.
+
+    `kernels` (device tensors): "lds", the default - four state vectors and four rows of a frame in the 160 KiB
+    of a CU's LDS, a graph and tree beyond that refused (3000 states with more than about 7 200 pdfs); "auto" - those kernels
+    where they fit, else the general ones, which take any graph and tree and are slower; "rows" / "global" - the two general forms
+    by name.  Every form gives the same bits on a shape it takes.  ValueError for anything else; CPU tensors accept the keyword
+    and run the one host twin."""
+    return SMBRFunction.apply(x, lengths, den_graph, targets, leaky_coefficient, classes, targets_are_classes, kernels)
 
 
 class SMBRLoss(nn.Module):
     """-sum_b E_b, divided by the number of frames when `avg`: the sMBR criterion to MINIMISE, usually interpolated with
-    ChainLoss by plain addition.  `classes`: the accuracy by class (expected_accuracy)."""
+    ChainLoss by plain addition.  `classes`: the accuracy by class (expected_accuracy).  `kernels`: "lds" (the default), "auto" for
+    a tree beyond the LDS of a CU, "rows", "global" (expected_accuracy)."""
 
-    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, classes=None):
+    def __init__(self, den_graph, leaky_coefficient=1e-5, avg=True, classes=None, kernels="lds"):
         super(SMBRLoss, self).__init__()
         self.den_graph = den_graph
         self.leaky_coefficient = leaky_coefficient
         self.avg = avg
         self.classes = classes
+        self.kernels = kernels
+        native.smbr_form_code(kernels, "SMBRLoss")
 
     def forward(self, x, x_lengths, targets, targets_are_classes=False):
         acc = expected_accuracy(x, x_lengths, self.den_graph, targets, self.leaky_coefficient, classes=self.classes,
-                                targets_are_classes=targets_are_classes)
+                                targets_are_classes=targets_are_classes, kernels=self.kernels)
         loss = -acc
         if self.avg:
             loss = loss / torch.as_tensor(x_lengths).sum().to(device=acc.device, dtype=acc.dtype)
