@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 29
+#define PYCHAIN_HIP_ABI_VERSION 30
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -985,6 +985,64 @@ int pychain_hip_smbr_forward_backward_general(
     void* grad /* nnet_output_dtype */, double* acc_per_seq, float* closing, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream,
     const int32_t* pdf_classes, int num_classes, int targets_are_classes, int form);
+
+/* ------------------------------------------------------------------------
+ * Expected arc counts: the gradient of the denominator objective in the ARC WEIGHTS of its graph (ABI 30; DESIGN.md §3.29;
+ * csrc/arc_counts.hip).  Let log Z_b(w) be the denominator objective of sequence b with every arc probability p_k replaced by
+ * p_k exp(w_k), w = arc_log_weights in the order of forward_transitions (NULL: w = 0).  With x = exp(clamp(y, -30, 30)) and the
+ * leaky HMM of the denominator, v' = v + c leaky sum(v) forwards and u' = u + c sum(leaky u) backwards,
+ *
+ *   post(b,t,k) = alpha'(t,src_k) p_k e^{w_k} x(t,pdf_k) beta'(t+1,dst_k) / (the same summed over the arcs)      sums to 1 over k
+ *   c(b,k)      = d log Z_b / d w_k = sum_{t < L_b} post(b,t,k)                                                  sums to L_b over k
+ *   gamma(b,t,n) = d log Z_b / d y(t,n) = the sum of post(b,t,k) over the arcs that carry pdf n
+ *
+ * - the expected number of times a path of the denominator takes arc k: the E-step statistics of the graph, and what training
+ * the graph's weights (a learnable phone bigram, an LM or transition scale) needs.  At w = 0 log Z_b is the objective of
+ * pychain_hip_den_forward_backward.  leaky_probs, initial_probs and final_probs are HELD FIXED: they are the caller's arrays, not
+ * recomputed from the weighted graph and not differentiated; neither is the clamp.
+ *
+ * Arguments: the nine graph arrays in the reference layout and the arcs by pdf (pdf_arcs, pdf_index) as the sMBR entry points
+ * take them; the backward arrays must hold the same arcs as the forward ones (an arc's backward copy finds its weight by its
+ * endpoints, pdf and probability; arcs equal in all four pair up in order).  arc_log_weights: fp32 [num_transitions] or NULL; a
+ * weight that is not finite is counted in bad_count[1] and taken as 0.  nnet_output [B,T,num_pdfs] in nnet_output_dtype, any
+ * element-aligned start.  seq_weights: fp32 [B] or NULL (every u_b = 1).  Outputs:
+ *   objf_per_seq    fp64 [B]: log Z_b; NaN for a sequence that went bad
+ *   counts          fp64 [num_transitions]: sum_b u_b c(b,k)
+ *   counts_per_seq  fp64 [B, num_transitions] or NULL: c(b,k), not weighted; zeros for a sequence that went bad
+ *   grad            [B,T,num_pdfs] in nnet_output_dtype, or NULL (counts only): s u_b gamma(b,t,n), s = grad_scale
+ *                   (* *grad_scale_dev where given); rows t >= L_b are exact zeros; a pdf no arc carries gets an exact zero and
+ *                   its x is not read
+ *   bad_count       int32 [2], zeroed by the call: [0] the sequences that went bad - a NaN in a live row, a frame total or a
+ *                   frame divisor that is not positive and finite -, each counted once; [1] the weights that are not finite.
+ * A bad sequence adds exact zeros to counts and leaves every other sequence's results bit-identical to a call where its
+ * weight is 0.  No float atomics: fp32 vectors, every sum over time and over sequences in fp64 in a fixed order, so two calls
+ * give the same bits; the 2-byte forms equal the fp32 form on the up-cast input, the gradient rounded once.
+ * Launches: p exp(w) once; the recursions, 2B persistent workgroups with one state vector and the frame's row double-buffered in
+ * LDS; the counts, time-parallel, a workgroup per run of 64 frames of a sequence with a partial row of num_transitions doubles;
+ * log Z_b; the sums.  pychain_hip_den_arc_counts_lds_bytes(num_states, num_pdfs) = (2 H + 2 D + 64) * 4 + 256 must be within
+ * 160 KiB: a larger graph is refused with PYCHAIN_HIP_EUNSUPPORTED and the sizes in the message (no general form yet).
+ * Workspace: pychain_hip_den_arc_counts_workspace_bytes - the two trajectories, 8 (T+1) H B bytes, and B ceil(T / 64) partial rows.
+ * pychain_hip_cpu_den_arc_counts: the host twin, the same equations with fp32 vectors, fp64 sums and host threads over the
+ * sequences; fp32 rows and gradient. */
+size_t pychain_hip_den_arc_counts_workspace_bytes(int B, int T, int num_states, int num_transitions);
+size_t pychain_hip_den_arc_counts_lds_bytes(int num_states, int num_pdfs);
+int pychain_hip_den_arc_counts(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const float* arc_log_weights, const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
+    void* grad /* nnet_output_dtype */, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream);
+int pychain_hip_cpu_den_arc_counts(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const float* arc_log_weights, const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count, int num_threads);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

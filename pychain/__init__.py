@@ -6,6 +6,7 @@ from pychain_amd import native as _native, simplefst as _simplefst
 from pychain_amd.graph import *  # noqa: F401,F403
 from pychain_amd.loss import *  # noqa: F401,F403
 from pychain_amd.smbr import *  # noqa: F401,F403
+from pychain_amd.arcs import *  # noqa: F401,F403
 
 # `import pychain_C` / `import simplefst` written against the reference keep working
 _sys.modules.setdefault("pychain_C", _native)

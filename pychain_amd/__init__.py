@@ -31,3 +31,4 @@ from .loss import ChainFunction, ChainLoss, ChainLossFunction, numerator_xent, o
 from .loss import PosteriorTargets, occupancies, posterior_numerator, posterior_targets, posterior_xent, boost_rows  # noqa: F401
 from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401
 from .smbr import SMBRFunction, SMBRLoss, expected_accuracy  # noqa: F401
+from .arcs import ArcCounts, DenLogPartitionFunction, den_log_partition, expected_arc_counts  # noqa: F401

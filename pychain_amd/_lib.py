@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 29
+ABI_VERSION = 30
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -50,6 +50,7 @@ _FORWARD_BACKWARD = _FUSED_HEAD + [_f] + [_vp] * 4 + _FUSED_TAIL             # g
 _SMBR_GRAPH = [_vp] * 11 + [_i, _i]                                          # the nine graph tensors, pdf_arcs, pdf_index, H, K
 _SMBR_CLASSES = [_vp, _i, _i]                                                # pdf_classes, num_classes, targets_are_classes
 _SMBR_TAIL = [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]            # targets, K, frame_acc, coef, grad_scale[_dev], grad, acc, closing, bad
+_ARC_TAIL = [_f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]                          # coef, seq_weights, grad_scale[_dev], grad, objf, counts, counts_per_seq, bad
 
 _SIGNATURES = {
     "pychain_hip_abi_version": (_i, []),
@@ -131,6 +132,11 @@ _SIGNATURES = {
     "pychain_hip_smbr_general_lds_bytes": (_sz, [_i]),
     "pychain_hip_smbr_general_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "pychain_hip_smbr_forward_backward_general": (_i, _SMBR_GRAPH + _ROWS + [_i] * 3 + _SMBR_TAIL + _WS + [_vp] + _SMBR_CLASSES + [_i]),
+    # (ABI 30: expected arc counts - the gradient of the denominator objective in the arc weights of its graph)
+    "pychain_hip_den_arc_counts_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "pychain_hip_den_arc_counts_lds_bytes": (_sz, [_i, _i]),
+    "pychain_hip_den_arc_counts": (_i, _SMBR_GRAPH + [_vp] + _ROWS + [_i] * 3 + _ARC_TAIL + _WS + [_vp]),
+    "pychain_hip_cpu_den_arc_counts": (_i, _SMBR_GRAPH + [_vp] + _CPU_ROWS + [_i] * 3 + _ARC_TAIL + [_i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),

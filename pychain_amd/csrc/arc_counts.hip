@@ -1,0 +1,408 @@
+// arc_counts.hip - expected arc counts of the denominator's path distribution (include/pychain_hip.h: pychain_hip_den_arc_counts;
+// DESIGN.md §3.29): with every arc probability p_k replaced by p_k exp(w_k),
+//
+//   c(b,k) = d log Z_b / d w_k = sum_t alpha'(t,src_k) p_k e^{w_k} x(t,pdf_k) beta'(t+1,dst_k) / (the same summed over the arcs at t)
+//
+// the arc-level form of the occupancy identity (§3.3): the E-step statistics of the graph, and the gradient of log Z_b in the
+// arc log-weights.  The plan-compiled kernels bake the probabilities in, so this is a path of its own over the reference layout:
+//
+//   arc_weight_kernel      once per call: pw(k) = p_k exp(w_k) in the forward order and in the backward order (the backward copy of
+//                          an arc finds its forward id by its endpoints, pdf and probability; arcs equal in all four pair up in
+//                          order).  A weight that is not finite counts in bad_count[1] and is taken as 0.
+//   arc_recursion_kernel   smbr_recursion_kernel without its weighted pair: 2B persistent workgroups, one per (sequence, direction),
+//                          the state vector and the row x = exp(clamp(y)) double-buffered in LDS, the row made a frame ahead; a
+//                          thread owns states tid, tid + 1024, ...; alpha' and beta', normalised per frame, go to the workspace
+//                          with the totals divided out.
+//   arc_count_kernel       time-parallel over (sequence, run of kArcFrames frames): alpha'(t) and beta'(t+1) in LDS, a thread owns
+//                          pdfs tid, tid + 512, ... and walks that pdf's arcs through the caller's by-pdf order, twice: for the
+//                          frame's divisor sum_n x(n) q0(n), then for the arc posteriors, which it adds to the workgroup's partial
+//                          row [K] (fp64) in the workspace - every arc has one owner, so this is a plain read-modify-write - while
+//                          gamma(t,n) = x(n) q0(n) / divisor is the thread's own sum and is stored once, in x's type.
+//   arc_objf_kernel        log Z_b = sum_t log tot(t) + log sum_j alpha'(L,j) final(j) in fp64, and the sequence's verdict
+//   arc_reduce_kernel      counts(k) = sum_b u_b sum_j partial(b,j,k): fp64, the workgroups of a sequence in ascending j, then the
+//                          sequences in ascending b.  A sequence that went bad, or whose weight is 0, is left out.
+// Nothing is atomic but integer counters; every sum has a fixed order, so a call gives the same bits every time.  Contraction is
+// off for the whole unit, as in smbr.hip: the 2-byte forms compute what the fp32 form computes on the up-cast input.
+// A frame is kept in LDS; a graph beyond a CU's LDS is refused (a general form: DESIGN.md §8).
+#include <hip/hip_runtime.h>
+
+#include <climits>
+#include <cstring>
+
+#pragma clang fp contract(off)      // ahead of the project's headers: their inline helpers (clamp_exp, the row loads) are under it too
+
+#include "../../include/pychain_hip.h"
+#include "call_args.h"
+#include "common.h"
+#include "row_access.h"
+#include "smbr.h"
+#include "smbr_device.h"
+
+namespace pychain_hip {
+namespace {
+
+// 64 frames a count workgroup: at the benchmark shape (B = 64, T = 1500, K = 30000) 64 x 24 partial rows of 240 kB, 369 MB
+constexpr int kArcFrames = 64;
+constexpr int kArcNT = 256;                 // the small kernels
+
+struct ArcArgs {
+  SmbrGraph g;
+  const float* lw;                       // [K] arc log-weights in the forward order, or null
+  const void* x; int x_half;             // [B,T,D] raw
+  const int64_t* lengths;
+  const float* seq_w;                    // [B] or null
+  float coef, grad_scale; const float* grad_scale_dev;
+  void* grad;                            // [B,T,D] out in x's type, or null
+  double* objf;                          // [B]
+  double* counts;                        // [K]
+  double* counts_per_seq;                // [B,K] or null
+  int32_t* bad_count;                    // [2]
+  float *pwf, *pwb;                      // workspace: [K] p exp(w) in the forward / in the backward order
+  float *al, *be;                        // workspace: [B][T+1][H]
+  float *tot_a, *tot_b;                  // workspace: [B][T+1]
+  int32_t* seq_bad;                      // workspace: [3][B], zeroed: what the recursions found, the count frames, the verdict
+  double* partial;                       // workspace: [B][nblk][K]
+  int B, T, D, nblk;
+};
+
+// ---- p exp(w) ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float arc_weighted(const float* lw, int id, float p, bool& bad) {
+  if (!lw || id < 0) return p;
+  const float w = lw[id];
+  if (!(w - w == 0.f)) { bad = true; return p; }                               // NaN, +-inf: counted, taken as 0
+  return p * expf(w);
+}
+__global__ __launch_bounds__(kArcNT) void arc_weight_kernel(const ArcArgs a) {
+  const SmbrGraph& g = a.g;
+  const int k = blockIdx.x * kArcNT + threadIdx.x;
+  if (k >= g.K) return;
+  bool bad = false, none = false;
+  a.pwf[k] = arc_weighted(a.lw, k, g.fp[k], bad);
+  if (bad) atomicAdd(a.bad_count + 1, 1);                                      // (an integer count)
+  // the backward copy k of an arc: the r-th of its source's run with these endpoints, pdf and probability, r its rank among the
+  // equal arcs of its destination's run
+  const int src = g.bt[3 * k], dst = g.bt[3 * k + 1], pdf = g.bt[3 * k + 2];
+  const float p = g.bp[k];
+  int id = -1;
+  if (a.lw && src >= 0 && src < g.H && dst >= 0 && dst < g.H) {
+    int rank = 0;
+    for (int j = max(g.bi[2 * dst], 0); j < k; j++)
+      if (g.bt[3 * j] == src && g.bt[3 * j + 2] == pdf && g.bp[j] == p) rank++;
+    const int j1 = min(g.fi[2 * src + 1], g.K);
+    for (int j = max(g.fi[2 * src], 0); j < j1; j++)
+      if (g.ft[3 * j + 1] == dst && g.ft[3 * j + 2] == pdf && g.fp[j] == p && rank-- == 0) { id = j; break; }
+  }
+  a.pwb[k] = arc_weighted(a.lw, id, p, none);
+}
+
+// ---- the recursions ---------------------------------------------------------------------------------------------------------------
+template <int XH, bool FWD>
+__device__ __forceinline__ void arc_recursion(const ArcArgs& a, int b, float* lds) {
+  const int tid = threadIdx.x;
+  const SmbrGraph& g = a.g;
+  const int H = g.H, D = a.D, T = a.T;
+  const int L = seq_len(a.lengths, b, T);
+  float* const vec0 = lds;                       // [2][H] alpha' / beta'
+  float* const xrow = vec0 + 2 * (size_t)H;      // [2][D] x
+  float* const red = xrow + 2 * (size_t)D;
+  const size_t seq_rows = (size_t)b * (T + 1);
+  float* const st0 = (FWD ? a.al : a.be) + seq_rows * H;
+  float* const totv = (FWD ? a.tot_a : a.tot_b) + seq_rows;
+  const int32_t* const idx = FWD ? g.bi : g.fi;                // forwards: the arcs ENTERING a state; backwards: those leaving it
+  const int32_t* const arc = FWD ? g.bt : g.ft;
+  const float* const pr = FWD ? a.pwb : a.pwf;
+  const float coef = a.coef;
+  const size_t xseq = (size_t)b * T * D;
+  bool bad = false, nan = false;
+
+  // the first row: alpha'(0) from the initial, beta'(L) from the final probabilities
+  {
+    const float* start = FWD ? g.init : g.fin;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int i = tid; i < H; i += kSmNT) { s0 += start[i]; s1 += start[i] * g.leaky[i]; }
+    block_sum3<kSmNT>(s0, s1, s2, red, tid);
+    const float inv = 1.f / s0;
+    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
+    const int r0 = FWD ? 0 : L;
+    if (tid == 0) totv[r0] = s0;
+    for (int i = tid; i < H; i += kSmNT) {
+      const float v = FWD ? start[i] * inv + coef * g.leaky[i] : (start[i] + coef * s1) * inv;
+      vec0[i] = v;
+      st0[(size_t)r0 * H + i] = v;
+    }
+    const int t0 = FWD ? 0 : L - 1;
+    float held[kSmXR];
+    hold_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held);
+    nan = put_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held, xrow) || nan;
+    __syncthreads();
+  }
+  // frame j: forwards alpha'(t+1) from alpha'(t) and x(t), t = j; backwards beta'(t) from beta'(t+1) and x(t), t = L-1-j
+  for (int j = 0; j < L; j++) {
+    const int p = j & 1;
+    const int t = FWD ? j : L - 1 - j, tn = FWD ? t + 1 : t - 1;
+    const bool more = j + 1 < L;
+    const float* v0 = vec0 + (size_t)p * H;
+    float* w0 = vec0 + (size_t)(1 - p) * H;
+    const float* xr = xrow + (size_t)p * D;
+    float* xrn = xrow + (size_t)(1 - p) * D;
+    float held[kSmXR];
+    if (more) hold_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held);          // the next frame's row: in flight over the arc loop
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int i = tid; i < H; i += kSmNT) {
+      float acc0 = 0.f;
+      const int k1 = idx[2 * i + 1];
+      for (int k = idx[2 * i]; k < k1; k++) {
+        const int other = arc[3 * k + (FWD ? 0 : 1)], n = arc[3 * k + 2];
+        const float wu = pr[k] * v0[other];
+        acc0 += wu * xr[n];
+      }
+      w0[i] = acc0;                                                            // raw, finished below by the thread that wrote it
+      s0 += acc0;
+      if (!FWD) s1 += acc0 * g.leaky[i];
+    }
+    if (more) nan = put_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held, xrn) || nan;
+    block_sum3<kSmNT>(s0, s1, s2, red, tid);                                   // (its barrier: the next row is whole)
+    const float inv = 1.f / s0;
+    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
+    const int r = FWD ? t + 1 : t;
+    if (tid == 0) totv[r] = s0;
+    float* o0 = st0 + (size_t)r * H;
+    for (int i = tid; i < H; i += kSmNT) {
+      const float c0 = FWD ? w0[i] * inv + coef * g.leaky[i] : (w0[i] + coef * s1) * inv;
+      w0[i] = c0;
+      o0[i] = c0;
+    }
+    __syncthreads();
+  }
+  // a NaN in a live row of x (the clamp turns it into exp(-30): watched by the forward workgroup), a total that is not positive and
+  // finite: the sequence is bad.  (Both workgroups of a sequence may store the same 1.)
+  if (__syncthreads_or((bad || (FWD && nan)) ? 1 : 0) && tid == 0) a.seq_bad[b] = 1;
+}
+
+template <int XH>
+__global__ __launch_bounds__(kSmNT) void arc_recursion_kernel(const ArcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  if (blockIdx.x < (unsigned)a.B) arc_recursion<XH, true>(a, blockIdx.x, lds);
+  else arc_recursion<XH, false>(a, blockIdx.x - a.B, lds);
+}
+
+// ---- the counts -------------------------------------------------------------------------------------------------------------------
+template <int XH>
+__global__ __launch_bounds__(kSmGNT) void arc_count_kernel(const ArcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int tid = threadIdx.x, b = blockIdx.y;
+  const SmbrGraph& g = a.g;
+  const int H = g.H, D = a.D, T = a.T;
+  const int L = seq_len(a.lengths, b, T);
+  float* const sa = lds;                          // alpha'(t)
+  float* const sb = sa + H;                       // beta'(t+1)
+  float* const gx = sb + H;                       // [D] x
+  float* const gq = gx + D;                       // [D] x q0
+  float* const red = gq + D;
+  const size_t seq_rows = (size_t)b * (T + 1);
+  float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
+  if (a.seq_w) gscale = gscale * a.seq_w[b];
+  double* const prow = a.partial + ((size_t)b * a.nblk + blockIdx.x) * g.K;    // (written from the first live frame on: read by
+  bool first = true;                                                           // the reduction only where the run has one)
+  const int t_begin = blockIdx.x * kArcFrames, t_end = min(t_begin + kArcFrames, T);
+  for (int t = t_begin; t < t_end; t++) {
+    const size_t row = ((size_t)b * T + t) * D;
+    if (t >= L) {                                                              // padding: exact zeros
+      if (a.grad)
+        for (int n = tid; n < D; n += kSmGNT) row_store1<XH>(a.grad, row + n, 0.f);
+      continue;
+    }
+    const size_t r0 = (seq_rows + t) * H, r1 = r0 + H;
+    for (int i = tid; i < H; i += kSmGNT) { sa[i] = a.al[r0 + i]; sb[i] = a.be[r1 + i]; }
+    __syncthreads();
+    float part = 0.f, none1 = 0.f, none2 = 0.f;
+    for (int n = tid; n < D; n += kSmGNT) {
+      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
+      float q0 = 0.f;
+      for (int k = k0; k < k1; k++) {
+        const int id = g.parc[k];
+        q0 += (a.pwf[id] * sa[g.ft[3 * id]]) * sb[g.ft[3 * id + 1]];
+      }
+      float xx = 0.f, v0 = 0.f;
+      if (k0 != k1) {                                                          // a pdf no arc carries: its x is not read
+        xx = clamp_exp(row_load1<XH>(a.x, row + n), kXExpClamp);
+        v0 = xx * q0;
+      }
+      gx[n] = xx; gq[n] = v0;                                                  // (read back by this thread alone)
+      part += v0;
+    }
+    block_sum3<kSmGNT>(part, none1, none2, red, tid);
+    const float inv = 1.f / part, sc = gscale / part;
+    if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) a.seq_bad[a.B + b] = 1;      // (the same 1 whoever stores it)
+    for (int n = tid; n < D; n += kSmGNT) {
+      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
+      if (a.grad) row_store1<XH>(a.grad, row + n, k0 != k1 ? gq[n] * sc : 0.f);
+      const float xs = gx[n] * inv;
+      for (int k = k0; k < k1; k++) {
+        const int id = g.parc[k];
+        const float post = ((a.pwf[id] * sa[g.ft[3 * id]]) * sb[g.ft[3 * id + 1]]) * xs;
+        prow[id] = first ? (double)post : prow[id] + (double)post;             // the arc's one owner
+      }
+    }
+    first = false;
+    __syncthreads();                                                           // (the rows are free for the next frame)
+  }
+}
+
+// ---- log Z_b and the verdict ----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kArcNT) void arc_objf_kernel(const ArcArgs a) {
+  __shared__ double red[2][kArcNT / 64];
+  const int tid = threadIdx.x, b = blockIdx.x;
+  const int H = a.g.H, L = seq_len(a.lengths, b, a.T);
+  const size_t seq_rows = (size_t)b * (a.T + 1);
+  double lz = 0.0, c0 = 0.0;
+  for (int t = tid; t <= L; t += kArcNT) lz += log((double)a.tot_a[seq_rows + t]);
+  const float* aL = a.al + (seq_rows + L) * H;
+  for (int i = tid; i < H; i += kArcNT) c0 += (double)aL[i] * (double)a.g.fin[i];
+  lz = wave_sum_f64(lz); c0 = wave_sum_f64(c0);
+  if ((tid & 63) == 0) { red[0][tid >> 6] = lz; red[1][tid >> 6] = c0; }
+  __syncthreads();
+  if (tid == 0) {
+    lz = 0.0; c0 = 0.0;
+    for (int w = 0; w < kArcNT / 64; w++) { lz += red[0][w]; c0 += red[1][w]; }
+    lz += log(c0);
+    const bool bad = a.seq_bad[b] != 0 || a.seq_bad[a.B + b] != 0 || !(c0 > 0.0) || !(lz - lz == 0.0);
+    a.seq_bad[2 * a.B + b] = bad ? 1 : 0;
+    a.objf[b] = bad ? __builtin_nan("") : lz;
+    if (bad) atomicAdd(a.bad_count, 1);                                        // (an integer count; once per sequence)
+  }
+}
+
+// ---- the sums -------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kArcNT) void arc_reduce_kernel(const ArcArgs a) {
+  const int K = a.g.K;
+  const int k = blockIdx.x * kArcNT + threadIdx.x;
+  if (k >= K) return;
+  double total = 0.0;
+  for (int b = 0; b < a.B; b++) {
+    double s = 0.0;
+    if (!a.seq_bad[2 * a.B + b]) {
+      const int runs = (seq_len(a.lengths, b, a.T) + kArcFrames - 1) / kArcFrames;
+      const double* p = a.partial + (size_t)b * a.nblk * K + k;
+      for (int j = 0; j < runs; j++) s += p[(size_t)j * K];
+      const float u = a.seq_w ? a.seq_w[b] : 1.f;
+      if (u != 0.f) total += (double)u * s;
+    }
+    if (a.counts_per_seq) a.counts_per_seq[(size_t)b * K + k] = s;
+  }
+  a.counts[k] = total;
+}
+
+size_t arc_recursion_lds(int H, int D) { return (2 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
+size_t arc_count_lds(int H, int D) { return (2 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
+size_t arc_lds_bytes(int H, int D) {
+  const size_t r = arc_recursion_lds(H, D) + kSmStaticLds, c = arc_count_lds(H, D);
+  return r > c ? r : c;
+}
+
+template <int XH>
+hipError_t launch_as(const ArcArgs& a, hipStream_t st) {
+  const size_t lds_r = arc_recursion_lds(a.g.H, a.D), lds_c = arc_count_lds(a.g.H, a.D);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(arc_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(arc_count_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((arc_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((arc_count_kernel<XH>), dim3(a.nblk, a.B), dim3(kSmGNT), lds_c, st, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_arc_counts(const ArcArgs& a, hipStream_t st) {
+  hipError_t e = hipMemsetAsync(a.seq_bad, 0, 3 * (size_t)a.B * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(a.bad_count, 0, 2 * sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
+  const int kgrid = (a.g.K + kArcNT - 1) / kArcNT;
+  hipLaunchKernelGGL(arc_weight_kernel, dim3(kgrid), dim3(kArcNT), 0, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = a.x_half == kXF32 ? launch_as<kXF32>(a, st) : a.x_half == kXBf16 ? launch_as<kXBf16>(a, st) : launch_as<kXF16>(a, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(arc_objf_kernel, dim3(a.B), dim3(kArcNT), 0, st, a);
+  e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(arc_reduce_kernel, dim3(kgrid), dim3(kArcNT), 0, st, a);
+  return hipGetLastError();
+}
+
+struct ArcCarve { size_t al, be, tot_a, tot_b, seq_bad, pwf, pwb, partial, total; int nblk; };
+ArcCarve arc_carve(int B, int T, int H, int K) {
+  ArcCarve c;
+  const size_t traj = align256((size_t)B * (T + 1) * H * sizeof(float)), tot = align256((size_t)B * (T + 1) * sizeof(float));
+  const size_t pw = align256((size_t)K * sizeof(float));
+  c.nblk = (T + kArcFrames - 1) / kArcFrames;
+  size_t o = 0;
+  c.al = o; o += traj; c.be = o; o += traj;
+  c.tot_a = o; o += tot; c.tot_b = o; o += tot;
+  c.seq_bad = o; o += align256(3 * (size_t)B * sizeof(int32_t));
+  c.pwf = o; o += pw; c.pwb = o; o += pw;
+  c.partial = o; o += align256((size_t)B * c.nblk * K * sizeof(double));
+  c.total = o + 256;                               // (the base is aligned inside the caller's buffer)
+  return c;
+}
+
+}  // namespace
+}  // namespace pychain_hip
+
+using namespace pychain_hip;
+
+// ---- the entry points (include/pychain_hip.h) -----------------------------------------------------------------------------------
+extern "C" size_t pychain_hip_den_arc_counts_workspace_bytes(int B, int T, int H, int num_arcs) {
+  if (B <= 0 || T <= 0 || H <= 0 || num_arcs <= 0) return 0;
+  return arc_carve(B, T, H, num_arcs).total;
+}
+
+extern "C" size_t pychain_hip_den_arc_counts_lds_bytes(int H, int D) {
+  if (H <= 0 || D <= 0) return 0;
+  return arc_lds_bytes(H, D);
+}
+
+extern "C" int pychain_hip_den_arc_counts(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const float* arc_log_weights, const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int D,
+    float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
+    void* grad, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream) {
+  const char* who = "den_arc_counts";
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
+  const Rows rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D};
+  int rc = bad_dtype(who, nnet_output_dtype);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (graphs.any_null() || !leaky || !pdf_arcs || !pdf_index || !rows.x || !rows.lengths || !objf_per_seq || !counts || !bad_count || !workspace)
+    return null_pointer(who);
+  if ((rc = bad_sizes(who, rows, graphs)) != PYCHAIN_HIP_OK) return rc;
+  if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  const size_t lds = arc_lds_bytes(H, D);
+  if (lds > kSmbrLdsBudget)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: %d states and %d pdfs need %zu bytes of LDS (two state vectors and two rows), a CU has %zu",
+                who, H, D, lds, kSmbrLdsBudget);
+  if ((size_t)B * (T + 1) > (size_t)INT_MAX) return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: B * (T + 1) = %zu rows", who, (size_t)B * (T + 1));
+  const ArcCarve c = arc_carve(B, T, H, num_arcs);
+  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, c.total);
+  char* base = ws_base(workspace);
+  ArcArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = SmbrGraph{ft, fi, fp, bt, bi, bp, leaky, initial, final_, pdf_arcs, pdf_index, H, num_arcs};
+  a.lw = arc_log_weights; a.x = nnet_output; a.x_half = nnet_output_dtype; a.lengths = seq_lengths; a.seq_w = seq_weights;
+  a.coef = leaky_hmm_coefficient; a.grad_scale = grad_scale; a.grad_scale_dev = grad_scale_dev;
+  a.grad = grad; a.objf = objf_per_seq; a.counts = counts; a.counts_per_seq = counts_per_seq; a.bad_count = bad_count;
+  a.pwf = (float*)(base + c.pwf); a.pwb = (float*)(base + c.pwb);
+  a.al = (float*)(base + c.al); a.be = (float*)(base + c.be);
+  a.tot_a = (float*)(base + c.tot_a); a.tot_b = (float*)(base + c.tot_b); a.seq_bad = (int32_t*)(base + c.seq_bad);
+  a.partial = (double*)(base + c.partial);
+  a.B = B; a.T = T; a.D = D; a.nblk = c.nblk;
+  const hipError_t err = launch_arc_counts(a, (hipStream_t)stream);
+  if (err != hipSuccess) return launch_failed(who, err, nullptr);
+  return PYCHAIN_HIP_OK;
+}

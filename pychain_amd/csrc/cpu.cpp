@@ -1095,3 +1095,161 @@ extern "C" int pychain_hip_cpu_smbr_forward_backward_classes(
                                    K, frame_acc, leaky_hmm_coefficient, grad_scale, grad_scale_dev, grad, acc_per_seq, closing, bad_count,
                                    num_threads, pdf_classes ? &c : nullptr);
 }
+
+// ---- expected arc counts (include/pychain_hip.h: pychain_hip_den_arc_counts; the device: arc_counts.hip) -----------
+// The same equations with fp32 state vectors, every sum in fp64, and the sequences dealt to host threads: the plain alpha' / beta'
+// recursions of smbr_one over p exp(w), then per frame the arc posteriors alpha'(t,src) p e^w x(t,pdf) beta'(t+1,dst) / (their
+// sum), added to the sequence's counts and, by pdf, into the gradient row.
+namespace pychain_hip {
+namespace {
+bool arc_counts_one(const Csr& fwd, const Csr& bwd, const float* pwf, const float* pwb, const float* leaky, const float* init, const float* fin,
+                    const int32_t* parc, const int32_t* pidx, int H, const float* x, int L, int D, float coef, float gscale,
+                    float* grad, double* counts, double* objf) {
+  const size_t rows = (size_t)L + 1;
+  std::vector<float> al(rows * H), be(rows * H), xr((size_t)D);
+  std::vector<double> r0((size_t)H);
+  bool ok = true;
+  auto stage = [&](int t) {
+    const float* y = x + (size_t)t * D;
+    for (int n = 0; n < D; n++) {
+      if (y[n] != y[n]) ok = false;
+      xr[n] = std::exp(y[n] != y[n] ? -30.f : clamp30(y[n]));
+    }
+  };
+  auto positive = [&](double tot) { if (!(tot > 0.0) || !std::isfinite(tot) || !std::isfinite(1.0 / tot)) ok = false; };
+  double lz = 0.0;
+  {
+    double tot = 0.0;
+    for (int i = 0; i < H; i++) tot += (double)init[i];
+    positive(tot);
+    lz += std::log(tot);
+    for (int i = 0; i < H; i++) al[i] = (float)((double)init[i] / tot + (double)coef * leaky[i]);
+  }
+  for (int t = 0; t < L; t++) {
+    stage(t);
+    const float* a0 = al.data() + (size_t)t * H;
+    double tot = 0.0;
+    for (int j = 0; j < H; j++) {
+      double acc = 0.0;
+      for (int k = bwd.idx[2 * j]; k < bwd.idx[2 * j + 1]; k++) acc += (double)pwb[k] * a0[bwd.trans[3 * k]] * xr[bwd.trans[3 * k + 2]];
+      r0[j] = acc; tot += acc;
+    }
+    positive(tot);
+    lz += std::log(tot);
+    float* o0 = al.data() + (size_t)(t + 1) * H;
+    for (int j = 0; j < H; j++) o0[j] = (float)(r0[j] / tot + (double)coef * leaky[j]);
+  }
+  {
+    double tot = 0.0, w = 0.0, c0 = 0.0;
+    for (int i = 0; i < H; i++) { tot += (double)fin[i]; w += (double)fin[i] * leaky[i]; c0 += (double)al[(size_t)L * H + i] * fin[i]; }
+    positive(tot);
+    if (!(c0 > 0.0)) ok = false;
+    lz += std::log(c0);
+    for (int i = 0; i < H; i++) be[(size_t)L * H + i] = (float)(((double)fin[i] + (double)coef * w) / tot);
+  }
+  for (int t = L - 1; t >= 0; t--) {
+    stage(t);
+    const float* b0 = be.data() + (size_t)(t + 1) * H;
+    double tot = 0.0, s1 = 0.0;
+    for (int i = 0; i < H; i++) {
+      double acc = 0.0;
+      for (int k = fwd.idx[2 * i]; k < fwd.idx[2 * i + 1]; k++) acc += (double)pwf[k] * b0[fwd.trans[3 * k + 1]] * xr[fwd.trans[3 * k + 2]];
+      r0[i] = acc; tot += acc; s1 += acc * leaky[i];
+    }
+    positive(tot);
+    float* o0 = be.data() + (size_t)t * H;
+    for (int i = 0; i < H; i++) o0[i] = (float)((r0[i] + (double)coef * s1) / tot);
+    // the arc posteriors of frame t: alpha'(t), beta'(t+1); x of frame t is staged
+    const float* a0 = al.data() + (size_t)t * H;
+    double den = 0.0;
+    for (int n = 0; n < D; n++)
+      for (int k = pidx[n]; k < pidx[n + 1]; k++) {
+        const int id = parc[k];
+        den += (double)pwf[id] * a0[fwd.trans[3 * id]] * b0[fwd.trans[3 * id + 1]] * xr[n];
+      }
+    if (!(den > 0.0) || !std::isfinite(den) || !std::isfinite(1.0 / den)) ok = false;
+    for (int n = 0; n < D; n++) {
+      double g = 0.0;
+      for (int k = pidx[n]; k < pidx[n + 1]; k++) {
+        const int id = parc[k];
+        const double post = (double)pwf[id] * a0[fwd.trans[3 * id]] * b0[fwd.trans[3 * id + 1]] * xr[n] / den;
+        counts[id] += post;
+        g += post;
+      }
+      if (grad) grad[(size_t)t * D + n] = pidx[n] == pidx[n + 1] ? 0.f : (float)((double)gscale * g);
+    }
+  }
+  if (!std::isfinite(lz)) ok = false;
+  *objf = lz;
+  return ok;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_den_arc_counts(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* leaky, const float* initial, const float* final_, const int32_t* pdf_arcs, const int32_t* pdf_index, int H, int num_arcs,
+    const float* arc_log_weights, const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D,
+    float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
+    float* grad, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count, int num_threads) {
+  const char* who = "cpu_den_arc_counts";
+  const NumGraphs g{ft, fi, fp, bt, bi, bp, initial, final_, 0, H, num_arcs};
+  if (g.any_null() || !leaky || !pdf_arcs || !pdf_index || !nnet_output || !seq_lengths || !objf_per_seq || !counts || !bad_count)
+    return null_pointer(who);
+  int rc = bad_sizes(who, B, T, H, num_arcs, D);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if (!(leaky_hmm_coefficient > 0.f && leaky_hmm_coefficient < 1.f))
+    return fail(PYCHAIN_HIP_EINVAL, "%s: leaky_hmm_coefficient must be in (0,1), got %g", who, (double)leaky_hmm_coefficient);
+  g_cpu_calls++;
+  const int K = num_arcs;
+  bad_count[0] = bad_count[1] = 0;
+  // p exp(w) in both orders: the backward copy of an arc is the r-th arc of its source's run with these endpoints, pdf and
+  // probability, r its rank among the equal arcs of its destination's run (arc_counts.hip: arc_weight_kernel)
+  std::vector<float> pwf((size_t)K), pwb((size_t)K);
+  auto weighted = [&](int id, float p, bool count) {
+    if (!arc_log_weights || id < 0) return p;
+    const float w = arc_log_weights[id];
+    if (!std::isfinite(w)) { if (count) bad_count[1]++; return p; }
+    return p * std::exp(w);
+  };
+  for (int k = 0; k < K; k++) pwf[k] = weighted(k, fp[k], true);
+  for (int k = 0; k < K; k++) {
+    const int src = bt[3 * k], dst = bt[3 * k + 1], pdf = bt[3 * k + 2];
+    int id = -1;
+    if (arc_log_weights && src >= 0 && src < H && dst >= 0 && dst < H) {
+      int rank = 0;
+      for (int j = bi[2 * dst] < 0 ? 0 : bi[2 * dst]; j < k; j++)
+        if (bt[3 * j] == src && bt[3 * j + 2] == pdf && bp[j] == bp[k]) rank++;
+      const int j1 = fi[2 * src + 1] < K ? fi[2 * src + 1] : K;
+      for (int j = fi[2 * src] < 0 ? 0 : fi[2 * src]; j < j1; j++)
+        if (ft[3 * j + 1] == dst && ft[3 * j + 2] == pdf && fp[j] == bp[k] && rank-- == 0) { id = j; break; }
+    }
+    pwb[k] = weighted(id, bp[k], false);
+  }
+  const float gs = grad_scale * (grad_scale_dev ? *grad_scale_dev : 1.f);
+  std::vector<double> per((size_t)B * K, 0.0);
+  std::vector<char> bads((size_t)B, 0);
+  for_each_sequence(B, num_threads, [&](int b) {
+    const int L = clamped_length(seq_lengths[b], T);
+    const size_t f = (size_t)b * T;
+    float* gb = grad ? grad + f * D : nullptr;
+    const float u = seq_weights ? seq_weights[b] : 1.f;
+    const bool ok = arc_counts_one(fwd_of(g), bwd_of(g), pwf.data(), pwb.data(), leaky, initial, final_, pdf_arcs, pdf_index, H,
+                                   nnet_output + f * D, L, D, leaky_hmm_coefficient, gs * u, gb, per.data() + (size_t)b * K, objf_per_seq + b);
+    if (gb) for (size_t i = (size_t)L * D; i < (size_t)T * D; i++) gb[i] = 0.f;
+    if (!ok) {
+      bads[b] = 1;
+      objf_per_seq[b] = std::numeric_limits<double>::quiet_NaN();
+      for (int k = 0; k < K; k++) per[(size_t)b * K + k] = 0.0;
+    }
+  });
+  for (int k = 0; k < K; k++) counts[k] = 0.0;
+  for (int b = 0; b < B; b++) {                    // in ascending b, whatever thread ran the sequence
+    bad_count[0] += bads[b];
+    const float u = seq_weights ? seq_weights[b] : 1.f;
+    if (!bads[b] && u != 0.f)
+      for (int k = 0; k < K; k++) counts[k] += (double)u * per[(size_t)b * K + k];
+  }
+  if (counts_per_seq) memcpy(counts_per_seq, per.data(), per.size() * sizeof(double));
+  return PYCHAIN_HIP_OK;
+}

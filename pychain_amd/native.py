@@ -869,6 +869,75 @@ def cpu_smbr(gt, num_states, x, lengths, gamma, pdfs, probs, leaky_coefficient=1
     return acc, grad, bad, closing, frame_acc
 
 
+def _arc_weight_args(arc_log_weights, utt_weights, K, B, device):
+    """(arc_log_weights float32 [K], utt_weights float32 [B]) as the arc-count entry points read them, on `device`; None stays
+    None.  Both are read one element at a time: a contiguous view off the 16-byte grid goes as it is."""
+    w, u = arc_log_weights, utt_weights
+    if w is not None:
+        if not torch.is_tensor(w) or not w.is_floating_point():
+            raise ValueError("arc_log_weights must be a float tensor [%d], got %s" % (K, getattr(w, "dtype", type(w))))
+        if tuple(w.shape) != (K,):
+            raise ValueError("arc_log_weights must have one entry per arc, [%d], got %s" % (K, list(w.shape)))
+        w = w.detach().to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+    if u is not None:
+        u = torch.as_tensor(u).detach().to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+        if tuple(u.shape) != (B,):
+            raise ValueError("utterance weights must have shape [%d], got %s" % (B, tuple(u.shape)))
+    return w, u
+
+
+def den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_log_weights=None, utt_weights=None, with_grad=True,
+                   grad_scale=1.0, grad_scale_dev=None, per_seq=False):
+    """Expected arc counts of the denominator on the GPU (include/pychain_hip.h: pychain_hip_den_arc_counts), on the current
+    stream.  `gt`: smbr_graph(...); `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernels as it is.  Returns (objf_per_seq
+    float64 [B], counts float64 [K], counts_per_seq float64 [B,K] or None, grad in x's dtype or None, bad_count int32 [2])."""
+    _require_device(x, "nnet_output")
+    if x.dtype not in _DTYPE_CODE:
+        raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
+    x = x.detach().contiguous()
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    L = _lib.lib()
+    dev = x.device
+    H, K = int(num_states), int(gt[0].shape[0])
+    with torch.cuda.device(dev):
+        w, u = _arc_weight_args(arc_log_weights, utt_weights, K, B, dev)
+        ld = _lengths_dev(lengths, dev)
+        objf = torch.empty(B, dtype=torch.float64, device=dev)
+        counts = torch.empty(K, dtype=torch.float64, device=dev)
+        cps = torch.empty(B, K, dtype=torch.float64, device=dev) if per_seq else None
+        grad = torch.empty_like(x) if with_grad else None
+        bad = torch.empty(2, dtype=torch.int32, device=dev)
+        grad_scale_dev = _dev_scalar(grad_scale_dev, dev)
+        ws = _workspace(L.pychain_hip_den_arc_counts_workspace_bytes(B, T, H, K), dev, "arcs")
+        _lib.check(L.pychain_hip_den_arc_counts(
+            *[t.data_ptr() for t in gt], H, K, _ptr(w), x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
+            float(leaky_coefficient), _ptr(u), float(grad_scale), _ptr(grad_scale_dev), _ptr(grad), objf.data_ptr(), counts.data_ptr(),
+            _ptr(cps), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_den_arc_counts")
+    return objf, counts, cps, grad, bad
+
+
+def cpu_den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_log_weights=None, utt_weights=None, with_grad=True,
+                       grad_scale=1.0, per_seq=False):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_den_arc_counts), fp32 rows and gradient."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_den_arc_counts is for CPU tensors; device tensors run on the HIP kernels")
+    xf, lc = _host_inputs(x, lengths)
+    B, T, D = xf.shape
+    H, K = int(num_states), int(gt[0].shape[0])
+    w, u = _arc_weight_args(arc_log_weights, utt_weights, K, B, torch.device("cpu"))
+    objf = torch.empty(B, dtype=torch.float64)
+    counts = torch.empty(K, dtype=torch.float64)
+    cps = torch.empty(B, K, dtype=torch.float64) if per_seq else None
+    grad = torch.empty(B, T, D, dtype=torch.float32) if with_grad else None
+    bad = torch.zeros(2, dtype=torch.int32)
+    _lib.check(_lib.lib().pychain_hip_cpu_den_arc_counts(
+        *[t.data_ptr() for t in gt], H, K, _ptr(w), xf.data_ptr(), lc.data_ptr(), B, T, D, float(leaky_coefficient), _ptr(u),
+        float(grad_scale), None, _ptr(grad), objf.data_ptr(), counts.data_ptr(), _ptr(cps), bad.data_ptr(), int(CPU_THREADS)),
+        "pychain_hip_cpu_den_arc_counts")
+    return objf, counts, cps, grad, bad
+
+
 def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     """Sparse targets out of dense posterior rows on the GPU (include/pychain_hip.h: pychain_hip_topk_rows), on the current
     stream: `rows` [B,T,D] in fp32 / bf16 / fp16 as it is.  Returns (pdfs int32 [B,T,k], probs float32 [B,T,k])."""
