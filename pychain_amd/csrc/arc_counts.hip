@@ -9,7 +9,8 @@
 //   arc_weight_kernel      once per call: pw(k) = p_k exp(w_k) in the forward order and in the backward order (the backward copy of
 //                          an arc finds its forward id by its endpoints, pdf and probability; arcs equal in all four pair up in
 //                          order).  A weight that is not finite counts in bad_count[1] and is taken as 0.
-//   arc_recursion_kernel   smbr_recursion_kernel without its weighted pair: 2B persistent workgroups, one per (sequence, direction),
+//   arc_recursion_kernel   the `recursion` of smbr_device.h without its weighted pair (the body smbr_recursion_kernel runs with it;
+//                          no instruction of the pair is left): 2B persistent workgroups, one per (sequence, direction),
 //                          the state vector and the row x = exp(clamp(y)) double-buffered in LDS, the row made a frame ahead; a
 //                          thread owns states tid, tid + 1024, ...; alpha' and beta', normalised per frame, go to the workspace
 //                          with the totals divided out.
@@ -96,95 +97,18 @@ __global__ __launch_bounds__(kArcNT) void arc_weight_kernel(const ArcArgs a) {
 }
 
 // ---- the recursions ---------------------------------------------------------------------------------------------------------------
-template <int XH, bool FWD>
-__device__ __forceinline__ void arc_recursion(const ArcArgs& a, int b, float* lds) {
-  const int tid = threadIdx.x;
-  const SmbrGraph& g = a.g;
-  const int H = g.H, D = a.D, T = a.T;
-  const int L = seq_len(a.lengths, b, T);
-  float* const vec0 = lds;                       // [2][H] alpha' / beta'
-  float* const xrow = vec0 + 2 * (size_t)H;      // [2][D] x
-  float* const red = xrow + 2 * (size_t)D;
-  const size_t seq_rows = (size_t)b * (T + 1);
-  float* const st0 = (FWD ? a.al : a.be) + seq_rows * H;
-  float* const totv = (FWD ? a.tot_a : a.tot_b) + seq_rows;
-  const int32_t* const idx = FWD ? g.bi : g.fi;                // forwards: the arcs ENTERING a state; backwards: those leaving it
-  const int32_t* const arc = FWD ? g.bt : g.ft;
-  const float* const pr = FWD ? a.pwb : a.pwf;
-  const float coef = a.coef;
-  const size_t xseq = (size_t)b * T * D;
-  bool bad = false, nan = false;
-
-  // the first row: alpha'(0) from the initial, beta'(L) from the final probabilities
-  {
-    const float* start = FWD ? g.init : g.fin;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = tid; i < H; i += kSmNT) { s0 += start[i]; s1 += start[i] * g.leaky[i]; }
-    block_sum3<kSmNT>(s0, s1, s2, red, tid);
-    const float inv = 1.f / s0;
-    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
-    const int r0 = FWD ? 0 : L;
-    if (tid == 0) totv[r0] = s0;
-    for (int i = tid; i < H; i += kSmNT) {
-      const float v = FWD ? start[i] * inv + coef * g.leaky[i] : (start[i] + coef * s1) * inv;
-      vec0[i] = v;
-      st0[(size_t)r0 * H + i] = v;
-    }
-    const int t0 = FWD ? 0 : L - 1;
-    float held[kSmXR];
-    hold_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held);
-    nan = put_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held, xrow) || nan;
-    __syncthreads();
-  }
-  // frame j: forwards alpha'(t+1) from alpha'(t) and x(t), t = j; backwards beta'(t) from beta'(t+1) and x(t), t = L-1-j
-  for (int j = 0; j < L; j++) {
-    const int p = j & 1;
-    const int t = FWD ? j : L - 1 - j, tn = FWD ? t + 1 : t - 1;
-    const bool more = j + 1 < L;
-    const float* v0 = vec0 + (size_t)p * H;
-    float* w0 = vec0 + (size_t)(1 - p) * H;
-    const float* xr = xrow + (size_t)p * D;
-    float* xrn = xrow + (size_t)(1 - p) * D;
-    float held[kSmXR];
-    if (more) hold_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held);          // the next frame's row: in flight over the arc loop
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = tid; i < H; i += kSmNT) {
-      float acc0 = 0.f;
-      const int k1 = idx[2 * i + 1];
-      for (int k = idx[2 * i]; k < k1; k++) {
-        const int other = arc[3 * k + (FWD ? 0 : 1)], n = arc[3 * k + 2];
-        const float wu = pr[k] * v0[other];
-        acc0 += wu * xr[n];
-      }
-      w0[i] = acc0;                                                            // raw, finished below by the thread that wrote it
-      s0 += acc0;
-      if (!FWD) s1 += acc0 * g.leaky[i];
-    }
-    if (more) nan = put_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held, xrn) || nan;
-    block_sum3<kSmNT>(s0, s1, s2, red, tid);                                   // (its barrier: the next row is whole)
-    const float inv = 1.f / s0;
-    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
-    const int r = FWD ? t + 1 : t;
-    if (tid == 0) totv[r] = s0;
-    float* o0 = st0 + (size_t)r * H;
-    for (int i = tid; i < H; i += kSmNT) {
-      const float c0 = FWD ? w0[i] * inv + coef * g.leaky[i] : (w0[i] + coef * s1) * inv;
-      w0[i] = c0;
-      o0[i] = c0;
-    }
-    __syncthreads();
-  }
-  // a NaN in a live row of x (the clamp turns it into exp(-30): watched by the forward workgroup), a total that is not positive and
-  // finite: the sequence is bad.  (Both workgroups of a sequence may store the same 1.)
-  if (__syncthreads_or((bad || (FWD && nan)) ? 1 : 0) && tid == 0) a.seq_bad[b] = 1;
-}
-
+// `recursion` (smbr_device.h) without the weighted pair, over FrameLds, on the weighted probabilities.  LDS: [2][H] alpha' / beta',
+// [2][D] x, the reduction scratch
 template <int XH>
 __global__ __launch_bounds__(kSmNT) void arc_recursion_kernel(const ArcArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* lds = reinterpret_cast<float*>(smem_raw);
-  if (blockIdx.x < (unsigned)a.B) arc_recursion<XH, true>(a, blockIdx.x, lds);
-  else arc_recursion<XH, false>(a, blockIdx.x - a.B, lds);
+  RecArgs r{a.g};
+  r.pf = a.pwf; r.pb = a.pwb; r.x = a.x; r.lengths = a.lengths; r.coef = a.coef;
+  r.al = a.al; r.be = a.be; r.tot_a = a.tot_a; r.tot_b = a.tot_b; r.seq_bad = a.seq_bad; r.T = a.T; r.D = a.D;
+  r.vec0 = lds; r.xrow = r.vec0 + 2 * (size_t)a.g.H; r.red = r.xrow + 2 * (size_t)a.D;
+  if (blockIdx.x < (unsigned)a.B) recursion<XH, true, false, false, FrameLds>(r, SmbrClasses{}, blockIdx.x);
+  else recursion<XH, false, false, false, FrameLds>(r, SmbrClasses{}, blockIdx.x - a.B);
 }
 
 // ---- the counts -------------------------------------------------------------------------------------------------------------------
@@ -295,26 +219,9 @@ __global__ __launch_bounds__(kArcNT) void arc_reduce_kernel(const ArcArgs a) {
   a.counts[k] = total;
 }
 
-size_t arc_recursion_lds(int H, int D) { return (2 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
-size_t arc_count_lds(int H, int D) { return (2 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
-size_t arc_lds_bytes(int H, int D) {
-  const size_t r = arc_recursion_lds(H, D) + kSmStaticLds, c = arc_count_lds(H, D);
-  return r > c ? r : c;
-}
-
-template <int XH>
-hipError_t launch_as(const ArcArgs& a, hipStream_t st) {
-  const size_t lds_r = arc_recursion_lds(a.g.H, a.D), lds_c = arc_count_lds(a.g.H, a.D);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(arc_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(arc_count_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_c);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((arc_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((arc_count_kernel<XH>), dim3(a.nblk, a.B), dim3(kSmGNT), lds_c, st, a);
-  return hipGetLastError();
-}
+// both kernels: two state vectors, two rows, the reduction scratch
+size_t arc_kernel_lds(int H, int D) { return (2 * (size_t)H + 2 * (size_t)D + kSmRed) * sizeof(float); }
+size_t arc_lds_bytes(int H, int D) { return arc_kernel_lds(H, D) + kSmStaticLds; }       // (the recursion's static LDS)
 
 hipError_t launch_arc_counts(const ArcArgs& a, hipStream_t st) {
   hipError_t e = hipMemsetAsync(a.seq_bad, 0, 3 * (size_t)a.B * sizeof(int32_t), st);
@@ -325,7 +232,13 @@ hipError_t launch_arc_counts(const ArcArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(arc_weight_kernel, dim3(kgrid), dim3(kArcNT), 0, st, a);
   e = hipGetLastError();
   if (e != hipSuccess) return e;
-  e = a.x_half == kXF32 ? launch_as<kXF32>(a, st) : a.x_half == kXBf16 ? launch_as<kXBf16>(a, st) : launch_as<kXF16>(a, st);
+  e = by_row_dtype(a.x_half, [&](auto xh) {
+    constexpr int XH = decltype(xh)::value;
+    const size_t lds = arc_kernel_lds(a.g.H, a.D);
+    const hipError_t er = launch_with_lds(arc_recursion_kernel<XH>, dim3(2 * a.B), dim3(kSmNT), lds, st, a);
+    if (er != hipSuccess) return er;
+    return launch_with_lds(arc_count_kernel<XH>, dim3(a.nblk, a.B), dim3(kSmGNT), lds, st, a);
+  });
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(arc_objf_kernel, dim3(a.B), dim3(kArcNT), 0, st, a);
   e = hipGetLastError();

@@ -66,9 +66,8 @@ size_t smbr_recursion_lds(int H, int D, int C);     // ... the class form: one t
 size_t smbr_grad_lds(int H, int D, int C);
 size_t smbr_lds_bytes(int H, int D, int C);         // the larger of the two, static LDS included; C = 0: the pdf-level form
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st);
-hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st);     // the recursion launch, then the gradient launch
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hipStream_t st);   // the dense pass, then the per-sequence sums
-hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st);
+hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st);     // the recursion launch, then the gradient launch; c.cls null: the pdf-level kernels
 
 // The general kernels (smbr_general.hip): any H, D, C.  What the LDS kernels keep in LDS beside the state vectors
 // - the frame's row x, its companion x A, the class table; the two D-rows of the gradient - lies in scratch rows of the workspace,

@@ -25,7 +25,7 @@
 // kernels above can take, so each has a counterpart; the pdf-level kernels keep their code.
 //   smbr_class_frame_acc_kernel   a dense pass over gamma: a wave per frame on a grid over (frames, B), the frame's entries merged
 //                                 into distinct classes first, fp64 sums in a fixed order; smbr_class_seq_acc_kernel sums E_b
-//   smbr_class_recursion_kernel   smbr_recursion with CLS: one table Acls(t, .) in LDS, written for the next frame before the arc
+//   smbr_class_recursion_kernel   the recursion with CLS: one table Acls(t, .) in LDS, written for the next frame before the arc
 //                                 loop; the dense companion row x A is made behind the reduction's barrier, where the pdf-level
 //                                 form scatters its K entries.  No barrier more, the arc loop unchanged.
 //   smbr_class_grad_kernel        the frame's table made beside the state rows; every carried pdf takes its class's credit; the
@@ -35,8 +35,10 @@
 //
 // These kernels keep a frame in LDS and the two entry points that launch only them refuse what does not fit.  The general kernels
 // (smbr_general.hip) take any graph and tree with the same bits; they share this unit's argument checks, workspace
-// layout and entry-point code (pychain_hip_smbr_forward_backward_general, pychain_hip_smbr_form, below) and the device helpers of
-// smbr_device.h.
+// layout and entry-point code (pychain_hip_smbr_forward_backward_general, pychain_hip_smbr_form, below).
+// The bodies of the four stage-2 kernels are not here: `recursion`, `smbr_grad_frame` and `smbr_close` of smbr_device.h are shared
+// with the general kernels and with the expected arc counts (arc_counts.hip); the kernels below lay out their LDS and instantiate
+// them over FrameLds.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -54,8 +56,7 @@
 namespace pychain_hip {
 namespace {
 
-// (the workgroup shapes, block_sum3, owned_entry, scatter_entries, entry_class, class_table, hold_row, put_row and smbr_condemn:
-// smbr_device.h, shared with the general kernels of smbr_general.hip)
+// (the workgroup shapes, the helpers and the bodies of stage 2: smbr_device.h)
 constexpr int kSmAccNT = 256;
 
 // ---- stage 1: frame accuracies ------------------------------------------------------------------------------------------------
@@ -178,370 +179,63 @@ __global__ __launch_bounds__(kSmAccNT) void smbr_class_seq_acc_kernel(const Smbr
 }
 
 // ---- stage 2: the recursions ----------------------------------------------------------------------------------------------------
-// (hold_row / put_row - row t of the sequence into LDS as exp(clamp(.)) -: smbr_device.h)
-// x A of the elements put_row stored, by class: xacc[n] = xrow[n] * acl[cls[n]] - the thread reads back what it wrote itself;
-// `hc`: cls of the elements held in registers, those beyond are loaded again
-__device__ __forceinline__ void class_row(const int32_t* cls, const int (&hc)[kSmXR], int D, int tid, const float* acl, const float* xrow, float* xacc) {
-#pragma unroll
-  for (int i = 0; i < kSmXR; i++) {
-    const int n = tid + i * kSmNT;
-    if (n < D) xacc[n] = xrow[n] * acl[hc[i]];
-  }
-  for (int n = tid + kSmXR * kSmNT; n < D; n += kSmNT) xacc[n] = xrow[n] * acl[cls[n]];
-}
-
-// CLS: the accuracy by class (§3.27) - `c` is read, the table acl [C] lies behind the reduction scratch, and the companion row is
-// dense: made from the next row and the next frame's table in the slot where the pdf-level form scatters its K entries.
-template <int XH, bool FWD, bool CLS>
-__device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, const SmbrClasses& c, int b, float* lds) {
-  const int tid = threadIdx.x;
-  const SmbrGraph& g = a.g;
-  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
-  const int L = seq_len(a.lengths, b, T);
-  float* const vec0 = lds;                       // [2][H] alpha' / beta'
-  float* const vec1 = lds + 2 * (size_t)H;       // [2][H] alpha-bar' / beta-bar'
-  float* const xrow = vec1 + 2 * (size_t)H;      // [2][D] x
-  float* const xacc = xrow + 2 * (size_t)D;      // [2][D] x * A
-  float* const red = xacc + 2 * (size_t)D;
-  float* const acl = red + kSmRed;               // [C] Acls of the frame whose companion row is made next (CLS)
-  int hc[kSmXR];
-  if constexpr (CLS) {
-#pragma unroll
-    for (int i = 0; i < kSmXR; i++) hc[i] = tid + i * kSmNT < D ? c.cls[tid + i * kSmNT] : 0;
-  }
-  const size_t seq_rows = (size_t)b * (T + 1);
-  float* const st0 = (FWD ? a.al : a.be) + seq_rows * H;
-  float* const st1 = (FWD ? a.ab : a.bb) + seq_rows * H;
-  float* const totv = (FWD ? a.tot_a : a.tot_b) + seq_rows;
-  const int32_t* const idx = FWD ? g.bi : g.fi;                // forwards: the arcs ENTERING a state; backwards: those leaving it
-  const int32_t* const arc = FWD ? g.bt : g.ft;
-  const float* const pr = FWD ? g.bp : g.fp;
-  const float coef = a.coef;
-  const size_t xseq = (size_t)b * T * D, fseq = (size_t)b * T;
-  bool bad = false, nan = false;
-
-  // the first row: alpha'(0) from the initial, beta'(L) from the final probabilities; the weighted vector starts at zero
-  {
-    const float* start = FWD ? g.init : g.fin;
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = tid; i < H; i += kSmNT) { s0 += start[i]; s1 += start[i] * g.leaky[i]; }
-    block_sum3<kSmNT>(s0, s1, s2, red, tid);
-    const float inv = 1.f / s0;
-    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
-    const int r0 = FWD ? 0 : L;
-    if (tid == 0) totv[r0] = s0;
-    for (int i = tid; i < H; i += kSmNT) {
-      const float v = FWD ? start[i] * inv + coef * g.leaky[i] : (start[i] + coef * s1) * inv;
-      vec0[i] = v; vec1[i] = 0.f;
-      st0[(size_t)r0 * H + i] = v; st1[(size_t)r0 * H + i] = 0.f;
-    }
-    const int t0 = FWD ? 0 : L - 1;
-    float held[kSmXR];
-    hold_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held);
-    nan = put_row<XH>(a.x, xseq + (size_t)t0 * D, D, tid, held, xrow) || nan;
-    if constexpr (CLS) {
-      class_table(c, a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, acl);
-      __syncthreads();
-      class_row(c.cls, hc, D, tid, acl, xrow, xacc);
-    } else {
-      for (int n = tid; n < D; n += kSmNT) xacc[n] = 0.f;
-      __syncthreads();
-      scatter_entries(a.pdfs + (fseq + t0) * Kt, a.probs + (fseq + t0) * Kt, Kt, D, tid, kSmNT, xrow, xacc);
-    }
-    __syncthreads();
-  }
-  // frame j: forwards alpha'(t+1) from alpha'(t) and x(t), t = j; backwards beta'(t) from beta'(t+1) and x(t), t = L-1-j
-  for (int j = 0; j < L; j++) {
-    const int p = j & 1;
-    const int t = FWD ? j : L - 1 - j, tn = FWD ? t + 1 : t - 1;
-    const bool more = j + 1 < L;
-    const float* v0 = vec0 + (size_t)p * H;
-    const float* v1 = vec1 + (size_t)p * H;
-    float* w0 = vec0 + (size_t)(1 - p) * H;
-    float* w1 = vec1 + (size_t)(1 - p) * H;
-    const float* xr = xrow + (size_t)p * D;
-    const float* xa = xacc + (size_t)p * D;
-    float* xrn = xrow + (size_t)(1 - p) * D;
-    float* xan = xacc + (size_t)(1 - p) * D;
-    float held[kSmXR];
-    if (more) hold_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held);          // the next frame's row: in flight over the arc loop
-    if constexpr (CLS) {                                                       // (the table's readers are behind the last barrier)
-      if (more) class_table(c, a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, acl);
-    } else {
-      for (int n = tid; n < D; n += kSmNT) xan[n] = 0.f;
-    }
-    const float e_t = a.frame_acc[fseq + t];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-    for (int i = tid; i < H; i += kSmNT) {
-      float acc0 = 0.f, acc1 = 0.f;
-      const int k1 = idx[2 * i + 1];
-      for (int k = idx[2 * i]; k < k1; k++) {
-        const int other = arc[3 * k + (FWD ? 0 : 1)], n = arc[3 * k + 2];
-        const float w = pr[k], u0 = v0[other], u1 = v1[other], xx = xr[n], xq = xa[n];
-        const float wu = w * u0;
-        acc0 += wu * xx;
-        acc1 += (w * u1) * xx + wu * xq;
-      }
-      acc1 -= e_t * acc0;                                                      // the centring: a(t,n) = A(t,n) - e(t)
-      w0[i] = acc0; w1[i] = acc1;                                              // raw, finished below by the thread that wrote them
-      s0 += acc0;
-      if (FWD) s1 += acc1;
-      else { s1 += acc0 * g.leaky[i]; s2 += acc1 * g.leaky[i]; }
-    }
-    if (more) nan = put_row<XH>(a.x, xseq + (size_t)tn * D, D, tid, held, xrn) || nan;
-    block_sum3<kSmNT>(s0, s1, s2, red, tid);                                   // (its barrier: the next rows are whole)
-    if constexpr (CLS) {
-      if (more) class_row(c.cls, hc, D, tid, acl, xrn, xan);
-    } else {
-      if (more) scatter_entries(a.pdfs + (fseq + tn) * Kt, a.probs + (fseq + tn) * Kt, Kt, D, tid, kSmNT, xrn, xan);
-    }
-    const float inv = 1.f / s0;
-    if (!(s0 > 0.f) || !(inv > 0.f) || !(inv - inv == 0.f)) bad = true;
-    const int r = FWD ? t + 1 : t;
-    if (tid == 0) totv[r] = s0;
-    float* o0 = st0 + (size_t)r * H;
-    float* o1 = st1 + (size_t)r * H;
-    for (int i = tid; i < H; i += kSmNT) {
-      float c0, c1;
-      if (FWD) {
-        const float lk = coef * g.leaky[i];
-        c0 = w0[i] * inv + lk;                                                 // (the normalised alpha sums to one)
-        c1 = (w1[i] + lk * s1) * inv;
-      } else {
-        c0 = (w0[i] + coef * s1) * inv;
-        c1 = (w1[i] + coef * s2) * inv;
-      }
-      w0[i] = c0; w1[i] = c1;
-      o0[i] = c0; o1[i] = c1;
-    }
-    __syncthreads();
-  }
-  // a NaN in a live row of x (the clamp turns it into exp(-30): watched here, by the forward workgroup), a total that is not
-  // positive and finite: the sequence is bad.  (Both workgroups of a sequence may store the same 1.)
-  if (__syncthreads_or((bad || (FWD && nan)) ? 1 : 0) && tid == 0) a.seq_bad[b] = 1;
-}
-
-template <int XH>
-__global__ __launch_bounds__(kSmNT) void smbr_recursion_kernel(const SmbrArgs a) {
+// the body: smbr_device.h, `recursion` with the weighted pair over FrameLds.  LDS: [2][H] alpha' / beta', [2][H] alpha-bar' /
+// beta-bar', [2][D] x, [2][D] x A, the reduction scratch and, by class, the table [C]
+template <int XH, bool CLS>
+__device__ __forceinline__ void smbr_recursion(const SmbrArgs& a, const SmbrClasses& c) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* lds = reinterpret_cast<float*>(smem_raw);
-  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true, false>(a, SmbrClasses{}, blockIdx.x, lds);
-  else smbr_recursion<XH, false, false>(a, SmbrClasses{}, blockIdx.x - a.B, lds);
+  const size_t H = a.g.H, D = a.D;
+  RecArgs r = smbr_rec_args(a);
+  r.vec0 = lds; r.vec1 = r.vec0 + 2 * H; r.xrow = r.vec1 + 2 * H; r.xacc = r.xrow + 2 * D; r.red = r.xacc + 2 * D; r.acl = r.red + kSmRed;
+  if (blockIdx.x < (unsigned)a.B) recursion<XH, true, CLS, true, FrameLds>(r, c, blockIdx.x);
+  else recursion<XH, false, CLS, true, FrameLds>(r, c, blockIdx.x - a.B);
+}
+template <int XH>
+__global__ __launch_bounds__(kSmNT) void smbr_recursion_kernel(const SmbrArgs a) {
+  smbr_recursion<XH, false>(a, SmbrClasses{});
 }
 template <int XH>
 __global__ __launch_bounds__(kSmNT) void smbr_class_recursion_kernel(const SmbrArgs a, const SmbrClasses c) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* lds = reinterpret_cast<float*>(smem_raw);
-  if (blockIdx.x < (unsigned)a.B) smbr_recursion<XH, true, true>(a, c, blockIdx.x, lds);
-  else smbr_recursion<XH, false, true>(a, c, blockIdx.x - a.B, lds);
+  smbr_recursion<XH, true>(a, c);
 }
 
 // ---- stage 2: the gradient ------------------------------------------------------------------------------------------------------
-// (smbr_condemn - a sequence that went bad is counted once, its E_b NaN -: smbr_device.h)
+// the frame: smbr_device.h, smbr_grad_frame over FrameLds.  LDS: the four state rows [4][H], [D] x q0, [D] x (q1 + a q0), the
+// reduction scratch and, by class, the frame's table [C].  The sequence's first workgroup closes it.
+template <int XH, bool CLS>
+__device__ __forceinline__ void smbr_grad(const SmbrArgs& a, const SmbrClasses& c) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+  float* lds = reinterpret_cast<float*>(smem_raw);
+  const int b = blockIdx.y, H = a.g.H, D = a.D;
+  const int L = seq_len(a.lengths, b, a.T);
+  float* const gq = lds + 4 * (size_t)H;
+  float* const gv = gq + D;
+  float* const red = gv + D;
+  const float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
+  const int t_begin = blockIdx.x * kSmFrames, t_end = min(t_begin + kSmFrames, a.T);
+  for (int t = t_begin; t < t_end; t++) smbr_grad_frame<XH, CLS, FrameLds>(a, c, b, t, L, gscale, lds, gq, gv, red + kSmRed, red);
+  if (blockIdx.x == 0) smbr_close(a, b, L, red);
+}
 template <int XH>
 __global__ __launch_bounds__(kSmGNT) void smbr_grad_kernel(const SmbrArgs a) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* lds = reinterpret_cast<float*>(smem_raw);
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const SmbrGraph& g = a.g;
-  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
-  const int L = seq_len(a.lengths, b, T);
-  float* const sa = lds;                          // alpha'(t)
-  float* const sab = sa + H;                      // alpha-bar'(t)
-  float* const sb = sab + H;                      // beta'(t+1)
-  float* const sbb = sb + H;                      // beta-bar'(t+1)
-  float* const gq = sbb + H;                      // [D] x q0
-  float* const gv = gq + D;                       // [D] x (q1 - e q0), then + A x q0 where the frame has an entry
-  float* const red = gv + D;
-  const size_t seq_rows = (size_t)b * (T + 1);
-  const float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
-  const int t_begin = blockIdx.x * kSmFrames, t_end = min(t_begin + kSmFrames, T);
-  for (int t = t_begin; t < t_end; t++) {
-    const size_t row = ((size_t)b * T + t) * D;
-    if (t >= L) {                                                              // padding: exact zeros
-      for (int n = tid; n < D; n += kSmGNT) row_store1<XH>(a.grad, row + n, 0.f);
-      continue;
-    }
-    const size_t r0 = (seq_rows + t) * H, r1 = r0 + H;
-    for (int i = tid; i < H; i += kSmGNT) { sa[i] = a.al[r0 + i]; sab[i] = a.ab[r0 + i]; sb[i] = a.be[r1 + i]; sbb[i] = a.bb[r1 + i]; }
-    __syncthreads();
-    const float e_t = a.frame_acc[(size_t)b * T + t];
-    float part = 0.f, none1 = 0.f, none2 = 0.f;
-    for (int n = tid; n < D; n += kSmGNT) {
-      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
-      float q0 = 0.f, q1 = 0.f;
-      for (int k = k0; k < k1; k++) {
-        const int id = g.parc[k];
-        const int src = g.ft[3 * id], dst = g.ft[3 * id + 1];
-        const float w = g.fp[id];
-        const float wa = w * sa[src];
-        q0 += wa * sb[dst];
-        q1 += (w * sab[src]) * sb[dst] + wa * sbb[dst];
-      }
-      float v0 = 0.f, v1 = 0.f;
-      if (k0 != k1) {                                                          // a pdf no arc carries: its x is not read
-        const float xx = clamp_exp(row_load1<XH>(a.x, row + n), kXExpClamp);
-        v0 = xx * q0;
-        v1 = xx * (q1 - e_t * q0);
-      }
-      gq[n] = v0; gv[n] = v1;
-      part += v0;
-    }
-    block_sum3<kSmGNT>(part, none1, none2, red, tid);
-    {
-      const int32_t* pd = a.pdfs + ((size_t)b * T + t) * Kt;
-      const float* pr = a.probs + ((size_t)b * T + t) * Kt;
-      int d;
-      float q;
-      for (int k = tid; k < Kt; k += kSmGNT)
-        if (owned_entry(pd, pr, k, Kt, D, d, q)) gv[d] += q * gq[d];
-    }
-    __syncthreads();
-    // The row's mean: a second sum, over the FINISHED elements.  (Summing x (q1 - e q0) in the first block sum and the owners'
-    // A x q0 beside it gives the same mean in exact arithmetic, but at a pdf with gamma near one the two halves are each as large
-    // as the divisor and cancel: the mean must carry the rounding its elements carry, or it spreads 1e-7 of gamma over the row.)
-    // Its scratch is red[48 ..], which block_sum3 leaves alone - slower waves may still read red[0 .. 47].
-    float mean = 0.f;
-    for (int n = tid; n < D; n += kSmGNT) mean += gv[n];
-    mean = wave_sum(mean);
-    if ((tid & 63) == 0) red[48 + (tid >> 6)] = mean;
-    __syncthreads();
-    mean = 0.f;
-    for (int w = 0; w < kSmGNT / 64; w++) mean += red[48 + w];                   // (same order in every thread)
-    const float sc = gscale / part, inv = 1.f / part;
-    if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) smbr_condemn(a, b);    // (the host twin's check of the same divisor)
-    // The row is centred by its own mean, as smbr_class_grad_kernel's: sum_n x (q1 + a q0) is zero but for the rounding of e(t),
-    // and that residue enters alpha-bar and beta-bar at every frame and stays - uncentred, the row carries gamma(t,n) times the
-    // residue accumulated over the sequence (`closing` is that sum; DESIGN.md §3.26, "The residue").
-    const float eps = mean * inv;
-    for (int n = tid; n < D; n += kSmGNT) {
-      const bool carried = g.pidx[n] != g.pidx[n + 1];
-      row_store1<XH>(a.grad, row + n, carried ? (gv[n] - eps * gq[n]) * sc : 0.f);
-    }
-    __syncthreads();                                                           // (the rows are free for the next frame)
-  }
-  // the sequence's first workgroup closes it: the diagnostic sum_j alpha-bar'(L,j) final(j) / sum_j alpha'(L,j) final(j), and the
-  // sequence's verdict
-  if (blockIdx.x == 0) {
-    const size_t rL = (seq_rows + L) * H;
-    float c0 = 0.f, c1 = 0.f, none = 0.f;
-    for (int i = tid; i < H; i += kSmGNT) { c0 += a.al[rL + i] * g.fin[i]; c1 += a.ab[rL + i] * g.fin[i]; }
-    block_sum3<kSmGNT>(c0, c1, none, red, tid);
-    if (tid == 0) {
-      const bool bad = a.seq_bad[b] != 0 || !(c0 > 0.f);                       // what the recursions found
-      a.closing[b] = bad ? __builtin_nanf("") : c1 / c0;
-      if (bad) smbr_condemn(a, b);
-    }
-  }
+  smbr_grad<XH, false>(a, SmbrClasses{});
 }
-
-// The same by class (§3.27): smbr_grad_kernel with the frame's table acl [C] made beside the state rows, and every carried pdf
-// taking its class's credit in the pass that forms it, where the pdf-level form adds the K owned entries behind the reduction.
 template <int XH>
 __global__ __launch_bounds__(kSmGNT) void smbr_class_grad_kernel(const SmbrArgs a, const SmbrClasses c) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-  float* lds = reinterpret_cast<float*>(smem_raw);
-  const int tid = threadIdx.x, b = blockIdx.y;
-  const SmbrGraph& g = a.g;
-  const int H = g.H, D = a.D, T = a.T, Kt = a.Kt;
-  const int L = seq_len(a.lengths, b, T);
-  float* const sa = lds;                          // alpha'(t)
-  float* const sab = sa + H;                      // alpha-bar'(t)
-  float* const sb = sab + H;                      // beta'(t+1)
-  float* const sbb = sb + H;                      // beta-bar'(t+1)
-  float* const gq = sbb + H;                      // [D] x q0
-  float* const gv = gq + D;                       // [D] x (q1 + a q0)
-  float* const red = gv + D;
-  float* const acl = red + kSmRed;                // [C] Acls of the frame
-  const size_t seq_rows = (size_t)b * (T + 1);
-  const float gscale = a.grad_scale_dev ? a.grad_scale * *a.grad_scale_dev : a.grad_scale;
-  const int t_begin = blockIdx.x * kSmFrames, t_end = min(t_begin + kSmFrames, T);
-  for (int t = t_begin; t < t_end; t++) {
-    const size_t row = ((size_t)b * T + t) * D;
-    if (t >= L) {                                                              // padding: exact zeros
-      for (int n = tid; n < D; n += kSmGNT) row_store1<XH>(a.grad, row + n, 0.f);
-      continue;
-    }
-    const size_t r0 = (seq_rows + t) * H, r1 = r0 + H;
-    for (int i = tid; i < H; i += kSmGNT) { sa[i] = a.al[r0 + i]; sab[i] = a.ab[r0 + i]; sb[i] = a.be[r1 + i]; sbb[i] = a.bb[r1 + i]; }
-    class_table(c, a.pdfs + ((size_t)b * T + t) * Kt, a.probs + ((size_t)b * T + t) * Kt, Kt, D, tid, kSmGNT, acl);
-    __syncthreads();
-    const float e_t = a.frame_acc[(size_t)b * T + t];
-    float part = 0.f, none1 = 0.f, none2 = 0.f;
-    for (int n = tid; n < D; n += kSmGNT) {
-      const int k0 = g.pidx[n], k1 = g.pidx[n + 1];
-      float q0 = 0.f, q1 = 0.f;
-      for (int k = k0; k < k1; k++) {
-        const int id = g.parc[k];
-        const int src = g.ft[3 * id], dst = g.ft[3 * id + 1];
-        const float w = g.fp[id];
-        const float wa = w * sa[src];
-        q0 += wa * sb[dst];
-        q1 += (w * sab[src]) * sb[dst] + wa * sbb[dst];
-      }
-      float v0 = 0.f, v1 = 0.f;
-      if (k0 != k1) {                                                          // a pdf no arc carries: its x is not read
-        const float xx = clamp_exp(row_load1<XH>(a.x, row + n), kXExpClamp);
-        v0 = xx * q0;
-        v1 = xx * (q1 - e_t * q0);
-        v1 += acl[c.cls[n]] * v0;                                             // (+ A x q0: the thread's own element)
-      }
-      gq[n] = v0; gv[n] = v1;
-      part += v0;
-      none1 += v1;
-    }
-    block_sum3<kSmGNT>(part, none1, none2, red, tid);                          // (below a thread reads its own elements only)
-    const float sc = gscale / part, inv = 1.f / part;
-    if ((!(part > 0.f) || !(inv - inv == 0.f)) && tid == 0) smbr_condemn(a, b);    // (the host twin's check of the same divisor)
-    // The row is centred by its own mean: sum_n x (q1 + a q0) is zero but for the rounding of e(t) - the occupancies are another
-    // kernel's, in fp32 -, and with a dense A of order one that residue, times gamma(t,n), is what the row would carry.
-    const float eps = none1 * inv;
-    for (int n = tid; n < D; n += kSmGNT) {
-      const bool carried = g.pidx[n] != g.pidx[n + 1];
-      row_store1<XH>(a.grad, row + n, carried ? (gv[n] - eps * gq[n]) * sc : 0.f);
-    }
-    __syncthreads();                                                           // (the rows are free for the next frame)
-  }
-  // the sequence's first workgroup closes it: the diagnostic sum_j alpha-bar'(L,j) final(j) / sum_j alpha'(L,j) final(j), and the
-  // sequence's verdict
-  if (blockIdx.x == 0) {
-    const size_t rL = (seq_rows + L) * H;
-    float c0 = 0.f, c1 = 0.f, none = 0.f;
-    for (int i = tid; i < H; i += kSmGNT) { c0 += a.al[rL + i] * g.fin[i]; c1 += a.ab[rL + i] * g.fin[i]; }
-    block_sum3<kSmGNT>(c0, c1, none, red, tid);
-    if (tid == 0) {
-      const bool bad = a.seq_bad[b] != 0 || !(c0 > 0.f);                       // what the recursions found
-      a.closing[b] = bad ? __builtin_nanf("") : c1 / c0;
-      if (bad) smbr_condemn(a, b);
-    }
-  }
-}
-template <int XH>
-hipError_t launch_classes_as(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st) {
-  const size_t lds_r = smbr_recursion_lds(a.g.H, a.D, c.C), lds_g = smbr_grad_lds(a.g.H, a.D, c.C);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_class_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_class_grad_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smbr_class_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a, c);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smbr_class_grad_kernel<XH>), dim3((a.T + kSmFrames - 1) / kSmFrames, a.B), dim3(kSmGNT), lds_g, st, a, c);
-  return hipGetLastError();
+  smbr_grad<XH, true>(a, c);
 }
 
+// the recursion launch, then the gradient launch; c.cls null: the pdf-level kernels
 template <int XH>
-hipError_t launch_as(const SmbrArgs& a, hipStream_t st) {
-  const size_t lds_r = smbr_recursion_lds(a.g.H, a.D), lds_g = smbr_grad_lds(a.g.H, a.D);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_recursion_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_r);
+hipError_t launch_as(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st) {
+  const size_t lds_r = smbr_recursion_lds(a.g.H, a.D, c.C), lds_g = smbr_grad_lds(a.g.H, a.D, c.C);
+  const dim3 grid_r(2 * a.B), grid_g((a.T + kSmFrames - 1) / kSmFrames, a.B);
+  hipError_t e = c.cls ? launch_with_lds(smbr_class_recursion_kernel<XH>, grid_r, dim3(kSmNT), lds_r, st, a, c)
+                       : launch_with_lds(smbr_recursion_kernel<XH>, grid_r, dim3(kSmNT), lds_r, st, a);
   if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(smbr_grad_kernel<XH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_g);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smbr_recursion_kernel<XH>), dim3(2 * a.B), dim3(kSmNT), lds_r, st, a);
-  e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL((smbr_grad_kernel<XH>), dim3((a.T + kSmFrames - 1) / kSmFrames, a.B), dim3(kSmGNT), lds_g, st, a);
-  return hipGetLastError();
+  return c.cls ? launch_with_lds(smbr_class_grad_kernel<XH>, grid_g, dim3(kSmGNT), lds_g, st, a, c)
+               : launch_with_lds(smbr_grad_kernel<XH>, grid_g, dim3(kSmGNT), lds_g, st, a);
 }
 
 }  // namespace
@@ -562,14 +256,6 @@ hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, hipStream_t st) {
   return hipGetLastError();
 }
 
-hipError_t launch_smbr(const SmbrArgs& a, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(a.seq_bad, 0, 2 * (size_t)a.B * sizeof(int32_t), st);
-  if (e != hipSuccess) return e;
-  if (a.x_half == kXF32) return launch_as<kXF32>(a, st);
-  if (a.x_half == kXBf16) return launch_as<kXBf16>(a, st);
-  return launch_as<kXF16>(a, st);
-}
-
 hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hipStream_t st) {
   hipError_t e = hipMemsetAsync(a.bad_count, 0, 2 * sizeof(int32_t), st);
   if (e != hipSuccess) return e;
@@ -585,11 +271,9 @@ hipError_t launch_smbr_frame_acc(const SmbrAccArgs& a, const SmbrClasses& c, hip
 }
 
 hipError_t launch_smbr(const SmbrArgs& a, const SmbrClasses& c, hipStream_t st) {
-  hipError_t e = hipMemsetAsync(a.seq_bad, 0, 2 * (size_t)a.B * sizeof(int32_t), st);
+  const hipError_t e = hipMemsetAsync(a.seq_bad, 0, 2 * (size_t)a.B * sizeof(int32_t), st);
   if (e != hipSuccess) return e;
-  if (a.x_half == kXF32) return launch_classes_as<kXF32>(a, c, st);
-  if (a.x_half == kXBf16) return launch_classes_as<kXBf16>(a, c, st);
-  return launch_classes_as<kXF16>(a, c, st);
+  return by_row_dtype(a.x_half, [&](auto xh) { return launch_as<decltype(xh)::value>(a, c, st); });
 }
 
 }  // namespace pychain_hip
@@ -791,7 +475,7 @@ int smbr_forward_backward(
   const SmbrClasses cl{pdf_classes, C, targets_are_classes != 0, nullptr};
   hipError_t err;
   if (run == PYCHAIN_HIP_SMBR_LDS) {
-    err = pdf_classes ? launch_smbr(a, cl, (hipStream_t)stream) : launch_smbr(a, (hipStream_t)stream);
+    err = launch_smbr(a, cl, (hipStream_t)stream);
   } else {
     gc.s.rec = (float*)(base + gc.rec); gc.s.grad = (float*)(base + gc.grad);
     gc.s.state_lds = run == PYCHAIN_HIP_SMBR_ROWS;

@@ -19,11 +19,13 @@ FAULTS = ("beta_unleaked", "neighbour_divisor", "no_w_in_recursion")
 
 # name -> how it is made: the three shapes of smbr_reference.case; a graph of more than 2048 states (a recursion thread owns
 # three) on two short sequences; one sequence of 1500 frames beside 400, 100 and 48 (24 count workgroups of 64 frames, the last
-# one short; the sum over time)
-CASES = ("small", "wide", "degenerate", "states2100", "long")
+# one short; the sum over time); the graph of tests/test_gpu_smbr_general.py's `long_row` on rows of 4200 pdfs, more than the 4096
+# elements the recursion threads hold in registers (four arcs carry pdfs beyond)
+CASES = ("small", "wide", "degenerate", "states2100", "long", "long_row")
 _OWN = {
     "states2100": dict(H=2100, K=9000, D=130, B=2, T=9, lengths=[9, 5], scale=2.0),
     "long": dict(H=300, K=1500, D=130, B=4, T=1500, lengths=[1500, 400, 100, 48], scale=2.0),
+    "long_row": dict(H=37, K=150, D=4200, B=2, T=3, lengths=[3, 1], scale=2.0, graph_seed=3),
 }
 _made, _refs = {}, {}
 
@@ -34,7 +36,7 @@ def case(name):
         if name in _OWN:
             from pychain_amd import synthetic as syn
             c = _OWN[name]
-            _made[name] = (syn.make_den_graph(c["H"], c["K"], c["D"], seed=7), syn.make_input(c["B"], c["T"], c["D"], seed=9, scale=c["scale"]),
+            _made[name] = (syn.make_den_graph(c["H"], c["K"], c["D"], seed=c.get("graph_seed", 7)), syn.make_input(c["B"], c["T"], c["D"], seed=9, scale=c["scale"]),
                            torch.tensor(c["lengths"]))
         else:
             g, y, lengths, _, _ = sref.case(name)

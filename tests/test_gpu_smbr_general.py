@@ -4,7 +4,9 @@
 SAME BITS where the LDS kernels run too: the cases of tests/smbr_reference at leaky coefficients 0.1 and 1e-5 - `wide` has more
 states than a recursion workgroup has threads, `degenerate` a pdf no arc carries -, pdf-level and under the maps `phones` and
 `identity` of tests/smbr_class_reference on that file's own targets, fp32, bf16 and fp16 rows: kernels="rows" and "global" each
-give torch.equal to "lds" on the gradient, per_seq, closing and bad_count.
+give torch.equal to "lds" on the gradient, per_seq, closing and bad_count.  `long_row` (37 states, 4200 pdfs: within the LDS, beyond
+the 4096 elements of a row the recursion threads hold in registers) does the same pdf-level and under `phones`, fp32 and bf16, and
+holds "lds" to the fp64 recursions.
 
 AGAINST FP64 beyond the LDS of a CU, under kernels="auto" with the form asserted through pychain_hip_smbr_form: the shape
 tests/test_gpu_smbr.py shows refused by default (37 states, 10180 pdfs), C4's graph (3000 states, 8408 pdfs) pdf-level, by
@@ -36,8 +38,10 @@ SHAPES = {
     "c4_graph": dict(H=3000, K=30000, D=8408, B=2, T=6, lengths=[6, 4], form=ROWS),
     "states_beyond": dict(H=12000, K=40000, D=130, B=2, T=5, lengths=[5, 2], form=GLOBAL),
     "both_beyond": dict(H=11000, K=36000, D=8408, B=1, T=3, lengths=[3], form=GLOBAL),
+    # within the LDS, with a row of more than the 4096 elements the recursion threads hold in registers: four arcs carry pdfs beyond
+    "long_row": dict(H=37, K=150, D=4200, B=2, T=3, lengths=[3, 1], form=LDS),
 }
-BEYOND = [(name, which) for name in SHAPES for which in (None, "phones")] + [("c4_graph", "identity")]
+BEYOND = [(name, which) for name in SHAPES if SHAPES[name]["form"] != LDS for which in (None, "phones")] + [("c4_graph", "identity")]
 _made, _refs = {}, {}
 
 
@@ -121,6 +125,41 @@ def test_the_bits_of_the_lds_form_on_two_byte_rows(name, which, dtype):
     assert lds[0].grad.dtype == dtype and float(lds[0].grad.float().abs().max()) > 0
     for kernels in ("rows", "global"):
         assert _same(_run(case, 0.1, kernels, which, dtype=dtype), lds), kernels
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
+@pytest.mark.parametrize("which", [None, "phones"])
+def test_the_bits_of_the_lds_form_on_a_long_row(which, dtype):
+    """4200 pdfs: the elements beyond 4096 take the tail loops of the row's staging and of the dense companion row, in every form.
+    "rows" and "global" give the bits of "lds"; "lds" is held to the fp64 recursions on the rows it saw (two-byte: the fp32 call
+    on the up-cast input, rounded once, as tests/test_gpu_smbr.py holds them)."""
+    c = SHAPES["long_row"]
+    case = shape("long_row")
+    g, y, lengths, pdfs, probs = case
+    D = c["D"]
+    assert int(g.forward_transitions[:, 2].max()) >= 4096                     # arcs carry pdfs of the tail
+    C = 0 if which is None else int(cr.class_map(which, D).max()) + 1
+    assert _lib.lib().pychain_hip_smbr_form(c["H"], D, C, AUTO) == LDS
+    up = y.to(dtype).float()
+    lds = _run(case, 0.1, "lds", which, dtype=dtype, y=up)
+    assert lds[0].grad.dtype == dtype and float(lds[0].grad.float().abs().max()) > 0 and lds[1].bad_count.tolist() == [0, 0]
+    for kernels in ("rows", "global"):
+        assert _same(_run(case, 0.1, kernels, which, dtype=dtype, y=up), lds), kernels
+    (want, bound, d32, scale), f32 = reference("long_row", which, 0.1), lds
+    if dtype != torch.float32:
+        f32 = _run(case, 0.1, "lds", which, y=up)
+        assert torch.equal(lds[0].grad, f32[0].grad.to(dtype))
+        assert torch.equal(lds[1].per_seq, f32[1].per_seq) and torch.equal(lds[1].closing, f32[1].closing)
+        pd, pr = pdfs.numpy(), probs.numpy()
+        want = (sr.batch(sr.recursions, g, up, lengths, pd, pr, 0.1) if which is None else
+                cr.batch(sr.recursions, g, up, lengths, pd, pr, cr.class_map(which, D), 0.1))
+    dv = sr.value_dist(f32[1].per_seq.cpu().numpy(), want[0])
+    dg = cr.grad_dist(f32[0].grad.cpu().numpy(), want[1], scale)
+    closing = float(f32[1].closing.abs().max())
+    print("long_row %s %s: E %.3g grad %.3g closing %.3g (fp32 reference %.3g, bound %.3g)" % (which, dtype, dv, dg, closing, d32, bound))
+    record_parity("smbr_general_long_row_%s_%s" % (which or "pdf", str(dtype).split(".")[-1]), value=dv, grad=dg, closing=closing,
+                  f32_reference=d32, bound=bound)
+    assert dv <= bound and dg <= bound and closing <= bound
 
 
 # ---- against fp64 beyond the LDS ---------------------------------------------------------------------------------------------------
