@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 30
+#define PYCHAIN_HIP_ABI_VERSION 31
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -955,6 +955,7 @@ int pychain_hip_cpu_smbr_forward_backward_classes(
  *   PYCHAIN_HIP_SMBR_GLOBAL  the state vectors too are read back from the trajectories in the workspace: always runs
  *   PYCHAIN_HIP_SMBR_AUTO    LDS where pychain_hip_smbr_lds_bytes is within 160 KiB, else ROWS where the state vectors fit, else
  *                            GLOBAL
+ * The four codes name the forms of the expected arc counts too (pychain_hip_den_arc_counts_general, below): one set.
  * SAME BITS: thread-to-state and thread-to-pdf ownership, the arc order and the order of every sum are those of the LDS kernels,
  * so on a shape two forms take they give the same gradient, acc_per_seq, closing and bad_count, bit for bit.  No float atomics;
  * a call gives the same bits every time.
@@ -1020,7 +1021,7 @@ int pychain_hip_smbr_forward_backward_general(
  * Launches: p exp(w) once; the recursions, 2B persistent workgroups with one state vector and the frame's row double-buffered in
  * LDS; the counts, time-parallel, a workgroup per run of 64 frames of a sequence with a partial row of num_transitions doubles;
  * log Z_b; the sums.  pychain_hip_den_arc_counts_lds_bytes(num_states, num_pdfs) = (2 H + 2 D + 64) * 4 + 256 must be within
- * 160 KiB: a larger graph is refused with PYCHAIN_HIP_EUNSUPPORTED and the sizes in the message (no general form yet).
+ * 160 KiB: a larger graph is refused with PYCHAIN_HIP_EUNSUPPORTED and the sizes in the message (the general form: below).
  * Workspace: pychain_hip_den_arc_counts_workspace_bytes - the two trajectories, 8 (T+1) H B bytes, and B ceil(T / 64) partial rows.
  * pychain_hip_cpu_den_arc_counts: the host twin, the same equations with fp32 vectors, fp64 sums and host threads over the
  * sequences; fp32 rows and gradient. */
@@ -1043,6 +1044,46 @@ int pychain_hip_cpu_den_arc_counts(
     const float* arc_log_weights, const float* nnet_output, const int64_t* seq_lengths, int B, int T, int num_pdfs,
     float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
     float* grad, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count, int num_threads);
+
+/* ------------------------------------------------------------------------
+ * Expected arc counts on graphs and trees beyond the LDS of a CU (ABI 31; csrc/arc_counts.hip).
+ * pychain_hip_den_arc_counts keeps two state vectors and two rows of a frame in LDS and refuses num_states + num_pdfs > 20416:
+ * 3000 states from about 17 400 pdfs, more than about 20 400 states at any num_pdfs.  The general kernels take any num_states,
+ * num_pdfs and num_transitions the int32 layout holds, with the same equations, checks, outputs and workspace layout, between
+ * the same launches (p exp(w) before; log Z_b and the sums behind); they are slower - what does not fit LDS is gathered from
+ * global memory - and are asked for by name through an entry point of their own.  The forms are sMBR's, PYCHAIN_HIP_SMBR_*:
+ *   LDS     the kernels of pychain_hip_den_arc_counts, launch for launch
+ *   ROWS    the state vectors stay in LDS (pychain_hip_den_arc_counts_general_lds_bytes(num_states) within 160 KiB); the
+ *           frame's row x of a recursion workgroup and the two rows x, x q0 of a count workgroup lie in scratch rows of the
+ *           workspace; the counts run as at most 512 workgroups, persistent over the (sequence, run of 64 frames) items
+ *   GLOBAL  the state vectors too are read back from the trajectories in the workspace: always runs
+ *   AUTO    LDS where pychain_hip_den_arc_counts_lds_bytes is within 160 KiB, else ROWS where the state vectors fit, else GLOBAL
+ * SAME BITS: thread-to-state and thread-to-pdf ownership, the arc order and the order of every sum are those of the LDS kernels,
+ * so on a shape two forms take they give the same counts, counts_per_seq, objf_per_seq, grad and bad_count, bit for bit.  No
+ * float atomics; a call gives the same bits every time.
+ * pychain_hip_den_arc_counts_general_lds_bytes: the LDS of the ROWS form - one double-buffered state vector, the reduction
+ *   scratch and the static LDS: (2 H + 64) * 4 + 256 bytes; 0 for num_states <= 0.
+ * pychain_hip_den_arc_counts_form: host only; the form a call with `requested` would run, or PYCHAIN_HIP_EUNSUPPORTED (LDS or
+ *   ROWS asked for on a shape it cannot hold: the sizes, the bytes and the budget are in the message) or PYCHAIN_HIP_EINVAL
+ *   (sizes that are not positive, an unknown form).
+ * pychain_hip_den_arc_counts_general_workspace_bytes: the layout of pychain_hip_den_arc_counts_workspace_bytes, then per
+ *   recursion workgroup (2 B of them) and per count workgroup (min(B ceil(T / 64), 512)) a row of 2 num_pdfs floats rounded up
+ *   to 64 floats, each region rounded up to 256 bytes; 0 for a size that is not positive.  A call whose form resolves to LDS
+ *   needs pychain_hip_den_arc_counts_workspace_bytes only.
+ * pychain_hip_den_arc_counts_general: the arguments of pychain_hip_den_arc_counts, then `form`; the same argument checks in
+ *   the same order, made before the device is touched. */
+size_t pychain_hip_den_arc_counts_general_lds_bytes(int num_states);
+int pychain_hip_den_arc_counts_form(int num_states, int num_pdfs, int requested);
+size_t pychain_hip_den_arc_counts_general_workspace_bytes(int B, int T, int num_states, int num_transitions, int num_pdfs);
+int pychain_hip_den_arc_counts_general(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* leaky_probs, const float* initial_probs, const float* final_probs,
+    const int32_t* pdf_arcs, const int32_t* pdf_index, int num_states, int num_transitions,
+    const float* arc_log_weights, const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths, int B, int T, int num_pdfs,
+    float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
+    void* grad /* nnet_output_dtype */, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, int form);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

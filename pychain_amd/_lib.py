@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 30
+ABI_VERSION = 31
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -137,6 +137,10 @@ _SIGNATURES = {
     "pychain_hip_den_arc_counts_lds_bytes": (_sz, [_i, _i]),
     "pychain_hip_den_arc_counts": (_i, _SMBR_GRAPH + [_vp] + _ROWS + [_i] * 3 + _ARC_TAIL + _WS + [_vp]),
     "pychain_hip_cpu_den_arc_counts": (_i, _SMBR_GRAPH + [_vp] + _CPU_ROWS + [_i] * 3 + _ARC_TAIL + [_i]),
+    "pychain_hip_den_arc_counts_general_lds_bytes": (_sz, [_i]),
+    "pychain_hip_den_arc_counts_form": (_i, [_i, _i, _i]),
+    "pychain_hip_den_arc_counts_general_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pychain_hip_den_arc_counts_general": (_i, _SMBR_GRAPH + [_vp] + _ROWS + [_i] * 3 + _ARC_TAIL + _WS + [_vp, _i]),
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),

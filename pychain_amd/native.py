@@ -887,11 +887,14 @@ def _arc_weight_args(arc_log_weights, utt_weights, K, B, device):
 
 
 def den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_log_weights=None, utt_weights=None, with_grad=True,
-                   grad_scale=1.0, grad_scale_dev=None, per_seq=False):
+                   grad_scale=1.0, grad_scale_dev=None, per_seq=False, *, form="lds"):
     """Expected arc counts of the denominator on the GPU (include/pychain_hip.h: pychain_hip_den_arc_counts), on the current
     stream.  `gt`: smbr_graph(...); `x` ([B,T,D], fp32 / bf16 / fp16) goes to the kernels as it is.  Returns (objf_per_seq
-    float64 [B], counts float64 [K], counts_per_seq float64 [B,K] or None, grad in x's dtype or None, bad_count int32 [2])."""
+    float64 [B], counts float64 [K], counts_per_seq float64 [B,K] or None, grad in x's dtype or None, bad_count int32 [2]).
+    `form`: "lds" - the entry point above, which refuses a graph and tree beyond the LDS of a CU -, or "auto", "rows", "global":
+    pychain_hip_den_arc_counts_general with that form (any H, D; the bits of "lds" wherever both run)."""
     _require_device(x, "nnet_output")
+    form_code = smbr_form_code(form, who="den_arc_counts")
     if x.dtype not in _DTYPE_CODE:
         raise ValueError("nnet_output must be float32, bfloat16 or float16, got %s" % x.dtype)
     x = x.detach().contiguous()
@@ -909,17 +912,25 @@ def den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_log_w
         grad = torch.empty_like(x) if with_grad else None
         bad = torch.empty(2, dtype=torch.int32, device=dev)
         grad_scale_dev = _dev_scalar(grad_scale_dev, dev)
-        ws = _workspace(L.pychain_hip_den_arc_counts_workspace_bytes(B, T, H, K), dev, "arcs")
-        _lib.check(L.pychain_hip_den_arc_counts(
-            *[t.data_ptr() for t in gt], H, K, _ptr(w), x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
-            float(leaky_coefficient), _ptr(u), float(grad_scale), _ptr(grad_scale_dev), _ptr(grad), objf.data_ptr(), counts.data_ptr(),
-            _ptr(cps), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev)), "pychain_hip_den_arc_counts")
+        if form == "lds":
+            ws = _workspace(L.pychain_hip_den_arc_counts_workspace_bytes(B, T, H, K), dev, "arcs")
+        else:
+            ws = _workspace(L.pychain_hip_den_arc_counts_general_workspace_bytes(B, T, H, K, D), dev, "arcs")
+        args = (*[t.data_ptr() for t in gt], H, K, _ptr(w), x.data_ptr(), _DTYPE_CODE[x.dtype], ld.data_ptr(), B, T, D,
+                float(leaky_coefficient), _ptr(u), float(grad_scale), _ptr(grad_scale_dev), _ptr(grad), objf.data_ptr(), counts.data_ptr(),
+                _ptr(cps), bad.data_ptr(), ws.data_ptr(), ws.numel(), _stream(dev))
+        if form == "lds":
+            _lib.check(L.pychain_hip_den_arc_counts(*args), "pychain_hip_den_arc_counts")
+        else:
+            _lib.check(L.pychain_hip_den_arc_counts_general(*args, form_code), "pychain_hip_den_arc_counts_general")
     return objf, counts, cps, grad, bad
 
 
 def cpu_den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_log_weights=None, utt_weights=None, with_grad=True,
-                       grad_scale=1.0, per_seq=False):
-    """The same on CPU tensors: the host twin (pychain_hip_cpu_den_arc_counts), fp32 rows and gradient."""
+                       grad_scale=1.0, per_seq=False, *, form="lds"):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_den_arc_counts), fp32 rows and gradient.  `form` is checked and
+    changes nothing: the one host twin has no size limit."""
+    smbr_form_code(form, "cpu_den_arc_counts")
     if x.is_cuda:
         raise RuntimeError("pychain_amd: cpu_den_arc_counts is for CPU tensors; device tensors run on the HIP kernels")
     xf, lc = _host_inputs(x, lengths)
