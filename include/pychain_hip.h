@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PYCHAIN_HIP_ABI_VERSION 31
+#define PYCHAIN_HIP_ABI_VERSION 32
 
 /* Element type of the network output [B,T,D] - and of the gradient an entry point writes for it (ABI 14).
  * 2-byte rows are read as they are by the kernels and converted where they land; the gradient is rounded (to nearest even)
@@ -1084,6 +1084,68 @@ int pychain_hip_den_arc_counts_general(
     float leaky_hmm_coefficient, const float* seq_weights, float grad_scale, const float* grad_scale_dev,
     void* grad /* nnet_output_dtype */, double* objf_per_seq, double* counts, double* counts_per_seq, int32_t* bad_count,
     void* workspace, size_t workspace_bytes, void* stream, int form);
+
+/* ------------------------------------------------------------------------
+ * Expected arc counts of the NUMERATOR: the gradient of log P_b in per-sequence arc log-weights (ABI 32; DESIGN.md §3.31;
+ * csrc/num_arcs.hip).  With every arc log-probability lp_k of sequence b's numerator graph replaced by fl32(lp_k + w(b,k)),
+ * w = arc_log_weights [B, num_transitions] in the order of each sequence's forward_transitions,
+ *
+ *   c(b,k) = d log P_b / d w(b,k)
+ *          = sum_{t < L_b} exp(alpha'(t,src_k) + lp_k + w(b,k) + x(t,pdf_k) + beta'(t+1,dst_k) - log P_b)      sums to L_b over k
+ *
+ * alpha', beta' and log P_b those of the weighted graph under the call's time windows (the recursions of
+ * pychain_hip_num_forward_backward_tw), x = clamp(nnet_output, -30, 30).  initial_probs and final_probs are HELD FIXED and not
+ * differentiated; neither is the clamp.  The expected number of times a path of the numerator takes arc k: which pronunciation
+ * or optional-silence arc an utterance takes, how long it stays in each state, and - minus the counts of
+ * pychain_hip_den_arc_counts - the LF-MMI gradient of a parameter that lives in both graphs.
+ *
+ * Arguments: those of pychain_hip_num_forward_backward_tw, with
+ *   arc_log_weights  fp32 [B, num_transitions], any element-aligned start, or NULL.  Weights are per SEQUENCE also where the
+ *                    graph is shared (graph_batch_stride 0): the call then keeps a copy per sequence of the graph in its workspace.
+ *                    A weight that is not finite is counted in bad_count[1] and taken as 0.  Only the weights of a sequence's
+ *                    used arcs - k < the largest forward_transition_indices[h][1] - are read.  The backward arrays must hold the
+ *                    same arcs as the forward ones: an arc's backward copy finds its weight by (source, destination, pdf,
+ *                    log-probability), and arcs equal in all four pair up in order, the r-th with the r-th.
+ *   objf_per_seq     fp64 [B]: log P_b as the recursion found it (-inf without an admissible path, NaN where an arc emits one);
+ *                    rounded to float it is the objf_per_seq of pychain_hip_num_forward_backward_tw
+ *   grad             fp32 [B,T,num_pdfs] or NULL: the occupancies, as pychain_hip_num_forward_backward_tw writes them; NULL
+ *                    skips the occupancy launch.  grad_mode: PYCHAIN_HIP_GRAD_LINEAR or _ACCUM; _LOG is PYCHAIN_HIP_EINVAL
+ *   counts_per_seq   fp64 [B, num_transitions]: c(b,k); exact zeros for the arcs beyond a sequence's used arcs (batch padding)
+ *                    and for a sequence whose log P_b is not finite - the other sequences' bits do not depend on it
+ *   bad_count        int32 [2], zeroed by the call: [0] exactly what pychain_hip_num_forward_backward_tw counts for the same
+ *                    call - with grad = NULL the occupancy checks do not run and only the recursion's verdicts (a log P_b that
+ *                    is not finite, a length outside [1, T]) are counted; [1] the weights that are not finite
+ * IDENTITIES: with arc_log_weights = NULL the graph's own buffers are read and no weight launch runs; with NULL and with all-zero
+ * weights objf, grad and bad_count[0] are bit-identical to pychain_hip_num_forward_backward_tw on the same inputs.  Scattered by
+ * pdf, c(b,.) is the sum over t of that call's LINEAR gradient rows.  No float atomics; two calls give the same bits.
+ * Option num_compat = 1 (the reference's own arithmetic) takes no weights and leaves no log-shares: PYCHAIN_HIP_EUNSUPPORTED.
+ * Launches: fl32(lp + w) in both arc orders (only with weights); the recursions and, with grad, the occupancy pass of
+ * pychain_hip_num_forward_backward_tw on the substituted buffers; the counts, time-parallel - a workgroup per run of 64 frames of
+ * a sequence, every arc with one owner thread, the posterior exp(fl32(alpha' + beta' - log P)(t,src_k) + r_k(t)) in fp32 from the
+ * log-share r_k(t) the backward recursion stored, summed over the run in fp64 in ascending t into a partial row; the partial rows
+ * of a sequence summed in ascending run.  Any num_states, num_transitions and num_pdfs the numerator takes.
+ * pychain_hip_num_arc_counts_workspace_bytes: pychain_hip_num_workspace_bytes, then 8 B num_transitions bytes of weighted
+ *   log-probabilities, a copy per sequence of the other graph arrays (24 B num_transitions + 24 B num_states bytes) and
+ *   B ceil(T / 64) partial rows of num_transitions doubles; 0 for a size that is not positive; monotone in T.
+ * pychain_hip_cpu_num_arc_counts: the host twin - pychain_hip_cpu_num_forward_backward_tw on fl32(lp + w), per-arc posteriors
+ * summed in fp64, sequences on host threads; bad_count[0] counts sequences, as that twin does. */
+size_t pychain_hip_num_arc_counts_workspace_bytes(int B, int T, int num_states, int num_transitions, int num_pdfs);
+int pychain_hip_num_arc_counts(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    const float* arc_log_weights, double* objf_per_seq, float* grad, double* counts_per_seq, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows);
+int pychain_hip_cpu_num_arc_counts(
+    const int32_t* forward_transitions, const int32_t* forward_transition_indices, const float* forward_transition_probs,
+    const int32_t* backward_transitions, const int32_t* backward_transition_indices, const float* backward_transition_probs,
+    const float* initial_probs, const float* final_probs, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths,
+    int B, int T, int num_pdfs, int num_states, int num_transitions, int grad_mode, float grad_scale,
+    const float* arc_log_weights, double* objf_per_seq, float* grad, double* counts_per_seq, int32_t* bad_count,
+    int num_threads, const int32_t* time_windows);
 
 /* ------------------------------------------------------------------------
  * Fused ChainLoss (replaces the two ChainFunction calls + the autograd add of

@@ -32,3 +32,4 @@ from .loss import PosteriorTargets, occupancies, posterior_numerator, posterior_
 from .align import Alignment, alignment_windows, viterbi_align  # noqa: F401
 from .smbr import SMBRFunction, SMBRLoss, expected_accuracy  # noqa: F401
 from .arcs import ArcCounts, DenLogPartitionFunction, den_log_partition, expected_arc_counts  # noqa: F401
+from .arcs import NumArcCounts, NumLogPartitionFunction, num_log_partition, expected_num_arc_counts  # noqa: F401

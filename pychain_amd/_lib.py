@@ -10,7 +10,7 @@ import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PYCHAIN_HIP_LIB") or os.path.join(_HERE, "libpychain_hip.so")  # env: kernel experiments only
-ABI_VERSION = 31
+ABI_VERSION = 32
 TOTALS = 8            # floats of a `totals` buffer (include/pychain_hip.h: PYCHAIN_HIP_TOTALS)
 
 GRAD_LOG, GRAD_LINEAR, GRAD_ACCUM = 0, 1, 2
@@ -51,6 +51,8 @@ _SMBR_GRAPH = [_vp] * 11 + [_i, _i]                                          # t
 _SMBR_CLASSES = [_vp, _i, _i]                                                # pdf_classes, num_classes, targets_are_classes
 _SMBR_TAIL = [_vp, _vp, _i, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp]            # targets, K, frame_acc, coef, grad_scale[_dev], grad, acc, closing, bad
 _ARC_TAIL = [_f, _vp, _f, _vp, _vp, _vp, _vp, _vp, _vp]                          # coef, seq_weights, grad_scale[_dev], grad, objf, counts, counts_per_seq, bad
+
+_NUM_ARC_OUT = [_i, _f, _vp, _vp, _vp, _vp, _vp]   # grad_mode, grad_scale, arc_log_weights, objf_per_seq, grad, counts_per_seq, bad_count
 
 _SIGNATURES = {
     "pychain_hip_abi_version": (_i, []),
@@ -141,6 +143,10 @@ _SIGNATURES = {
     "pychain_hip_den_arc_counts_form": (_i, [_i, _i, _i]),
     "pychain_hip_den_arc_counts_general_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "pychain_hip_den_arc_counts_general": (_i, _SMBR_GRAPH + [_vp] + _ROWS + [_i] * 3 + _ARC_TAIL + _WS + [_vp, _i]),
+    # (ABI 32: expected arc counts of the numerator - the gradient of log P_b in per-sequence arc log-weights)
+    "pychain_hip_num_arc_counts_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "pychain_hip_num_arc_counts": (_i, _GRAPHS + _ROWS + _SIZES + _NUM_ARC_OUT + _WS + [_vp, _vp]),      # ..., stream, time_windows
+    "pychain_hip_cpu_num_arc_counts": (_i, _GRAPHS + _CPU_ROWS + _SIZES + _NUM_ARC_OUT + [_i, _vp]),   # ..., num_threads, time_windows
     "pychain_hip_cpu_calls": (ctypes.c_long, []),
     "pychain_hip_cpu_den_forward_backward": (_i, [_vp] * 9 + [_i, _vp, _i, _vp, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _i]),
     "pychain_hip_cpu_num_forward_backward": (_i, _CPU_NUM),
@@ -199,7 +205,7 @@ def lib():
     return _lib
 
 
-OPTIONS = ("verbose", "den_phase_mask", "den_lazy", "den_dma", "den_segments", "den_pair", "gamma16", "debug_corrupt_row", "num_compat", "den_tseg", "den_tburn", "plan_split", "chain_slices", "den_sg", "den_cross", "den_q")
+OPTIONS = ("verbose", "den_phase_mask", "den_lazy", "den_dma", "den_segments", "den_pair", "gamma16", "debug_corrupt_row", "num_compat", "den_tseg", "den_tburn", "plan_split", "chain_slices", "den_sg", "den_cross", "den_q", "num_arcs_gather")
 
 _thread_values = threading.local()       # what this thread's overrides currently are (for restoring)
 

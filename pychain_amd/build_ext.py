@@ -17,9 +17,9 @@ INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 LIB = os.path.join(_HERE, "libpychain_hip.so")
 OBJ = os.path.join(os.path.dirname(_HERE), "build", "obj")
 SOURCES = ["den_rec.hip", "den_lazy.hip", "den_kernels.hip", "plan.cpp", "fst.cpp", "pack.cpp", "cpu.cpp", "den_general.hip", "num_kernels.hip", "num_general.hip", "num_compat.hip",
-           "align.hip", "api.hip", "den_policy.hip", "xent.hip", "outreg.hip", "weights.hip", "post.hip", "boost.hip", "smbr.hip", "smbr_general.hip", "arc_counts.hip"]         # (the slowest translation units first: they are compiled side by side)
+           "align.hip", "api.hip", "den_policy.hip", "xent.hip", "outreg.hip", "weights.hip", "post.hip", "boost.hip", "smbr.hip", "smbr_general.hip", "arc_counts.hip", "num_arcs.hip"]         # (the slowest translation units first: they are compiled side by side)
 HEADERS = ["common.h", "plan_format.h", "den_kernels.h", "num_kernels.h", "device_utils.h", "den_common.inc.h", "den_lazy.inc.h",
-           "den_pair.inc.h", "call_args.h", "den_policy.h", "xent.h", "row_access.h", "post.h", "boost.h", "smbr.h", "smbr_device.h"]
+           "den_pair.inc.h", "call_args.h", "den_policy.h", "xent.h", "row_access.h", "post.h", "boost.h", "smbr.h", "smbr_device.h", "num_arcs.h"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-fno-slp-vectorize"]   # v_pk_*_f32 pairs cost v_movs and lengthen the dependent chains here
 

@@ -16,6 +16,7 @@
 #include "den_kernels.h"
 #include "den_policy.h"
 #include "device_utils.h"
+#include "num_arcs.h"
 #include "num_kernels.h"
 #include "plan_format.h"
 #include "xent.h"
@@ -35,7 +36,7 @@ OptionTable& thread_options() { static thread_local OptionTable t; return t; }  
 struct OptionSpec { const char* name; int dflt; };
 const OptionSpec kOptions[] = {{"verbose", 0}, {"den_phase_mask", 3}, {"den_lazy", 1}, {"den_dma", -1}, {"den_segments", 0}, {"den_pair", -1},
                                {"gamma16", 0}, {"debug_corrupt_row", 0}, {"num_compat", 0}, {"den_tseg", -1}, {"den_tburn", 192},
-                               {"plan_split", -1}, {"chain_slices", -1}, {"den_sg", 1}, {"den_cross", 0}, {"den_q", 0}};
+                               {"plan_split", -1}, {"chain_slices", -1}, {"den_sg", 1}, {"den_cross", 0}, {"den_q", 0}, {"num_arcs_gather", 0}};
 const OptionSpec* find_option(const char* name) {
   if (!name) return nullptr;
   for (const OptionSpec& o : kOptions) if (strcmp(o.name, name) == 0) return &o;
@@ -78,6 +79,7 @@ CallKnobs call_knobs() {
   k.chain_slices = option_int("chain_slices");
   k.den_sg = option_int("den_sg") ? 1 : 0;
   k.den_q = option_int("den_q") ? 1 : 0;          // (off by default: the frame is bound by VALU issue, not by the LDS time it saves - DESIGN.md 3.16)
+  k.num_arcs_gather = option_int("num_arcs_gather") ? 1 : 0;   // (test aid: the gathered form of num_arc_count_kernel where the staged one fits - DESIGN.md 3.31)
   k.den_cross = option_int("den_cross") ? 1 : 0;   // (off by default: measured slower than the streamed occupancy launch - DESIGN.md 3.15)
   std::string v;
   if (option_value("debug_corrupt_row", &v)) {   // "den,b,t,scale" / "num,b,t,scale"
@@ -632,6 +634,93 @@ extern "C" int pychain_hip_num_forward_backward(
   return pychain_hip_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, nnet_output_dtype,
                                              seq_lengths, B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count,
                                              workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- expected arc counts of the numerator (include/pychain_hip.h: pychain_hip_num_arc_counts; num_arcs.hip)
+namespace {
+// the numerator's workspace (num_carve), then: the float objective the recursion writes, lp + w in both arc orders, a copy per
+// sequence of a shared graph's other arrays (used only by a call with weights on a shared graph; always carved: the size query
+// does not know the stride), the partial rows
+struct NumArcCarve { size_t objf, wf, wb, rft, rbt, rfi, rbi, rinit, rfin, partial, total; int nrun; };
+NumArcCarve num_arc_carve(int B, int T, int H, int K, int D, bool compat) {
+  NumArcCarve c;
+  const size_t b = B, probs = align256(4 * b * K), trans = align256(12 * b * K), idx = align256(8 * b * H), vec = align256(4 * b * H);
+  c.nrun = (T + kNumArcFrames - 1) / kNumArcFrames;
+  size_t o = align256(num_carve(B, T, H, K, D, compat).total);
+  c.objf = o; o += align256(4 * b);
+  c.wf = o; o += probs; c.wb = o; o += probs;
+  c.rft = o; o += trans; c.rbt = o; o += trans;
+  c.rfi = o; o += idx; c.rbi = o; o += idx;
+  c.rinit = o; o += vec; c.rfin = o; o += vec;
+  c.partial = o; o += align256(8 * b * c.nrun * K);
+  c.total = o + 256;                                 // (the base is aligned inside the caller's buffer)
+  return c;
+}
+}  // namespace
+
+extern "C" size_t pychain_hip_num_arc_counts_workspace_bytes(int B, int T, int H, int K, int D) {
+  if (B <= 0 || T <= 0 || H <= 0 || K <= 0 || D <= 0) return 0;
+  return num_arc_carve(B, T, H, K, D, false).total;
+}
+
+extern "C" int pychain_hip_num_arc_counts(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const void* nnet_output, int nnet_output_dtype, const int64_t* seq_lengths,
+    int B, int T, int D, int H, int K, int grad_mode, float grad_scale, const float* arc_log_weights,
+    double* objf_per_seq, float* grad, double* counts_per_seq, int32_t* bad_count,
+    void* workspace, size_t workspace_bytes, void* stream, const int32_t* time_windows) {
+  const char* who = "num_arc_counts";
+  if (!counts_per_seq || !objf_per_seq) return null_pointer(who);
+  if (int rc = bad_sizes(who, B, T, H, K, D)) return rc;
+  if (grad_mode != PYCHAIN_HIP_GRAD_LINEAR && grad_mode != PYCHAIN_HIP_GRAD_ACCUM)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: grad_mode must be PYCHAIN_HIP_GRAD_LINEAR or PYCHAIN_HIP_GRAD_ACCUM, got %d (the log form is "
+                "the reference's contract for its own gradient, not a gradient beside arc counts)", who, grad_mode);
+  const CallKnobs knobs = call_knobs();
+  if (knobs.num_compat)
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: option num_compat (the reference's own arithmetic) takes no arc weights and leaves no "
+                "arc log-shares to count from", who);
+  const NumArcCarve c = num_arc_carve(B, T, H, K, D, false);
+  if (!workspace) return null_pointer(who);
+  if (workspace_bytes < c.total) return fail(PYCHAIN_HIP_EWORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, c.total);
+  char* ws = ws_base(workspace);
+  NumArgs a;
+  if (int rc = fill_num_args(a, NumGraphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K},
+                             Rows{nnet_output, nnet_output_dtype, seq_lengths, B, T, D}, grad_mode, grad_scale, (float*)(ws + c.objf),
+                             grad ? (void*)grad : (void*)ws, bad_count, Workspace{workspace, workspace_bytes}, who, time_windows)) return rc;
+  if (a.x_half && !num_half_native(a))
+    return fail(PYCHAIN_HIP_EUNSUPPORTED, "%s: this shape does not take 2-byte network outputs (pychain_hip_num_half_native)", who);
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(bad_count, 0, 2 * sizeof(int32_t), st) != hipSuccess)
+    return fail(PYCHAIN_HIP_ELAUNCH, "%s: hipMemsetAsync failed", who);
+  const char* why = nullptr;
+  hipError_t e = hipSuccess;
+  if (arc_log_weights) {
+    // the weighted graph: two substituted probability buffers [B,K] - and, for a shared graph, a copy per sequence of the
+    // arrays they are indexed with, so that the recursion kernels run as they are (one stride for all of a graph's arrays)
+    NumArcWeightArgs w;
+    memset(&w, 0, sizeof(w));
+    w.ft = ft; w.fi = fi; w.fp = fp; w.bt = bt; w.bi = bi; w.bp = bp; w.initial = initial; w.final_ = final_;
+    w.graph_stride = graph_batch_stride; w.B = B; w.H = H; w.K = K; w.w = arc_log_weights;
+    w.wf = (float*)(ws + c.wf); w.wb = (float*)(ws + c.wb); w.bad = bad_count + 1;
+    if (graph_batch_stride == 0) {
+      w.rft = (int32_t*)(ws + c.rft); w.rbt = (int32_t*)(ws + c.rbt); w.rfi = (int32_t*)(ws + c.rfi); w.rbi = (int32_t*)(ws + c.rbi);
+      w.rinit = (float*)(ws + c.rinit); w.rfin = (float*)(ws + c.rfin);
+      a.fwd_trans = w.rft; a.bwd_trans = w.rbt; a.fwd_idx = w.rfi; a.bwd_idx = w.rbi; a.initial = w.rinit; a.final_ = w.rfin;
+      a.graph_stride = 1;
+    }
+    a.fwd_probs = w.wf; a.bwd_probs = w.wb;
+    e = launch_num_arc_weights(w, st);
+  }
+  if (e == hipSuccess) e = launch_num_fb(a, st, &why);
+  if (e == hipSuccess && a.corrupt_b >= 0) e = launch_num_corrupt(a, st);
+  if (e == hipSuccess && grad) e = launch_num_occ(a, false, st, &why);
+  if (e == hipSuccess) {
+    NumArcArgs ca;
+    ca.n = a; ca.partial = (double*)(ws + c.partial); ca.counts = counts_per_seq; ca.objf = objf_per_seq; ca.nrun = c.nrun;
+    e = launch_num_arc_counts(ca, knobs.num_arcs_gather != 0, st);
+  }
+  return e == hipSuccess ? PYCHAIN_HIP_OK : launch_failed(who, e, why);
 }
 
 // ---- fused ChainLoss ------------------------------------------------------------------

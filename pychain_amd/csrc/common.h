@@ -34,6 +34,7 @@ struct CallKnobs {
   int den_sg;                 // 0: never the one-gather form of the lazy recursions for "pdf by state" plans (den_lazy.inc.h: SG); default 1
   int den_q;                  // 0: never the one-word state vectors of the lazy recursions (den_lazy.inc.h: MAP::kQ; launch hint bit 19); default 0
   int den_cross;              // 0: the recursions of a pdf-by-state plan never emit occupancies themselves (den_lazy.inc.h: XF); default 0
+  int num_arcs_gather;        // 1: pychain_hip_num_arc_counts sums the counts with the gathered form of its kernel also where the LDS-staged one fits; default 0
   int chain_slices;           // the fused loss over a batch larger than the chip: -1 automatic, 0 / 1 one call, n >= 2 that many slices (api.hip: chain_loss_slices)
   int plan_split;             // pychain_hip_den_plan_build: 0 = no state on more than one lane (plans of one batch with a stride must have
                               // the same number of positions), -1 = automatic (plan.cpp, "states on several lanes")

@@ -149,8 +149,12 @@ struct Lse64 {
 };
 // win: the sequence's alignment time windows, {lo, hi} per state, or nullptr (include/pychain_hip.h: pychain_hip_*_tw): a state
 // outside its window gets -inf, selected after its log-sum as on the device, and its arcs carry no occupancy
+// counts (pychain_hip_cpu_num_arc_counts): fp64 [fwd arcs] or nullptr - every forward arc's occupancy summed over the frames, left
+// as it is (zeros) for a sequence without a finite log-probability; logp_out: the fp64 log-probability; grad may then be nullptr:
+// the occupancy checks do not run and only the recursion's verdict is returned
 bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin, const float* x, int L, int T, int D, int H,
-             int grad_mode_flags, float gscale, float* objf, float* grad, const int32_t* win) {
+             int grad_mode_flags, float gscale, float* objf, float* grad, const int32_t* win, double* counts = nullptr,
+             double* logp_out = nullptr) {
   // (PYCHAIN_HIP_CPU_NO_CLAMP: the network output as it is - the contract of pychain_C.forward_backward_log_domain, whose C++
   // does not clamp (chain-log-domain-computation.cc:137-145); ChainFunction's clamp(-30, 30), pychain/loss.py:30, otherwise)
   const bool clamp = (grad_mode_flags & PYCHAIN_HIP_CPU_NO_CLAMP) == 0;
@@ -175,10 +179,13 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
   Lse64 tl;
   for (int h = 0; h < H; h++) tl.push(alpha[(size_t)L * H + h] + (double)fin[h]);
   const double logp = tl.value();
-  *objf = (float)logp;
+  if (objf) *objf = (float)logp;
+  if (logp_out) *logp_out = logp;
   if (!std::isfinite(logp)) ok = false;
+  if (!grad && (!counts || !ok)) return ok;
+  if (!ok) counts = nullptr;
   const float fill = grad_mode == PYCHAIN_HIP_GRAD_LOG ? -std::numeric_limits<float>::infinity() : 0.f;
-  if (grad_mode != PYCHAIN_HIP_GRAD_ACCUM) for (size_t i = 0; i < (size_t)T * D; i++) grad[i] = fill;
+  if (grad && grad_mode != PYCHAIN_HIP_GRAD_ACCUM) for (size_t i = 0; i < (size_t)T * D; i++) grad[i] = fill;
   double* bn = beta.data() + (size_t)(L & 1) * H;
   for (int h = 0; h < H; h++) bn[h] = adm(h, L) ? (double)fin[h] : ninf;
   std::vector<int> touched;
@@ -187,7 +194,7 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
     const double* a = alpha.data() + (size_t)t * H;
     const double* nb = beta.data() + (size_t)((t + 1) & 1) * H;
     double* b = beta.data() + (size_t)(t & 1) * H;
-    float* g = grad + (size_t)t * D;
+    float* g = grad ? grad + (size_t)t * D : nullptr;
     touched.clear();
     double fsum = 0.0;
     for (int h = 0; h < H; h++) {
@@ -198,11 +205,14 @@ bool num_one(const Csr& fwd, const Csr& bwd, const float* init, const float* fin
         const double term = (double)fwd.prob[k] + nb[fwd.trans[3 * k + 1]] + (double)xv(xr[pdf]);
         acc.push(term);
         const double o = std::exp(a[h] + term - logp);          // occupancy of the arc (0 where a state cannot be reached)
+        if (counts && o == o) counts[k] += o;
+        if (!grad) continue;
         if (o > 0.0) { if (occ[pdf] == 0.0) touched.push_back(pdf); occ[pdf] += o; fsum += o; }
         else if (o != o) ok = false;
       }
       b[h] = acc.value();
     }
+    if (!grad) continue;
     if (t == 0 && !(std::fabs(fsum - 1.0) <= 0.05)) ok = false;    // chain-log-domain-computation.cc:283-304
     for (int pdf : touched) {
       const double o = occ[pdf];
@@ -367,6 +377,87 @@ extern "C" int pychain_hip_cpu_num_forward_backward(
     float* objf_per_seq, float* grad, int32_t* bad_count, int num_threads) {
   return pychain_hip_cpu_num_forward_backward_tw(ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, nnet_output, seq_lengths,
                                                  B, T, D, H, K, grad_mode, grad_scale, objf_per_seq, grad, bad_count, num_threads, nullptr);
+}
+
+// ---- expected arc counts of the numerator (include/pychain_hip.h: pychain_hip_cpu_num_arc_counts; the device's num_arcs.hip):
+// the twin of pychain_hip_cpu_num_forward_backward_tw on fl32(lp + w), every arc's posteriors summed in fp64
+namespace pychain_hip {
+namespace {
+inline int used_arcs(const int32_t* idx, int H, int K) {
+  int kmax = 0;
+  for (int h = 0; h < H; h++) kmax = idx[2 * h + 1] > kmax ? idx[2 * h + 1] : kmax;
+  return kmax < K ? kmax : K;
+}
+// fl32(lp + w) of one sequence in the forward (wf) and in the backward (wb) order; the weights that are not finite (taken as 0)
+int weighted_probs(const Csr& fwd, const Csr& bwd, const float* w, int H, int K, float* wf, float* wb) {
+  const int Kf = used_arcs(fwd.idx, H, K), Kb = used_arcs(bwd.idx, H, K);
+  int bad = 0;
+  for (int k = 0; k < K; k++) {
+    float v = 0.f;                                                             // (padding arcs are not read)
+    if (k < Kf) {
+      float wk = w[k];
+      if (!std::isfinite(wk)) { bad++; wk = 0.f; }
+      v = fwd.prob[k] + wk;
+    }
+    wf[k] = v;
+  }
+  for (int k = 0; k < K; k++) {
+    float v = 0.f;
+    if (k < Kb) {
+      const int src = bwd.trans[3 * k], dst = bwd.trans[3 * k + 1], pdf = bwd.trans[3 * k + 2];
+      const float p = bwd.prob[k];
+      v = p;
+      if (src >= 0 && src < H && dst >= 0 && dst < H) {
+        int rank = 0;
+        for (int j = bwd.idx[2 * dst] > 0 ? bwd.idx[2 * dst] : 0; j < k; j++)
+          if (bwd.trans[3 * j] == src && bwd.trans[3 * j + 2] == pdf && bwd.prob[j] == p) rank++;
+        const int j1 = fwd.idx[2 * src + 1] < Kf ? fwd.idx[2 * src + 1] : Kf;
+        for (int j = fwd.idx[2 * src] > 0 ? fwd.idx[2 * src] : 0; j < j1; j++)
+          if (fwd.trans[3 * j + 1] == dst && fwd.trans[3 * j + 2] == pdf && fwd.prob[j] == p && rank-- == 0) {
+            if (std::isfinite(w[j])) v = p + w[j];
+            break;
+          }
+      }
+    }
+    wb[k] = v;
+  }
+  return bad;
+}
+}  // namespace
+}  // namespace pychain_hip
+
+extern "C" int pychain_hip_cpu_num_arc_counts(
+    const int32_t* ft, const int32_t* fi, const float* fp, const int32_t* bt, const int32_t* bi, const float* bp,
+    const float* initial, const float* final_, int graph_batch_stride,
+    const float* nnet_output, const int64_t* seq_lengths, int B, int T, int D, int H, int K, int grad_mode, float grad_scale,
+    const float* arc_log_weights, double* objf_per_seq, float* grad, double* counts_per_seq, int32_t* bad_count, int num_threads,
+    const int32_t* time_windows) {
+  const char* who = "cpu_num_arc_counts";
+  const NumGraphs graphs{ft, fi, fp, bt, bi, bp, initial, final_, graph_batch_stride, H, K};
+  int rc = check_common(who, graphs, Rows{nnet_output, PYCHAIN_HIP_F32, seq_lengths, B, T, D}, objf_per_seq, counts_per_seq, bad_count);
+  if (rc != PYCHAIN_HIP_OK) return rc;
+  if ((rc = bad_stride(who, graph_batch_stride)) != PYCHAIN_HIP_OK) return rc;
+  if (grad_mode != PYCHAIN_HIP_GRAD_LINEAR && grad_mode != PYCHAIN_HIP_GRAD_ACCUM)
+    return fail(PYCHAIN_HIP_EINVAL, "%s: grad_mode must be PYCHAIN_HIP_GRAD_LINEAR or PYCHAIN_HIP_GRAD_ACCUM, got %d", who, grad_mode);
+  g_cpu_calls++;
+  std::atomic<int> bad{0}, bad_w{0};
+  for_each_sequence(B, num_threads, [&](int b) {
+    const NumGraphs g = graphs.at(b);
+    Csr fwd = fwd_of(g), bwd = bwd_of(g);
+    std::vector<float> wf, wb;
+    if (arc_log_weights) {
+      wf.resize(K); wb.resize(K);
+      bad_w += weighted_probs(fwd, bwd, arc_log_weights + (size_t)b * K, H, K, wf.data(), wb.data());
+      fwd.prob = wf.data(); bwd.prob = wb.data();
+    }
+    double* counts = counts_per_seq + (size_t)b * K;
+    std::fill(counts, counts + K, 0.0);
+    const bool ok = num_one(fwd, bwd, g.initial, g.final_, nnet_output + (size_t)b * T * D, (int)seq_lengths[b], T, D, H, grad_mode, grad_scale,
+                            nullptr, grad ? grad + (size_t)b * T * D : nullptr, window_row(time_windows, b, H), counts, objf_per_seq + b);
+    if (!ok) bad++;
+  });
+  bad_count[0] = bad.load(); bad_count[1] = bad_w.load();
+  return PYCHAIN_HIP_OK;
 }
 
 extern "C" int pychain_hip_cpu_align_tw(

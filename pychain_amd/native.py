@@ -949,6 +949,85 @@ def cpu_den_arc_counts(gt, num_states, x, lengths, leaky_coefficient=1e-5, arc_l
     return objf, counts, cps, grad, bad
 
 
+def _num_arc_weights(arc_log_weights, B, K, device):
+    """arc_log_weights float32 [B,K] contiguous on `device` as the numerator's arc-count entry points read them (one element at
+    a time: any element-aligned start); None stays None."""
+    w = arc_log_weights
+    if w is None:
+        return None
+    if not torch.is_tensor(w) or not w.is_floating_point():
+        raise ValueError("arc_log_weights must be a float tensor [%d, %d], got %s" % (B, K, getattr(w, "dtype", type(w))))
+    if tuple(w.shape) != (B, K):
+        raise ValueError("arc_log_weights must have one entry per sequence and arc, [%d, %d], got %s" % (B, K, list(w.shape)))
+    return w.detach().to(device=device, dtype=torch.float32, non_blocking=True).contiguous()
+
+
+def num_arc_counts(gt, graph_stride, num_states, x, lengths, arc_log_weights=None, with_grad=False, grad_mode=_lib.GRAD_LINEAR,
+                   grad_scale=1.0, grad_out=None, windows=None):
+    """Expected arc counts of the numerator on the GPU (include/pychain_hip.h: pychain_hip_num_arc_counts), on the current stream,
+    without a host synchronisation.  `gt`, `graph_stride`, `windows`: as num_forward_backward takes them; `arc_log_weights`:
+    float [B,K] or None.  Returns (objf_per_seq float64 [B], counts_per_seq float64 [B,K], grad float32 [B,T,D] or None,
+    bad_count int32 [2])."""
+    _require_device(x, "nnet_output")
+    x = _kernel_tensor(x)
+    B, T, D = x.shape
+    _check_lengths(lengths, B, T)
+    K = gt["forward_transitions"].shape[1]
+    L = _lib.lib()
+    dev = x.device
+    with torch.cuda.device(dev):
+        w = _num_arc_weights(arc_log_weights, B, K, dev)
+        x, xcode = _rows_as_given(x, lambda: L.pychain_hip_num_half_native(int(num_states), K, D))
+        ld = _lengths_dev(lengths, dev)
+        objf = torch.empty(B, dtype=torch.float64, device=dev)
+        counts = torch.empty(B, K, dtype=torch.float64, device=dev)
+        grad = None
+        if grad_mode == _lib.GRAD_ACCUM:
+            if grad_out is None:
+                raise ValueError("GRAD_ACCUM needs grad_out")
+            grad = grad_out
+        elif with_grad:
+            grad = torch.empty(x.shape, dtype=torch.float32, device=dev)
+        gk, put_back = _kernel_buffer(grad)
+        bad = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = _workspace(L.pychain_hip_num_arc_counts_workspace_bytes(B, T, int(num_states), K, D), dev, "num_arcs")
+        if windows is not None:
+            windows = _check_windows(windows, B, int(num_states), dev)
+        _lib.check(L.pychain_hip_num_arc_counts(
+            *_graph_ptrs(gt), int(graph_stride), x.data_ptr(), xcode, ld.data_ptr(), B, T, D, int(num_states), K, int(grad_mode),
+            float(grad_scale), _ptr(w), objf.data_ptr(), _ptr(gk), counts.data_ptr(), bad.data_ptr(), ws.data_ptr(), ws.numel(),
+            _stream(dev), _ptr(windows)), "pychain_hip_num_arc_counts")
+        put_back()
+    return objf, counts, grad, bad
+
+
+def cpu_num_arc_counts(graphs, x, lengths, arc_log_weights=None, with_grad=False, grad_mode=_lib.GRAD_LINEAR, grad_scale=1.0,
+                       grad_out=None, windows=None):
+    """The same on CPU tensors: the host twin (pychain_hip_cpu_num_arc_counts).  `graphs`: the ChainGraphBatch."""
+    if x.is_cuda:
+        raise RuntimeError("pychain_amd: cpu_num_arc_counts is for CPU tensors; device tensors run on the HIP kernels")
+    xf, lc = _host_inputs(x, lengths)
+    B, T, D = xf.shape
+    ts, stride = _cpu_graph(graphs, False)
+    H, K = int(ts[1].shape[-2]), int(ts[0].shape[-2])
+    w = _num_arc_weights(arc_log_weights, B, K, torch.device("cpu"))
+    objf = torch.empty(B, dtype=torch.float64)
+    counts = torch.empty(B, K, dtype=torch.float64)
+    grad = None
+    if grad_mode == _lib.GRAD_ACCUM:
+        if grad_out is None:
+            raise ValueError("GRAD_ACCUM needs grad_out")
+        grad = grad_out
+    elif with_grad:
+        grad = torch.empty(B, T, D, dtype=torch.float32)
+    bad = torch.zeros(2, dtype=torch.int32)
+    tw = None if windows is None else _check_windows(windows.cpu(), B, H)
+    _lib.check(_lib.lib().pychain_hip_cpu_num_arc_counts(
+        *[t.data_ptr() for t in ts], stride, xf.data_ptr(), lc.data_ptr(), B, T, D, H, K, int(grad_mode), float(grad_scale), _ptr(w),
+        objf.data_ptr(), _ptr(grad), counts.data_ptr(), bad.data_ptr(), int(CPU_THREADS), _ptr(tw)), "pychain_hip_cpu_num_arc_counts")
+    return objf, counts, grad, bad
+
+
 def topk_rows(rows, lengths, k, floor=0.0, normalize=True):
     """Sparse targets out of dense posterior rows on the GPU (include/pychain_hip.h: pychain_hip_topk_rows), on the current
     stream: `rows` [B,T,D] in fp32 / bf16 / fp16 as it is.  Returns (pdfs int32 [B,T,k], probs float32 [B,T,k])."""
